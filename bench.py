@@ -12,6 +12,10 @@ occupancy (the refreshed grid is computed and discarded) so that the number of s
 ~65.  Inputs (rays, ground-truth colours, occupancy) are resident in HBM before the timed region starts.
 
 metric  : training samples/s = sum over steps and ranks of the samples actually marched (counter[0]) / wall time
+plain run (default): set up, warm up, time --steps steps, write --dump-outputs if asked, print the line.  Everything below that is not
+          the headline (roofline, dropin_path, cpu_baseline, the 800x800 frame, the strong-scaling line, the config 4 / 5 and
+          evolving-occupancy workloads, the 1-rank RCCL probe, --pmc) runs only with --full; in a plain run its keys are null.
+--dump-outputs DIR: the loss of the last timed step and the parameters after it as .npy files (dump_outputs).
 execution: the iteration is captured once into a HIP graph (torch-ngp_amd/graph.py) and replayed per step; --no-graph issues
           every launch eagerly, --no-fused uses the reference-style module-by-module network path.
 lookahead (N = 1, default; --no-lookahead switches it off): the batch pool plays the data loader, which knows its next batch one step early;
@@ -855,15 +859,48 @@ def canary_child(args, dev, world, rank):
     return ok and same, f"{res['elapsed'] / n_steps * 1e3:.4f} ms/step, capture_error={str(st.capture_error)[:80]}, shadows agree={same}"
 
 
+DUMP_SAMPLE = 1 << 21   # parameters of a larger tensor that --dump-outputs writes (a fixed, seeded sample)
+
+
+def dump_outputs(run, res, out_dir, rank):
+    """`--dump-outputs DIR`: what the timed path computed in its last step, as its caller receives it -- the step's loss (`loss.npy`,
+    float64) and the model's parameters after its update (`param_<name>.npy`, float32; a tensor of more than DUMP_SAMPLE values -- the
+    hash table -- as the values at DUMP_SAMPLE sorted indices drawn once with numpy seed 0, so two runs or two builds compare index for
+    index).  The inputs (parameters, batches, sampling noise) are seeded: the same arguments give the same inputs.  Rank 0 writes;
+    a sharded update first gathers the full fp32 weights on every rank (collective)."""
+    opt = run.optimizer
+    if getattr(opt, 'shard', False):
+        opt.wait_shadows()
+        opt.gather_master()
+    run.stepper.sync_params()
+    torch.cuda.synchronize()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), np.array([res['final_loss']], np.float64))
+    for name, p in run.model.named_parameters():
+        v = p.detach().reshape(-1).float()
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_SAMPLE, replace=False))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(out_dir, f"param_{name.replace('.', '_')}.npy"), v.cpu().numpy().astype(np.float32))
+
+
 def self_launch(args):
-    """`python bench.py --gpus N` (N > 1) started WITHOUT a launcher: replace this process by
+    """`python bench.py --gpus N` (N > 1) started WITHOUT a launcher: run
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>`,
-    one rank per GPU.  Fails loudly when the node has fewer than N devices (NGP_BENCH_SHARE_GPU=1, the one-GPU functional-test hook,
-    lifts that check) -- it never falls back to measuring one GPU under an `n_gpus: N` request."""
+    one rank per GPU, as a child process and exit with its return code.  This process never opens the GPU itself (the device count comes
+    from a short child of its own), so it does not hold a device while the ranks run.  Fails loudly when the node has fewer than N devices
+    (NGP_BENCH_SHARE_GPU=1, the one-GPU functional-test hook, lifts that check) -- it never falls back to measuring one GPU under an
+    `n_gpus: N` request."""
+    import signal
     import socket
-    have = torch.cuda.device_count()
-    if have < args.gpus and os.environ.get('NGP_BENCH_SHARE_GPU') != '1':
-        raise SystemExit(f'bench.py: --gpus {args.gpus} but only {have} GPU(s) are visible; refusing to benchmark fewer ranks than asked for')
+    import subprocess
+    if os.environ.get('NGP_BENCH_SHARE_GPU') != '1':
+        probe = subprocess.run([sys.executable, '-c', 'import torch; print(torch.cuda.device_count())'], capture_output=True, text=True, timeout=300)
+        have = int(probe.stdout.strip().splitlines()[-1]) if probe.returncode == 0 and probe.stdout.strip() else 0
+        if have < args.gpus:
+            raise SystemExit(f'bench.py: --gpus {args.gpus} but only {have} GPU(s) are visible; refusing to benchmark fewer ranks than asked for')
     with socket.socket() as sk:
         sk.bind(('127.0.0.1', 0))
         port = sk.getsockname()[1]
@@ -873,7 +910,17 @@ def self_launch(args):
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')   # dmabuf IPC: what RCCL needs on this host driver
     env.setdefault('OMP_NUM_THREADS', '4')
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    if args.watchdog > 0:
+        import faulthandler
+        faulthandler.cancel_dump_traceback_later()   # every rank keeps its own watchdog; this process only waits for them
+    proc = subprocess.Popen(cmd, env=env)
+
+    def forward(sig, _frame):
+        proc.send_signal(sig)   # (a time limit around this process reaches the launcher, which stops the ranks)
+    for sig in (signal.SIGTERM, signal.SIGINT):
+        signal.signal(sig, forward)
+    rc = proc.wait()
+    raise SystemExit(rc if rc >= 0 else 128 - rc)
 
 
 def main():
@@ -922,14 +969,23 @@ def main():
                     help="sharded update: how the global skip verdict travels (optim.NGPAdam(verdict=...))")
     ap.add_argument('--watchdog', type=float, default=900.0, help='seconds after which a run that has not finished dumps every thread\'s stack to stderr '
                     'and exits non-zero (a hung collective must not hang the box); 0 disables')
+    ap.add_argument('--full', action='store_true', help='also run everything beside the headline: roofline rows, the 800x800 frame, the strong-scaling '
+                    'line (N > 1), the drop-in path, the config 4 / 5 and evolving-occupancy workloads, the 1-rank RCCL probe and the CPU baseline '
+                    '(each still switched off by its own --no-* option).  Without it the run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if not args.full:
+        if args.pmc:
+            ap.error('--pmc measures the traffic of the roofline rows, which only a --full run has')
+        args.no_roofline = args.no_render = args.no_strong = args.no_dropin = args.no_extra = args.no_ddp_probe = args.no_cpu_baseline = True
     if args.watchdog > 0:
         import faulthandler
         faulthandler.dump_traceback_later(args.watchdog, exit=True)
 
-    assert torch.cuda.is_available(), 'bench.py needs a GPU (the HIP extension has no CPU fallback)'
     if args.gpus > 1 and int(os.environ.get('WORLD_SIZE', '1') or 1) <= 1 and 'LOCAL_RANK' not in os.environ:
-        self_launch(args)   # no launcher around this process: it becomes the launcher of N ranks (does not return)
+        self_launch(args)   # no launcher around this process: it starts the launcher of N ranks (does not return)
+    assert torch.cuda.is_available(), 'bench.py needs a GPU (the HIP extension has no CPU fallback)'
     # ONE JSON line on stdout, and nothing else: libraries write banners through C stdio (RCCL prints its version block to stdout when the
     # first communicator is created, and libc flushes it at EXIT -- i.e. after our line).  File descriptor 1 is pointed at stderr for the
     # whole run; the result line goes to a private duplicate of the real stdout (`emit`).
@@ -1017,6 +1073,8 @@ def main():
     res = run.timed(args.steps)
     elapsed, samples = res['elapsed'], res['samples']
     model, stepper = run.model, run.stepper
+    if args.dump_outputs:
+        dump_outputs(run, res, args.dump_outputs, rank)
 
     # roofline pass (untimed): HIP graphs cannot carry timing events, so the same iteration is run eagerly for a few steps
     # with HIP-event pairs around the named kernels, on the stream they are launched on, same batches, same state.
@@ -1296,7 +1354,7 @@ def main():
             'metric': 'training samples/s (rays x steps), lego-shaped synthetic, fp16 autocast, full step incl. Adam',
             'value': round(samples / elapsed, 1), 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
-            'dtype': 'f16', 'data': 'synthetic',
+            'dtype': 'f16', 'data': 'synthetic', 'full': bool(args.full),
             'rccl_ranks': comm['rccl_ranks'], 'comm': comm, 'sharded_update_fallback': fallback,
             'collectives_in_graph': {'used': bool(getattr(run.stepper, 'graph_collectives', False) and getattr(run.stepper, 'la', None) is not None
                                                   and getattr(run.stepper, 'la_apply', None) is None) if world > 1 or args.force_ddp else None,

@@ -23,7 +23,7 @@ def test_bench_pmc_measures_the_traffic_in_the_run():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     # (--no-fused-adam: the separate k_adam sweep IS the calibration point; the default mode carries the table's sweep in the grid backward)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--pmc', '--steps', '16', '--warmup', '2', '--no-cpu-baseline', '--no-dropin', '--no-extra',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--pmc', '--steps', '16', '--warmup', '2', '--no-cpu-baseline', '--no-dropin', '--no-extra',
            '--no-render', '--no-ddp-probe', '--watchdog', '500', '--no-fused-adam']
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=700)
     assert res.returncode == 0, res.stderr[-4000:]

@@ -18,8 +18,8 @@ def test_bench_two_ranks_share_one_gpu(extra):
     # GLOO_SOCKET_IFNAME=lo: the container's hostname may not resolve; gloo then needs no name lookup to pick its transport device
     env = dict(os.environ, NGP_BENCH_SHARE_GPU='1', NGP_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1', GLOO_SOCKET_IFNAME='lo')
     env.pop('WORLD_SIZE', None)
-    # plain `python bench.py --gpus 2`, NO launcher: bench.py re-executes itself under torch.distributed.run with one process per rank
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--no-cpu-baseline', '--no-dropin',
+    # `python bench.py --gpus 2`, NO launcher: bench.py starts torch.distributed.run as a child process, with one process per rank
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-dropin',
            '--strong-steps', '4', '--watchdog', '240'] + (['--no-render'] if extra else []) + extra
     # (--watchdog: a rank that hangs dumps every thread's stack and exits instead of sitting in a collective until the timeout below)
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=400)
@@ -51,17 +51,16 @@ def test_bench_two_ranks_share_one_gpu(extra):
     assert 4e5 < line['config']['samples_per_step_per_gpu'] * 2 < 7e5
 
 
-def test_bench_eight_ranks_share_one_gpu_with_the_canary_hand_over():
+def test_bench_eight_ranks_share_one_gpu():
     """BASELINE config 3's size (8 ranks) executed end to end on the one GPU over gloo (the driver's `bench.py --gpus 8` is a one-shot
-    run): the weak line, the strong-scaling run at 512 rays per rank, the sharded 800 x 800 frame in eight blocks -- and the canary hand-over with
-    EIGHT children (each rank starts a child on a rendezvous port of the children's own; the verdicts meet in a MIN all-reduce).  gloo cannot
-    be captured into a HIP graph, so the children report failure and the run must continue in the eager-collective form."""
+    run): the weak line, the strong-scaling run at 512 rays per rank, the sharded 800 x 800 frame in eight blocks.  The canary hand-over is
+    the next test's: eight ranks with eight children and this process would be 17 processes on the one device."""
     env = dict(os.environ, NGP_BENCH_SHARE_GPU='1', NGP_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1', GLOO_SOCKET_IFNAME='lo',
-               NGP_BENCH_CANARY_ANY_BACKEND='1', NGP_BENCH_CANARY_STEPS='2', OMP_NUM_THREADS='2')
-    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'NGP_GRAPH_COLLECTIVES'):
+               OMP_NUM_THREADS='2')
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'NGP_GRAPH_COLLECTIVES', 'NGP_BENCH_CANARY_ANY_BACKEND', 'NGP_BENCH_FORCE_CANARY'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '0', '--no-cpu-baseline', '--no-dropin', '--no-extra',
-           '--strong-steps', '2', '--watchdog', '800']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '0', '--full', '--no-cpu-baseline', '--no-dropin',
+           '--no-extra', '--strong-steps', '2', '--watchdog', '800']
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
     if res.returncode != 0 and 'Timeout (' in res.stderr:
         dump = os.path.join(ROOT, 'gpurun_out', 'ddp8_watchdog_dump.txt')
@@ -73,12 +72,9 @@ def test_bench_eight_ranks_share_one_gpu_with_the_canary_hand_over():
     assert line['comm']['ranks'] == 8 and line['comm']['self_launched'] and line['comm']['devices'] == [0] * 8
     assert line['scaling'] == 'weak' and line['config']['global_rays_per_step'] == 8 * 4096
     assert 'sharded' in line['config']['parallelism'] and line['sharded_update_fallback'] is None
-    # the hand-over ran on every rank and came back with a verdict (not a hang, not a port collision): eager collectives here
+    # gloo without the hand-over hook: no canary, eager collectives
     can = line['collectives_in_graph']
-    assert can['used'] is False and can['canary'] is not None and can['canary']['all_ranks_ok'] is False
-    assert 'did not finish' not in can['canary']['detail'], can['canary']
-    # (the children ended by themselves with a non-zero exit code -- a refused capture, here even a HIP error out of it -- and were not killed)
-    assert can['canary']['detail'].startswith('rc '), can['canary']
+    assert can['used'] is False and can['canary'] is None
     coll = line['collectives']
     for name in ('reduce_scatter_fp16_gradients', 'all_gather_fp16_shadows'):
         assert coll[name]['ms'] > 0 and coll[name]['calls'] >= 2
@@ -90,6 +86,33 @@ def test_bench_eight_ranks_share_one_gpu_with_the_canary_hand_over():
     assert line['config']['autograd_free_iteration'] and 'hip-graph replay' in line['config']['execution']
     assert line['value'] > 1e4 and line['config']['final_loss'] == line['config']['final_loss']
     assert 16e5 < line['config']['samples_per_step_per_gpu'] * 8 < 28e5      # 8 ranks x ~262 k samples per step
+
+
+def test_bench_seven_ranks_canary_hand_over():
+    """the canary hand-over with SEVEN children (each rank starts a child on a rendezvous port of the children's own; the verdicts meet in a
+    MIN all-reduce).  Seven ranks, their seven children and this process are 15 processes on the one device; the suite keeps that at 16 or
+    fewer.  gloo cannot be captured into a HIP graph, so the children report failure and the run must continue in the eager-collective form.
+    A plain run (no --full): the canary decides the form of the headline step itself."""
+    env = dict(os.environ, NGP_BENCH_SHARE_GPU='1', NGP_BENCH_BACKEND='gloo', MASTER_ADDR='127.0.0.1', GLOO_SOCKET_IFNAME='lo',
+               NGP_BENCH_CANARY_ANY_BACKEND='1', NGP_BENCH_CANARY_STEPS='2', OMP_NUM_THREADS='2')
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'NGP_GRAPH_COLLECTIVES'):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '7', '--steps', '2', '--warmup', '0', '--watchdog', '800']
+    res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1200)
+    assert res.returncode == 0, res.stderr[-6000:]
+    line = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['n_gpus'] == 7 and line['config']['captures_in_timed_region'] == 0
+    assert line['comm']['ranks'] == 7 and line['comm']['self_launched'] and line['comm']['devices'] == [0] * 7
+    assert 'sharded' in line['config']['parallelism'] and line['sharded_update_fallback'] is None
+    # the hand-over ran on every rank and came back with a verdict (not a hang, not a port collision): eager collectives here
+    can = line['collectives_in_graph']
+    assert can['used'] is False and can['canary'] is not None and can['canary']['all_ranks_ok'] is False
+    assert 'did not finish' not in can['canary']['detail'], can['canary']
+    # (the children ended by themselves with a non-zero exit code -- a refused capture, here even a HIP error out of it -- and were not killed)
+    assert can['canary']['detail'].startswith('rc '), can['canary']
+    assert line['config']['autograd_free_iteration'] and 'hip-graph replay' in line['config']['execution']
+    assert line['value'] > 1e4 and line['config']['final_loss'] == line['config']['final_loss']
+    assert 14e5 < line['config']['samples_per_step_per_gpu'] * 7 < 24.5e5      # 7 ranks x ~262 k samples per step
 
 
 def test_bench_refuses_more_ranks_than_gpus():

@@ -137,11 +137,11 @@ def test_one_rank_rccl_sharded_step_is_the_single_gpu_training():
 
 
 def test_bench_line_carries_the_one_rank_ddp_overhead():
-    """`python bench.py` at N = 1 runs the sharded step over a 1-rank RCCL group after the headline and reports it as `ddp_overhead_1rank`"""
+    """`python bench.py --full` at N = 1 runs the sharded step over a 1-rank RCCL group after the headline and reports it as `ddp_overhead_1rank`"""
     env = dict(os.environ)
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '16', '--warmup', '2', '--no-cpu-baseline', '--no-dropin', '--no-extra', '--no-render',
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '16', '--warmup', '2', '--no-cpu-baseline', '--no-dropin', '--no-extra', '--no-render',
            '--ddp-steps', '32', '--watchdog', '300']
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=500)
     assert res.returncode == 0, res.stderr[-4000:]

@@ -5,7 +5,7 @@ mkdir -p $out
 for rep in 1 2; do
 for v in "$@"; do
   if [ $v = base ]; then lib=""; else lib=$(pwd)/torch-ngp_amd/variants/$v/libngp_hip.so; fi
-  NGP_HIP_LIBRARY=$lib timeout 600 python bench.py $args --no-render --no-dropin --no-cpu-baseline > $out/${v}_$rep.json 2> $out/${v}_$rep.err || echo "$v failed"
+  NGP_HIP_LIBRARY=$lib timeout 600 python bench.py --full $args --no-render --no-dropin --no-cpu-baseline > $out/${v}_$rep.json 2> $out/${v}_$rep.err || echo "$v failed"
   python - <<PY
 import json
 try:

@@ -8,8 +8,8 @@ export TMPDIR=/tmp
 rocm-smi --showclocks --showpower --showuse > $out/box_state_before.txt 2>&1
 timeout 1500 python -m pytest tests -m gpu -q > $out/pytest_gpu.txt 2>&1; echo "pytest rc $?" >> $out/pytest_gpu.txt; tail -3 $out/pytest_gpu.txt
 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_n1_driver_args.json 2> $out/bench_n1_driver_args.err; echo "driver-args bench rc $?"
-timeout 900 python bench.py --pmc --no-cpu-baseline --no-extra --no-dropin > $out/bench_n1_default.json 2> $out/bench_n1_default.err; echo "default bench rc $?"
-timeout 600 python bench.py --steps 256 --warmup 16 --no-lookahead --no-cpu-baseline --no-extra --no-dropin --no-render > $out/bench_n1_no_lookahead.json 2> $out/bench_n1_no_lookahead.err; echo "no-lookahead bench rc $?"
+timeout 900 python bench.py --full --pmc --no-cpu-baseline --no-extra --no-dropin > $out/bench_n1_default.json 2> $out/bench_n1_default.err; echo "default bench rc $?"
+timeout 600 python bench.py --full --steps 256 --warmup 16 --no-lookahead --no-cpu-baseline --no-extra --no-dropin --no-render > $out/bench_n1_no_lookahead.json 2> $out/bench_n1_no_lookahead.err; echo "no-lookahead bench rc $?"
 bash tools/gpu_profile.sh $tag/prof_la --steps 64 --warmup 16 --no-render --no-dropin --no-cpu-baseline --no-extra --no-ddp-probe > /dev/null 2>&1
 bash tools/gpu_profile.sh $tag/prof_nola --steps 64 --warmup 16 --no-render --no-dropin --no-cpu-baseline --no-extra --no-lookahead --no-ddp-probe > /dev/null 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -36,7 +36,7 @@ import json
 for f in ('bench_n1_driver_args','bench_n1_default','bench_n1_no_lookahead'):
     try:
         l=json.loads(open('$out/'+f+'.json').read().strip().splitlines()[-1])
-        print(f, l['value'], l['ms_per_step'], l.get('render_800x800_ms'), [(r['kernel'][:24], r['avg_kernel_ms'], r['frac']) for r in l['rooflines']][:4])
+        print(f, l['value'], l['ms_per_step'], l.get('render_800x800_ms'), [(r['kernel'][:24], r['avg_kernel_ms'], r['frac']) for r in (l.get('rooflines') or [])][:4])
     except Exception as e: print(f, 'failed', e)
 PY
 head -20 $out/prof_nola/summary.md; cat $out/pmc_traffic.json | head -12; tail -4 $out/render_800x800.txt
