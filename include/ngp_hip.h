@@ -9,7 +9,10 @@
  *     the reference where the Python wrapper allocates all outputs and workspaces);
  *   - at::optional<at::Tensor> becomes a pointer that may be NULL;
  *   - the element type that the reference dispatches on (AT_DISPATCH_FLOATING_TYPES_AND_HALF) is an
- *     explicit `dtype` code; fp64 is not provided;
+ *     explicit `dtype` code.  NGP_F64 is accepted by the grid encoder (forward, backward -- with a workspace --,
+ *     total variation) and the SH encoder; the raymarching entries take float* and have *_f64 twins for the
+ *     compositors, near_far_from_aabb, sph_from_ray and packbits.  Every other entry refuses fp64 with
+ *     NGP_ERR_INVALID (the marchers, ffmlp, freq encoder, fused / graph / optimizer entries);
  *   - a trailing `stream` (a hipStream_t passed as void*; NULL = the legacy default stream the
  *     reference launches on);
  *   - every function returns 0 on success and a non-zero NGP_ERR_* code on failure, with a
@@ -41,7 +44,7 @@ enum {
     NGP_ERR_DEVICE = 3   /* no usable gfx950 device / runtime error */
 };
 
-enum { NGP_F32 = 0, NGP_F16 = 1 };
+enum { NGP_F32 = 0, NGP_F16 = 1, NGP_F64 = 2 };
 
 #define NGP_MAX_LEVELS 32 /* grid encoder: L <= 32 */
 
@@ -59,7 +62,9 @@ const char* ngp_target_arch(void);
 /* replaces grid_encode_forward (gridencoder.cu:448-471).
  * inputs [B,D] fp32 in [0,1]; embeddings [sO,C] dtype; offsets [L+1] int32 (device);
  * outputs [L,B,C] dtype; dy_dx [B,L*D*C] dtype or NULL.  D in {2,3,4,5}, C in {1,2,4,8}, L <= 32.
- * gridtype 0 = hash, 1 = tiled; interp 0 = linear, 1 = smoothstep. */
+ * gridtype 0 = hash, 1 = tiled; interp 0 = linear, 1 = smoothstep.
+ * NGP_F64: positions and interpolation weights as in the fp32 path (from the fp32 inputs), products with table
+ * entries and their sums in fp64 (DESIGN.md "The fp64 path"). */
 int ngp_grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs,
                             uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void* dy_dx,
                             uint32_t gridtype, int align_corners, uint32_t interp, int dtype, ngp_stream_t stream);
@@ -67,13 +72,15 @@ int ngp_grid_encode_forward(const float* inputs, const void* embeddings, const i
 /* replaces grid_encode_backward (gridencoder.cu:473-503).
  * grad [L,B,C] dtype; grad_embeddings [sO,C] dtype, pre-zeroed, accumulated with hardware atomics
  * (packed fp16 when dtype is F16 and C is even, as the reference); dy_dx / grad_inputs [B,D] dtype
- * both NULL or both non-NULL. */
+ * both NULL or both non-NULL.  NGP_F64 needs scratch memory: use ngp_grid_encode_backward_ws (this
+ * entry returns NGP_ERR_INVALID for it). */
 int ngp_grid_encode_backward(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
                              void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                              uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
                              uint32_t interp, int dtype, ngp_stream_t stream);
 
-/* replaces grad_total_variation (gridencoder.cu:639-645): inputs [B,D] dtype in [0,1]; adds into grad [sO,C]. */
+/* replaces grad_total_variation (gridencoder.cu:639-645): inputs [B,D] dtype in [0,1]; adds into grad [sO,C].
+ * NGP_F64: fp64 throughout, fp64 atomics. */
 int ngp_grad_total_variation(const void* inputs, const void* embeddings, void* grad, const int32_t* offsets,
                              float weight, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                              uint32_t gridtype, int align_corners, int dtype, ngp_stream_t stream);
@@ -95,7 +102,7 @@ int ngp_grid_level_table(uint32_t L, float S, uint32_t H, float* scale_out, uint
  * --------------------------------------------------------------------------------------------- */
 
 /* replaces sh_encode_forward (shencoder.cu:400-417): inputs [B,3]; outputs [B,C*C]; dy_dx [B,3*C*C] or NULL;
- * D must be 3, C (number of bands) in 1..8. */
+ * D must be 3, C (number of bands) in 1..8.  dtype F32, F16 or F64 (fp64 arithmetic and constants). */
 int ngp_sh_encode_forward(const void* inputs, void* outputs, uint32_t B, uint32_t D, uint32_t C, void* dy_dx,
                           int dtype, ngp_stream_t stream);
 /* replaces sh_encode_backward (shencoder.cu:419-439): grad_inputs[b,d] += sum_ch grad[b,ch]*dy_dx[b,d,ch] */
@@ -151,6 +158,25 @@ int ngp_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive,
 int ngp_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* rays_alive, float* rays_t,
                        const float* sigmas, const float* rgbs, const float* deltas, float* weights_sum,
                        float* depth, float* image, ngp_stream_t stream);
+
+/* fp64 twins of near_far_from_aabb, sph_from_ray, packbits, composite_rays_train_forward / _backward and composite_rays: the same
+ * arguments with every floating tensor double (the reference dispatches these on the tensor dtype); the scalars stay float and are
+ * widened exactly.  The reference's per-ray loops in fp64 (exp in double, T < T_thresh compared in double); a near/far miss gives
+ * DBL_MAX.  (No fp64 marchers.) */
+int ngp_near_far_from_aabb_f64(const double* rays_o, const double* rays_d, const double* aabb, uint32_t N, float min_near,
+                               double* nears, double* fars, ngp_stream_t stream);
+int ngp_sph_from_ray_f64(const double* rays_o, const double* rays_d, float radius, uint32_t N, double* coords, ngp_stream_t stream);
+int ngp_packbits_f64(const double* grid, uint32_t N, float density_thresh, uint8_t* bitfield, ngp_stream_t stream);
+int ngp_composite_rays_train_forward_f64(const double* sigmas, const double* rgbs, const double* deltas, const int32_t* rays,
+                                         uint32_t M, uint32_t N, float T_thresh, double* weights_sum, double* depth, double* image,
+                                         ngp_stream_t stream);
+int ngp_composite_rays_train_backward_f64(const double* grad_weights_sum, const double* grad_image, const double* sigmas,
+                                          const double* rgbs, const double* deltas, const int32_t* rays, const double* weights_sum,
+                                          const double* image, uint32_t M, uint32_t N, float T_thresh, double* grad_sigmas,
+                                          double* grad_rgbs, ngp_stream_t stream);
+int ngp_composite_rays_f64(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* rays_alive, double* rays_t,
+                           const double* sigmas, const double* rgbs, const double* deltas, double* weights_sum, double* depth,
+                           double* image, ngp_stream_t stream);
 
 /* Extension (no reference counterpart): stream compaction of the alive list on the
  * device, replacing `rays_alive[rays_alive >= 0]` + its host sync in the caller's render loop.
@@ -243,7 +269,11 @@ uint32_t ngp_grid_forward_work_lists(uint32_t L, uint32_t tiles, const float* le
  * add, in an undefined order) and is bit-reproducible; entries that receive a non-finite contribution become NaN.
  * offsets_host: a HOST copy of `offsets` (L + 1 values; the level sizes steer the plan).  workspace: device memory of at least
  * ngp_grid_backward_workspace_bytes(...) bytes, contents irrelevant.  offsets_host == NULL or workspace == NULL -> the atomic path
- * (= ngp_grid_encode_backward_ex).  Small batches and other dtypes/shapes use the atomic path as well (workspace_bytes() == 0). */
+ * (= ngp_grid_encode_backward_ex).  Small batches and other dtypes/shapes use the atomic path as well (workspace_bytes() == 0).
+ * NGP_F64 (this entry and _ws only; the _checked entries refuse it): the backward is bit-reproducible -- per level, one record per
+ * (point, corner) contribution, a stable radix sort on the table entry, each entry's contributions summed in fp64 in point order and
+ * added once (no float atomics).  Its workspace is a function of B and D alone (offsets_host may be NULL, e.g. during stream capture):
+ * ngp_grid_backward_workspace_bytes(NULL, B, D, ..., NGP_F64) bytes, 256-byte aligned, required; B * 2^D <= 2^31. */
 size_t ngp_grid_backward_workspace_bytes(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                                          uint32_t gridtype, int align_corners, int dtype);
 /* ngp_grid_encode_backward_ws that also does the optimizer's non-finite sweep over the gradient table where the values are produced:

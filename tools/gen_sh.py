@@ -2,6 +2,7 @@
 """Generate the real-spherical-harmonics polynomial tables used by
  (a) oracle/sh_table.inc          -- double precision, un-optimised, one expression per line
  (b) torch-ngp_amd/csrc/sh_poly.inc -- fp32 device code, common sub-expressions shared
+ (c) torch-ngp_amd/csrc/sh_poly64.inc -- the same device tables in double precision (fp64.hip)
 
 The 64 basis polynomials (bands 0..7) are the Cartesian forms the reference evaluates
 (reference: shencoder/src/shencoder.cu:50-120, closed forms given in its trailing comments);
@@ -14,7 +15,7 @@ The value polynomials are pinned independently in tests/test_oracle_sh.py agains
 scipy.special.sph_harm (all 64, unit vectors) and against golden vectors produced by the
 reference's own pure-torch SHEncoder_torch (testing/test_shencoder.py:8-89, bands 0..4).
 
-Run:  python tools/gen_sh.py       (rewrites both .inc files in place; needs sympy)
+Run:  python tools/gen_sh.py       (rewrites the three .inc files in place; needs sympy)
 """
 import os
 import sympy as sp
@@ -176,7 +177,26 @@ def main():
         dl.append('    ((void)0)')
     with open(os.path.join(root, 'torch-ngp_amd', 'csrc', 'sh_poly.inc'), 'w') as f:
         f.write('\n'.join(dl) + '\n')
-    print('wrote oracle/sh_table.inc and torch-ngp_amd/csrc/sh_poly.inc')
+
+    # ---------------- device (double): the same band macros with double literals, SH64_ prefix ----------------
+    dl = ['// GENERATED by tools/gen_sh.py -- do not edit.  fp64 device evaluation of the real SH',
+          '// basis, band by band (band b contributes components b*b .. (b+1)*(b+1)-1).',
+          '// SH_OUT(i, v) / SH_DX(i, v) / SH_DY(i, v) / SH_DZ(i, v) are supplied by the includer; x, y, z are double.']
+    for band in range(8):
+        lo, hi = band * band, (band + 1) * (band + 1)
+        dl.append('#define SH64_BAND_%d_VALUES \\' % band)
+        for i in range(lo, hi):
+            dl.append('    SH_OUT(%d, %s); \\' % (i, expand_pows(c_expr(Y[i], False))))
+        dl.append('    ((void)0)')
+        dl.append('#define SH64_BAND_%d_GRADS \\' % band)
+        for i in range(lo, hi):
+            dl.append('    SH_DX(%d, %s); \\' % (i, expand_pows(c_expr(dY[0][i], False))))
+            dl.append('    SH_DY(%d, %s); \\' % (i, expand_pows(c_expr(dY[1][i], False))))
+            dl.append('    SH_DZ(%d, %s); \\' % (i, expand_pows(c_expr(dY[2][i], False))))
+        dl.append('    ((void)0)')
+    with open(os.path.join(root, 'torch-ngp_amd', 'csrc', 'sh_poly64.inc'), 'w') as f:
+        f.write('\n'.join(dl) + '\n')
+    print('wrote oracle/sh_table.inc, torch-ngp_amd/csrc/sh_poly.inc and torch-ngp_amd/csrc/sh_poly64.inc')
 
 
 if __name__ == '__main__':

@@ -19,11 +19,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NGP_HIP_LIBRARY: developer override for A/B runs of compile-time variants (tools/build_variant.sh); default = the in-tree build
 LIB_PATH = os.environ.get('NGP_HIP_LIBRARY') or os.path.join(_HERE, 'libngp_hip.so')
 
-NGP_F32, NGP_F16 = 0, 1
+NGP_F32, NGP_F16, NGP_F64 = 0, 1, 2
 NGP_FF_INPUT_PLANAR, NGP_FF_DX_PLANAR, NGP_FF_LAYERED, NGP_FF_SINGLE_WAVE, NGP_FF_DEFER_REDUCE, NGP_FF_RECOMPUTE = 1, 2, 4, 8, 16, 32
 NGP_MARCH_RESET_COUNTER, NGP_MARCH_ZERO_TAIL, NGP_MARCH_NOISE_FROM_SEED, NGP_MARCH_SCAN_LAUNCH = 1, 2, 4, 8
 NGP_OPT_PHASE_CHECK, NGP_OPT_PHASE_UPDATE, NGP_OPT_PHASE_COMMIT, NGP_OPT_PHASE_FLIP = 1, 2, 4, 8
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -56,6 +56,12 @@ _SIGNATURES = {
     'ngp_march_rays': [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'ngp_march_rays_ex': [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     'ngp_composite_rays': [_u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'ngp_near_far_from_aabb_f64': [_vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp],
+    'ngp_sph_from_ray_f64': [_vp, _vp, _f32, _u32, _vp, _vp],
+    'ngp_packbits_f64': [_vp, _u32, _f32, _vp, _vp],
+    'ngp_composite_rays_train_forward_f64': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp, _vp],
+    'ngp_composite_rays_train_backward_f64': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp],
+    'ngp_composite_rays_f64': [_u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'ngp_compact_rays': [_vp, _u32, _vp, _vp, _vp, _vp],
     'ngp_coarse_occupancy': [_vp, _u32, _u32, _vp, _vp],
     'ngp_cull_rays': [_vp, _vp, _vp, _vp, _u32, _f32, _u32, _u32, _vp, _vp, _vp],
@@ -207,14 +213,26 @@ def require_int32(t, name):
 
 
 def float_code(t, name):
-    """dtype code of a floating tensor (fp64 is not provided by this library)."""
+    """dtype code of a floating tensor (the grid and SH encoders' entry points take all three)."""
     if t.dtype == torch.float16:
         return NGP_F16
     if t.dtype == torch.float32:
         return NGP_F32
     if t.dtype == torch.float64:
-        raise RuntimeError(f"{name}: float64 is not supported by the MI355X kernels (use float32 or float16)")
+        return NGP_F64
     raise RuntimeError(f"{name} must be a floating tensor")
+
+
+def float64_call(*named):
+    """(tensor or None, name) pairs of one call's floating tensors: True when the call is a float64 one -- then every tensor must be float64
+    and the error names the first that is not.  Calls without float64 tensors keep their fp32 / fp16 rules (False)."""
+    named = [(t, n) for t, n in named if t is not None]
+    if not any(t.dtype == torch.float64 for t, _ in named):
+        return False
+    for t, n in named:
+        if t.dtype != torch.float64:
+            raise RuntimeError(f"{n} must be a float64 tensor like the other floating tensors of this call (got {t.dtype})")
+    return True
 
 
 def dense(t, name):
@@ -239,6 +257,9 @@ def host_offsets(offsets):
 
 def grid_backward_workspace(offsets, B, D, C, L, S, H, gridtype, align_corners, code):
     """(offsets_host, workspace tensor or None, bytes) for ngp_grid_encode_backward_ws"""
+    if code == NGP_F64:   # the deterministic fp64 backward: scratch sized from B and D alone, no host offsets (also under stream capture)
+        n = int(lib.ngp_grid_backward_workspace_bytes(None, B, D, C, L, float(S), H, gridtype, int(bool(align_corners)), code))
+        return None, (torch.empty(n, dtype=torch.uint8, device=offsets.device) if n else None), n
     arr = host_offsets(offsets)
     if arr is None:
         return None, None, 0

@@ -51,9 +51,30 @@ inline void check(int rc) {
 inline int float_code(const Tensor& t, const char* name) {
     if (t.scalar_type() == at::ScalarType::Half) return NGP_F16;
     if (t.scalar_type() == at::ScalarType::Float) return NGP_F32;
-    TORCH_CHECK(t.scalar_type() != at::ScalarType::Double, name, ": float64 is not supported by the MI355X kernels (use float32 or float16)");
+    if (t.scalar_type() == at::ScalarType::Double) return NGP_F64;
     TORCH_CHECK(false, name, " must be a floating tensor");
     return -1;
+}
+// fp64 calls: when one floating tensor of a call is float64, every one must be (and dense) -- the error names the first that is not.  Returns
+// whether the call is a float64 one.  (Calls without float64 tensors keep their fp32 / fp16 rules.)
+struct Named {
+    const Tensor* t;
+    const char* name;
+};
+inline const Tensor* opt(const OptTensor& t) { return t.has_value() && t->defined() ? &*t : nullptr; }
+inline bool float64_call(std::initializer_list<Named> ts) {
+    bool any = false;
+    for (const Named& n : ts) any = any || (n.t && n.t->scalar_type() == at::ScalarType::Double);
+    if (!any) return false;
+    for (const Named& n : ts)
+        TORCH_CHECK(!n.t || n.t->scalar_type() == at::ScalarType::Double, n.name, " must be a float64 tensor like the other floating tensors of this call (got ",
+                    n.t->scalar_type(), ")");
+    for (const Named& n : ts) {
+        if (!n.t) continue;
+        TORCH_CHECK(n.t->device().is_cuda(), n.name, " must be a CUDA tensor");
+        TORCH_CHECK(n.t->is_contiguous(), n.name, " must be a contiguous tensor");
+    }
+    return true;
 }
 inline Tensor scratch(size_t bytes, const Tensor& like) {
     return at::empty({(int64_t)bytes}, like.options().dtype(at::kByte));
@@ -105,6 +126,7 @@ void grid_encode_forward(const Tensor inputs, const Tensor embeddings, const Ten
                          const bool align_corners, const uint32_t interp) {
     grid_common(inputs, embeddings, offsets);
     CHECK_DENSE(outputs);
+    float64_call({{&embeddings, "embeddings"}, {&outputs, "outputs"}, {opt(dy_dx), "dy_dx"}});
     check(ngp_grid_encode_forward((const float*)ptr(inputs), ptr(embeddings), (const int32_t*)ptr(offsets), ptr(outputs), B, D, C, L, S, H, ptr(dy_dx),
                                   gridtype, align_corners ? 1 : 0, interp, float_code(embeddings, "embeddings"), stream()));
 }
@@ -115,6 +137,17 @@ void grid_encode_backward(const Tensor grad, const Tensor inputs, const Tensor e
     grid_common(inputs, embeddings, offsets);
     CHECK_DENSE(grad);
     CHECK_DENSE(grad_embeddings);
+    if (float64_call({{&grad, "grad"}, {&embeddings, "embeddings"}, {&grad_embeddings, "grad_embeddings"}, {opt(dy_dx), "dy_dx"},
+                      {opt(grad_inputs), "grad_inputs"}})) {
+        // the deterministic fp64 backward: scratch sized from B and D alone (no host offsets, so also under stream capture)
+        const size_t bytes = ngp_grid_backward_workspace_bytes(nullptr, B, D, C, L, S, H, gridtype, align_corners ? 1 : 0, NGP_F64);
+        Tensor ws;
+        if (bytes) ws = scratch(bytes, grad);
+        check(ngp_grid_encode_backward_ws(ptr(grad), (const float*)ptr(inputs), ptr(embeddings), (const int32_t*)ptr(offsets), ptr(grad_embeddings), B, D,
+                                          C, L, S, H, ptr(dy_dx), ptr(grad_inputs), gridtype, align_corners ? 1 : 0, interp, NGP_F64, 0.0f, nullptr,
+                                          bytes ? ws.data_ptr() : nullptr, bytes, stream()));
+        return;
+    }
     const int code = float_code(grad, "grad");
     // large fp16 batches: the atomic-free record sort needs scratch memory the reference signature has no argument for
     const int32_t* host = host_offsets(offsets);
@@ -133,6 +166,7 @@ void grad_total_variation(const Tensor inputs, const Tensor embeddings, Tensor g
     CHECK_DENSE(embeddings);
     CHECK_DENSE(grad);
     CHECK_DENSE(offsets);
+    float64_call({{&inputs, "inputs"}, {&embeddings, "embeddings"}, {&grad, "grad"}});
     TORCH_CHECK(inputs.scalar_type() == embeddings.scalar_type() && grad.scalar_type() == embeddings.scalar_type(),
                 "grad_total_variation: inputs, embeddings and grad must share one dtype");
     check(ngp_grad_total_variation(ptr(inputs), ptr(embeddings), ptr(grad), (const int32_t*)ptr(offsets), weight, B, D, C, L, S, H, gridtype,
@@ -150,6 +184,7 @@ void sh_encode_forward(Tensor inputs, Tensor outputs, const uint32_t B, const ui
     CHECK_DENSE(inputs);
     CHECK_DENSE(outputs);
     CHECK_IS_FLOATING(inputs);
+    float64_call({{&inputs, "inputs"}, {&outputs, "outputs"}, {opt(dy_dx), "dy_dx"}});
     check(ngp_sh_encode_forward(ptr(inputs), ptr(outputs), B, D, C, ptr(dy_dx), float_code(inputs, "inputs"), stream()));
 }
 
@@ -159,6 +194,7 @@ void sh_encode_backward(Tensor grad, Tensor inputs, const uint32_t B, const uint
     CHECK_DENSE(dy_dx);
     CHECK_DENSE(grad_inputs);
     CHECK_IS_FLOATING(grad);
+    float64_call({{&grad, "grad"}, {&inputs, "inputs"}, {&dy_dx, "dy_dx"}, {&grad_inputs, "grad_inputs"}});
     check(ngp_sh_encode_backward(ptr(grad), ptr(inputs), B, D, C, ptr(dy_dx), ptr(grad_inputs), float_code(grad, "grad"), stream()));
 }
 
@@ -204,16 +240,26 @@ struct F32View {
     F32View x##_v(x, OUT); \
     TORCH_CHECK(x##_v.f32.scalar_type() == at::ScalarType::Float, #x " must be a float32 tensor (the reference wrappers cast with custom_fwd(cast_inputs=float32))")
 #define F32ARG(x) F32ANY(x, false)   // input
+// the entries with an fp64 twin (include/ngp_hip.h, *_f64)
+#define F64PTR(x) ((double*)x.data_ptr())   // (after float64_call(): float64, dense)
 #define F32OUT(x) F32ANY(x, true)    // output or in/out: finished with F32DONE after the call
 #define F32DONE(x) x##_v.finish()
 
 void near_far_from_aabb(const Tensor rays_o, const Tensor rays_d, const Tensor aabb, const uint32_t N, const float min_near, Tensor nears, Tensor fars) {
+    if (float64_call({{&rays_o, "rays_o"}, {&rays_d, "rays_d"}, {&aabb, "aabb"}, {&nears, "nears"}, {&fars, "fars"}})) {
+        check(ngp_near_far_from_aabb_f64(F64PTR(rays_o), F64PTR(rays_d), F64PTR(aabb), N, min_near, F64PTR(nears), F64PTR(fars), stream()));
+        return;
+    }
     F32ARG(rays_o); F32ARG(rays_d); F32ARG(aabb); F32OUT(nears); F32OUT(fars);
     check(ngp_near_far_from_aabb(rays_o_v.p(), rays_d_v.p(), aabb_v.p(), N, min_near, nears_v.p(), fars_v.p(), stream()));
     F32DONE(nears); F32DONE(fars);
 }
 
 void sph_from_ray(const Tensor rays_o, const Tensor rays_d, const float radius, const uint32_t N, Tensor coords) {
+    if (float64_call({{&rays_o, "rays_o"}, {&rays_d, "rays_d"}, {&coords, "coords"}})) {
+        check(ngp_sph_from_ray_f64(F64PTR(rays_o), F64PTR(rays_d), radius, N, F64PTR(coords), stream()));
+        return;
+    }
     F32ARG(rays_o); F32ARG(rays_d); F32OUT(coords);
     check(ngp_sph_from_ray(rays_o_v.p(), rays_d_v.p(), radius, N, coords_v.p(), stream()));
     F32DONE(coords);
@@ -230,9 +276,13 @@ void morton3D_invert(const Tensor indices, const uint32_t N, Tensor coords) {
 }
 
 void packbits(const Tensor grid, const uint32_t N, const float density_thresh, Tensor bitfield) {
-    F32ARG(grid);
     CHECK_DENSE(bitfield);
     TORCH_CHECK(bitfield.scalar_type() == at::ScalarType::Byte, "bitfield must be a uint8 tensor");
+    if (float64_call({{&grid, "grid"}})) {
+        check(ngp_packbits_f64(F64PTR(grid), N, density_thresh, (uint8_t*)ptr(bitfield), stream()));
+        return;
+    }
+    F32ARG(grid);
     check(ngp_packbits(grid_v.p(), N, density_thresh, (uint8_t*)ptr(bitfield), stream()));
 }
 
@@ -265,6 +315,12 @@ void march_rays_train(const Tensor rays_o, const Tensor rays_d, const Tensor gri
 
 void composite_rays_train_forward(const Tensor sigmas, const Tensor rgbs, const Tensor deltas, const Tensor rays, const uint32_t M, const uint32_t N,
                                   const float T_thresh, Tensor weights_sum, Tensor depth, Tensor image) {
+    if (float64_call({{&sigmas, "sigmas"}, {&rgbs, "rgbs"}, {&deltas, "deltas"}, {&weights_sum, "weights_sum"}, {&depth, "depth"}, {&image, "image"}})) {
+        CHECK_I32(rays);
+        check(ngp_composite_rays_train_forward_f64(F64PTR(sigmas), F64PTR(rgbs), F64PTR(deltas), (const int32_t*)ptr(rays), M, N, T_thresh,
+                                                   F64PTR(weights_sum), F64PTR(depth), F64PTR(image), stream()));
+        return;
+    }
     F32ARG(sigmas); F32ARG(rgbs); F32ARG(deltas); F32OUT(weights_sum); F32OUT(depth); F32OUT(image);
     CHECK_I32(rays);
     check(ngp_composite_rays_train_forward(sigmas_v.p(), rgbs_v.p(), deltas_v.p(), (const int32_t*)ptr(rays), M, N, T_thresh, weights_sum_v.p(),
@@ -275,6 +331,14 @@ void composite_rays_train_forward(const Tensor sigmas, const Tensor rgbs, const 
 void composite_rays_train_backward(const Tensor grad_weights_sum, const Tensor grad_image, const Tensor sigmas, const Tensor rgbs, const Tensor deltas,
                                    const Tensor rays, const Tensor weights_sum, const Tensor image, const uint32_t M, const uint32_t N,
                                    const float T_thresh, Tensor grad_sigmas, Tensor grad_rgbs) {
+    if (float64_call({{&grad_weights_sum, "grad_weights_sum"}, {&grad_image, "grad_image"}, {&sigmas, "sigmas"}, {&rgbs, "rgbs"}, {&deltas, "deltas"},
+                      {&weights_sum, "weights_sum"}, {&image, "image"}, {&grad_sigmas, "grad_sigmas"}, {&grad_rgbs, "grad_rgbs"}})) {
+        CHECK_I32(rays);
+        check(ngp_composite_rays_train_backward_f64(F64PTR(grad_weights_sum), F64PTR(grad_image), F64PTR(sigmas), F64PTR(rgbs), F64PTR(deltas),
+                                                    (const int32_t*)ptr(rays), F64PTR(weights_sum), F64PTR(image), M, N, T_thresh, F64PTR(grad_sigmas),
+                                                    F64PTR(grad_rgbs), stream()));
+        return;
+    }
     F32ARG(grad_weights_sum); F32ARG(grad_image); F32ARG(sigmas); F32ARG(rgbs); F32ARG(deltas); F32ARG(weights_sum); F32ARG(image);
     F32OUT(grad_sigmas); F32OUT(grad_rgbs);
     CHECK_I32(rays);
@@ -307,6 +371,13 @@ void march_rays_ex(const uint32_t n_alive, const uint32_t n_step, const Tensor r
 
 void composite_rays(const uint32_t n_alive, const uint32_t n_step, const float T_thresh, Tensor rays_alive, Tensor rays_t, Tensor sigmas, Tensor rgbs,
                     Tensor deltas, Tensor weights_sum, Tensor depth, Tensor image) {
+    if (float64_call({{&rays_t, "rays_t"}, {&sigmas, "sigmas"}, {&rgbs, "rgbs"}, {&deltas, "deltas"}, {&weights_sum, "weights_sum"}, {&depth, "depth"},
+                      {&image, "image"}})) {
+        CHECK_I32(rays_alive);
+        check(ngp_composite_rays_f64(n_alive, n_step, T_thresh, (int32_t*)ptr(rays_alive), F64PTR(rays_t), F64PTR(sigmas), F64PTR(rgbs), F64PTR(deltas),
+                                     F64PTR(weights_sum), F64PTR(depth), F64PTR(image), stream()));
+        return;
+    }
     F32OUT(rays_t); F32ARG(sigmas); F32ARG(rgbs); F32ARG(deltas); F32OUT(weights_sum); F32OUT(depth); F32OUT(image);
     CHECK_I32(rays_alive);
     check(ngp_composite_rays(n_alive, n_step, T_thresh, (int32_t*)ptr(rays_alive), rays_t_v.p(), sigmas_v.p(), rgbs_v.p(), deltas_v.p(), weights_sum_v.p(),

@@ -1,0 +1,805 @@
+// fp64 kernels for gfx950 (MI355X): the grid encoder, its total-variation gradient, the SH encoder, the training and inference
+// compositors and the ray utilities (near/far, sph, packbits) -- the ops the reference dispatches with AT_DISPATCH_FLOATING_TYPES_AND_HALF,
+// so that torch.autograd.gradcheck can run against this backend.  A correctness tool, not a hot path: straightforward one-lane-per-item
+// kernels, kept in a unit of their own so that no fp16/fp32 kernel is compiled differently.
+//
+// Numerics (DESIGN.md "The fp64 path"):
+//   * grid forward: positions, fractions and interpolation weights come from the fp32 inputs through the fp32 path's own code
+//     (grid_index.h: locate, the fp32 weight product); every product with a table entry and every sum is fp64, nothing is rounded
+//     through fp32 after the weights;
+//   * grid backward: bit-reproducible.  Per level, every (point, corner) contribution becomes a record (table entry, point << D | corner)
+//     written at a fixed slot, a stable LSD radix sort on the entry (four 8-bit passes) groups the records of an entry in slot order, and
+//     one lane per entry sums its run in that order in fp64 and adds the sum once.  No float atomics, so two calls give the same bits;
+//   * TV: fp64 throughout, fp64 atomics (not on an autograd path);
+//   * SH: fp64 arithmetic and constants (sh_poly64.inc, tools/gen_sh.py);
+//   * compositing / near-far / sph / packbits: the reference's per-ray loops in fp64 (exp in double, T < T_thresh compared in double).
+#include "common.h"
+#include "grid_index.h"
+#include "fp64.h"
+#include "sh_poly64.inc"
+#include <float.h>
+#include <math.h>
+
+namespace ngp {
+
+constexpr int F64_THREADS = 256;
+
+static uint32_t f64_blocks(uint64_t n) {
+    const uint64_t nb = cdiv64(n, F64_THREADS);
+    return nb < 1 ? 1u : (nb > 65535u ? 65535u : (uint32_t)nb);
+}
+
+// interpolation weight of corner k (bit d set: the upper vertex in dimension d) -- the fp32 product of k_grid_forward, same order
+template <int D>
+__device__ __forceinline__ float corner_weight(const float (&frac)[D], uint32_t k) {
+    float w = 1.0f;
+#pragma unroll
+    for (int d = 0; d < D; d++) w *= ((k >> d) & 1u) ? frac[d] : (1.0f - frac[d]);
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid encoder: forward (gridencoder.cu:87-245)
+// ------------------------------------------------------------------------------------------------
+template <int D, int C, bool WITH_DYDX>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_fwd(const float* __restrict__ inputs, const double* __restrict__ grid,
+                                                               const int32_t* __restrict__ offsets, double* __restrict__ outputs, uint32_t B,
+                                                               uint32_t L, GridLevels lv, double* __restrict__ dy_dx, uint32_t gridtype,
+                                                               bool align_corners, uint32_t interp) {
+    const uint32_t level = blockIdx.y;
+    const uint32_t off0 = (uint32_t)offsets[level];
+    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
+    const float scale = lv.scale[level];
+    LevelIndexer<D> indexer;
+    indexer.init(gridtype, align_corners, hashmap_size, lv.res[level]);
+    const double* __restrict__ table = grid + (size_t)off0 * C;
+
+    for (uint32_t b = blockIdx.x * F64_THREADS + threadIdx.x; b < B; b += gridDim.x * F64_THREADS) {
+        float frac[D], deriv[D];
+        uint32_t cell[D];
+        double* out = outputs + ((size_t)level * B + b) * C;
+        double* dyo = WITH_DYDX ? dy_dx + ((size_t)b * L + level) * D * C : nullptr;
+        if (!locate<D>(inputs + (size_t)b * D, scale, align_corners, interp, frac, deriv, cell)) {
+#pragma unroll
+            for (int c = 0; c < C; c++) out[c] = 0.0;
+            if (WITH_DYDX) {
+#pragma unroll
+                for (int i = 0; i < D * C; i++) dyo[i] = 0.0;
+            }
+            continue;
+        }
+        double acc[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) acc[c] = 0.0;
+        // corners one after the other (unrolled, the 2^D * C fp64 loads are hoisted and D = 5, C = 8 spills)
+#pragma unroll 1
+        for (int k = 0; k < (1 << D); k++) {
+            uint32_t pg[D];
+#pragma unroll
+            for (int d = 0; d < D; d++) pg[d] = cell[d] + ((k >> d) & 1);
+            const double* v = table + (size_t)indexer(pg) * C;
+            NGP_BOUNDS(indexer(pg) < hashmap_size);
+            const double w = (double)corner_weight<D>(frac, (uint32_t)k);
+#pragma unroll
+            for (int c = 0; c < C; c++) acc[c] = __builtin_fma(w, v[c], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < C; c++) out[c] = acc[c];
+
+        if (WITH_DYDX) {
+            // gridencoder.cu:201-244: d out / d x_g = scale * sum_{left corners} w_other * deriv_g * (v_right - v_left); the weight factor is
+            // the fp32 path's, the difference and the sum are fp64
+#pragma unroll
+            for (int g = 0; g < D; g++) {
+                double ga[C];
+#pragma unroll
+                for (int c = 0; c < C; c++) ga[c] = 0.0;
+#pragma unroll 1
+                for (int k = 0; k < (1 << D); k++) {
+                    if ((k >> g) & 1) continue;
+                    float w = scale;
+#pragma unroll
+                    for (int d = 0; d < D; d++)
+                        if (d != g) w *= ((k >> d) & 1) ? frac[d] : (1.0f - frac[d]);
+                    const double wd = (double)(w * deriv[g]);
+                    uint32_t pl[D], pr[D];
+#pragma unroll
+                    for (int d = 0; d < D; d++) {
+                        pl[d] = cell[d] + ((k >> d) & 1);
+                        pr[d] = pl[d] + (d == g ? 1u : 0u);
+                    }
+                    const double* vl = table + (size_t)indexer(pl) * C;
+                    const double* vr = table + (size_t)indexer(pr) * C;
+#pragma unroll
+                    for (int c = 0; c < C; c++) ga[c] = __builtin_fma(wd, vr[c] - vl[c], ga[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < C; c++) dyo[g * C + c] = ga[c];
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid encoder: deterministic backward, one level at a time
+//   records -> 4 x (histogram, scan, stable scatter) on the entry -> per-entry ordered sum
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t F64_NO_ENTRY = 0xffffffffu;  // record of a point outside [0,1]^D (sorts last, contributes nothing)
+constexpr uint32_t RADIX_TILE = 256;             // items per scatter step = threads of the histogram / scatter workgroups
+constexpr uint32_t RADIX_MAX_GROUPS = 1024;      // workgroups per pass (each owns a contiguous range of tiles)
+constexpr uint32_t RADIX_COUNT_WORDS = 256 * RADIX_MAX_GROUPS + 256;   // per-(digit, group) counts, then the 256 digit totals
+
+// slot (b << D | k) of every contribution of level `level`: key = the entry inside the level, value = the slot itself
+template <int D>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_records(const float* __restrict__ inputs, const int32_t* __restrict__ offsets, uint32_t B,
+                                                                   uint32_t level, float scale, uint32_t resolution, uint32_t gridtype,
+                                                                   bool align_corners, uint32_t interp, uint32_t* __restrict__ keys,
+                                                                   uint32_t* __restrict__ vals) {
+    const uint32_t off0 = (uint32_t)offsets[level];
+    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
+    LevelIndexer<D> indexer;
+    indexer.init(gridtype, align_corners, hashmap_size, resolution);
+    for (uint32_t b = blockIdx.x * F64_THREADS + threadIdx.x; b < B; b += gridDim.x * F64_THREADS) {
+        float frac[D], deriv[D];
+        uint32_t cell[D];
+        const bool inside = locate<D>(inputs + (size_t)b * D, scale, align_corners, interp, frac, deriv, cell);
+#pragma unroll
+        for (int k = 0; k < (1 << D); k++) {
+            uint32_t pg[D];
+#pragma unroll
+            for (int d = 0; d < D; d++) pg[d] = cell[d] + ((k >> d) & 1);
+            const uint32_t slot = (b << D) | (uint32_t)k;
+            keys[slot] = inside ? indexer(pg) : F64_NO_ENTRY;
+            vals[slot] = slot;
+        }
+    }
+}
+
+// digit counts of one workgroup's range: hist[digit * groups + group]
+__global__ __launch_bounds__(RADIX_TILE) void k_f64_radix_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t tiles_per_group,
+                                                                uint32_t groups, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t begin = blockIdx.x * tiles_per_group * RADIX_TILE;
+    const uint32_t end = min(n, begin + tiles_per_group * RADIX_TILE);
+    for (uint32_t i = begin + threadIdx.x; i < end; i += RADIX_TILE) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
+    __syncthreads();
+    hist[threadIdx.x * groups + blockIdx.x] = h[threadIdx.x];
+}
+
+// one workgroup per digit: exclusive scan of the digit's group counts in place, the digit's total to totals[digit]
+__global__ __launch_bounds__(RADIX_MAX_GROUPS) void k_f64_radix_scan(uint32_t* __restrict__ hist, uint32_t groups, uint32_t* __restrict__ totals) {
+    __shared__ uint32_t part[RADIX_MAX_GROUPS];
+    const uint32_t t = threadIdx.x, digit = blockIdx.x;
+    const uint32_t v = t < groups ? hist[digit * groups + t] : 0u;
+    part[t] = v;
+    __syncthreads();
+    for (uint32_t o = 1; o < RADIX_MAX_GROUPS; o <<= 1) {
+        const uint32_t a = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += a;
+        __syncthreads();
+    }
+    if (t < groups) hist[digit * groups + t] = part[t] - v;
+    if (t == RADIX_MAX_GROUPS - 1) totals[digit] = part[t];
+}
+
+// stable scatter: a workgroup walks its range tile by tile in order; inside a tile an item's rank among the earlier items with its digit
+// comes from the lanes of its wave (8 ballots -> the lanes with the same digit, mbcnt) and the counts of the earlier waves.  A digit's first
+// slot for this workgroup: the totals of the smaller digits (scanned here, by every workgroup) + its scanned group count
+__global__ __launch_bounds__(RADIX_TILE) void k_f64_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
+                                                                   uint32_t shift, uint32_t tiles_per_group, uint32_t groups,
+                                                                   const uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals,
+                                                                   uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
+    constexpr uint32_t WAVES = RADIX_TILE / 64;
+    __shared__ uint32_t run[256];
+    __shared__ uint32_t wave_count[WAVES][256];
+    const uint32_t t = threadIdx.x, wave = t >> 6;
+    run[t] = totals[t];
+    __syncthreads();
+    for (uint32_t o = 1; o < 256; o <<= 1) {
+        const uint32_t a = t >= o ? run[t - o] : 0u;
+        __syncthreads();
+        run[t] += a;
+        __syncthreads();
+    }
+    run[t] += hist[t * groups + blockIdx.x] - totals[t];
+    const uint32_t begin = blockIdx.x * tiles_per_group * RADIX_TILE;
+    const uint32_t end = min(n, begin + tiles_per_group * RADIX_TILE);
+    for (uint32_t base = begin; base < end; base += RADIX_TILE) {
+        const uint32_t i = base + t;
+        const bool valid = i < end;
+        uint32_t key = 0u, val = 0u, digit = 0u;
+        if (valid) {
+            key = keys_in[i];
+            val = vals_in[i];
+            digit = (key >> shift) & 255u;
+        }
+        uint64_t same = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; bit++) {
+            const bool set = (digit >> bit) & 1u;
+            const uint64_t m = __ballot(valid && set);
+            same &= set ? m : ~m;
+        }
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
+#pragma unroll
+        for (uint32_t w = 0; w < WAVES; w++) wave_count[w][t] = 0u;
+        __syncthreads();
+        if (valid && rank == 0u) wave_count[wave][digit] = (uint32_t)__popcll(same);
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = run[digit] + rank;
+            for (uint32_t w = 0; w < wave; w++) pos += wave_count[w][digit];
+            NGP_BOUNDS(pos < n);
+            keys_out[pos] = key;
+            vals_out[pos] = val;
+        }
+        __syncthreads();
+        uint32_t add = 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < WAVES; w++) add += wave_count[w][t];
+        run[t] += add;
+        __syncthreads();
+    }
+}
+
+// one lane per run of equal entries (the run's first record): the contributions in slot order, summed in fp64, added once
+template <int D, int C>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_sum(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
+                                                               const double* __restrict__ grad, const float* __restrict__ inputs,
+                                                               const int32_t* __restrict__ offsets, double* __restrict__ grad_grid, uint32_t B,
+                                                               uint32_t level, float scale, bool align_corners, uint32_t interp) {
+    for (uint32_t i = blockIdx.x * F64_THREADS + threadIdx.x; i < n; i += gridDim.x * F64_THREADS) {
+        const uint32_t e = keys[i];
+        if (e == F64_NO_ENTRY || (i > 0u && keys[i - 1u] == e)) continue;
+        double acc[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) acc[c] = 0.0;
+        for (uint32_t j = i; j < n && keys[j] == e; j++) {
+            const uint32_t slot = vals[j], b = slot >> D, k = slot & ((1u << D) - 1u);
+            NGP_BOUNDS(b < B);
+            float frac[D], deriv[D];
+            uint32_t cell[D];
+            locate<D>(inputs + (size_t)b * D, scale, align_corners, interp, frac, deriv, cell);
+            const double w = (double)corner_weight<D>(frac, k);
+            const double* g = grad + ((size_t)level * B + b) * C;
+#pragma unroll
+            for (int c = 0; c < C; c++) acc[c] = __builtin_fma(w, g[c], acc[c]);
+        }
+        const uint32_t off0 = (uint32_t)offsets[level];
+        NGP_BOUNDS(e < (uint32_t)offsets[level + 1] - off0);
+        double* dst = grad_grid + ((size_t)off0 + e) * C;
+#pragma unroll
+        for (int c = 0; c < C; c++) dst[c] += acc[c];
+    }
+}
+
+// gridencoder.cu:343-369: grad_inputs[b, d] = sum_{l, c} grad[l, b, c] * dy_dx[b, l, d, c]
+__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_input_bwd(const double* __restrict__ grad, const double* __restrict__ dy_dx,
+                                                                     double* __restrict__ grad_inputs, uint32_t B, uint32_t L, uint32_t D, uint32_t C) {
+    const uint32_t t = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (t >= B * D) return;
+    const uint32_t b = t / D, d = t - b * D;
+    const double* dd = dy_dx + (size_t)b * L * D * C;
+    double r = 0.0;
+    for (uint32_t l = 0; l < L; l++)
+        for (uint32_t c = 0; c < C; c++) r = __builtin_fma(grad[((size_t)l * B + b) * C + c], dd[(l * D + d) * C + c], r);
+    grad_inputs[t] = r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// grid encoder: total-variation gradient (gridencoder.cu:506-610), fp64 throughout
+// ------------------------------------------------------------------------------------------------
+template <int D, int C>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_grad_tv(const double* __restrict__ inputs, const double* __restrict__ grid,
+                                                              double* __restrict__ grad, const int32_t* __restrict__ offsets, float weight, uint32_t B,
+                                                              GridLevels lv, uint32_t gridtype, bool align_corners) {
+    const uint32_t level = blockIdx.y;
+    const uint32_t off0 = (uint32_t)offsets[level];
+    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
+    const uint32_t resolution = lv.res[level];
+    const double scale = (double)lv.scale[level];
+    LevelIndexer<D> indexer;
+    indexer.init(gridtype, align_corners, hashmap_size, resolution);
+    const double* __restrict__ table = grid + (size_t)off0 * C;
+    double* __restrict__ gtable = grad + (size_t)off0 * C;
+    const double w = (double)weight / (double)(2 * D);
+    for (uint32_t b = blockIdx.x * F64_THREADS + threadIdx.x; b < B; b += gridDim.x * F64_THREADS) {
+        double x[D];
+        bool inside = true;
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            x[d] = inputs[(size_t)b * D + d];
+            inside = inside && !(x[d] < 0.0 || x[d] > 1.0);
+        }
+        if (!inside) continue;
+        uint32_t pg[D];
+#pragma unroll
+        for (int d = 0; d < D; d++) pg[d] = (uint32_t)floor(__builtin_fma(x[d], scale, align_corners ? 0.0 : 0.5));
+        const double* ctr = table + (size_t)indexer(pg) * C;
+        double* gctr = gtable + (size_t)indexer(pg) * C;
+        double res[C], idelta[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) res[c] = idelta[c] = 0.0;
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            const uint32_t cur = pg[d];
+            if (cur < resolution) {
+                pg[d] = cur + 1u;
+                const double* o = table + (size_t)indexer(pg) * C;
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    const double gv = ctr[c] - o[c];
+                    res[c] += gv;
+                    idelta[c] = __builtin_fma(gv, gv, idelta[c]);
+                }
+            }
+            if (cur > 0u) {
+                pg[d] = cur - 1u;
+                const double* o = table + (size_t)indexer(pg) * C;
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    const double gv = ctr[c] - o[c];
+                    res[c] += gv;
+                    idelta[c] = __builtin_fma(gv, gv, idelta[c]);
+                }
+            }
+            pg[d] = cur;
+        }
+#pragma unroll
+        for (int c = 0; c < C; c++) atomicAdd(gctr + c, w * res[c] / sqrt(idelta[c] + 1e-9));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// SH encoder (shencoder.cu:27-382): one lane per direction, fp64 polynomials of sh_poly64.inc
+// ------------------------------------------------------------------------------------------------
+template <int BANDS, bool WITH_GRAD>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_sh_fwd(const double* __restrict__ inputs, double* __restrict__ outputs, uint32_t B,
+                                                             double* __restrict__ dy_dx) {
+    constexpr int N = BANDS * BANDS;
+    const uint32_t b = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (b >= B) return;
+    const double x = inputs[(size_t)b * 3], y = inputs[(size_t)b * 3 + 1], z = inputs[(size_t)b * 3 + 2];
+    double* out = outputs + (size_t)b * N;
+#define SH_OUT(i, v) out[i] = (v)
+    SH64_BAND_0_VALUES;
+    if constexpr (BANDS > 1) { SH64_BAND_1_VALUES; }
+    if constexpr (BANDS > 2) { SH64_BAND_2_VALUES; }
+    if constexpr (BANDS > 3) { SH64_BAND_3_VALUES; }
+    if constexpr (BANDS > 4) { SH64_BAND_4_VALUES; }
+    if constexpr (BANDS > 5) { SH64_BAND_5_VALUES; }
+    if constexpr (BANDS > 6) { SH64_BAND_6_VALUES; }
+    if constexpr (BANDS > 7) { SH64_BAND_7_VALUES; }
+#undef SH_OUT
+    if constexpr (WITH_GRAD) {
+        // dy_dx [B, 3, N]
+        double* gx = dy_dx + (size_t)b * 3 * N;
+        double* gy = gx + N;
+        double* gz = gx + 2 * N;
+#define SH_DX(i, v) gx[i] = (v)
+#define SH_DY(i, v) gy[i] = (v)
+#define SH_DZ(i, v) gz[i] = (v)
+        SH64_BAND_0_GRADS;
+        if constexpr (BANDS > 1) { SH64_BAND_1_GRADS; }
+        if constexpr (BANDS > 2) { SH64_BAND_2_GRADS; }
+        if constexpr (BANDS > 3) { SH64_BAND_3_GRADS; }
+        if constexpr (BANDS > 4) { SH64_BAND_4_GRADS; }
+        if constexpr (BANDS > 5) { SH64_BAND_5_GRADS; }
+        if constexpr (BANDS > 6) { SH64_BAND_6_GRADS; }
+        if constexpr (BANDS > 7) { SH64_BAND_7_GRADS; }
+#undef SH_DX
+#undef SH_DY
+#undef SH_DZ
+    }
+}
+
+__global__ __launch_bounds__(F64_THREADS) void k_f64_sh_bwd(const double* __restrict__ grad, uint32_t B, uint32_t N, const double* __restrict__ dy_dx,
+                                                             double* __restrict__ grad_inputs) {
+    const uint32_t t = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (t >= B * 3) return;
+    const uint32_t b = t / 3, d = t - b * 3;
+    const double* g = grad + (size_t)b * N;
+    const double* dd = dy_dx + ((size_t)b * 3 + d) * N;
+    double r = grad_inputs[t];
+    for (uint32_t i = 0; i < N; i++) r = __builtin_fma(g[i], dd[i], r);
+    grad_inputs[t] = r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ray utilities (raymarching.cu:92-300)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(F64_THREADS) void k_f64_near_far(const double* __restrict__ rays_o, const double* __restrict__ rays_d,
+                                                               const double* __restrict__ aabb, uint32_t N, float min_near, double* __restrict__ nears,
+                                                               double* __restrict__ fars) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const double ox = rays_o[(size_t)n * 3], oy = rays_o[(size_t)n * 3 + 1], oz = rays_o[(size_t)n * 3 + 2];
+    const double rdx = 1.0 / rays_d[(size_t)n * 3], rdy = 1.0 / rays_d[(size_t)n * 3 + 1], rdz = 1.0 / rays_d[(size_t)n * 3 + 2];
+    nears[n] = fars[n] = DBL_MAX;
+    double near = (aabb[0] - ox) * rdx, far = (aabb[3] - ox) * rdx, t;
+    if (near > far) { t = near; near = far; far = t; }
+    double ny = (aabb[1] - oy) * rdy, fy = (aabb[4] - oy) * rdy;
+    if (ny > fy) { t = ny; ny = fy; fy = t; }
+    if (near > fy || ny > far) return;
+    if (ny > near) near = ny;
+    if (fy < far) far = fy;
+    double nz = (aabb[2] - oz) * rdz, fz = (aabb[5] - oz) * rdz;
+    if (nz > fz) { t = nz; nz = fz; fz = t; }
+    if (near > fz || nz > far) return;
+    if (nz > near) near = nz;
+    if (fz < far) far = fz;
+    if (near < (double)min_near) near = (double)min_near;
+    nears[n] = near;
+    fars[n] = far;
+}
+
+__global__ __launch_bounds__(F64_THREADS) void k_f64_sph_from_ray(const double* __restrict__ rays_o, const double* __restrict__ rays_d, float radius,
+                                                                   uint32_t N, double* __restrict__ coords) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const double ox = rays_o[(size_t)n * 3], oy = rays_o[(size_t)n * 3 + 1], oz = rays_o[(size_t)n * 3 + 2];
+    const double dx = rays_d[(size_t)n * 3], dy = rays_d[(size_t)n * 3 + 1], dz = rays_d[(size_t)n * 3 + 2];
+    const double r = (double)radius;
+    const double A = dx * dx + dy * dy + dz * dz;
+    const double Bh = ox * dx + oy * dy + oz * dz;
+    const double Cc = ox * ox + oy * oy + oz * oz - r * r;
+    const double t = (-Bh + sqrt(Bh * Bh - A * Cc)) / A;
+    const double x = ox + t * dx, y = oy + t * dy, z = oz + t * dz;
+    const double theta = atan2(sqrt(x * x + z * z), y);
+    const double phi = atan2(z, x);
+    const double RPI = 0.31830988618379067;  // 1 / pi
+    coords[(size_t)n * 2] = 2.0 * theta * RPI - 1.0;
+    coords[(size_t)n * 2 + 1] = phi * RPI;
+}
+
+__global__ __launch_bounds__(F64_THREADS) void k_f64_packbits(const double* __restrict__ grid, uint32_t N, float thresh, uint8_t* __restrict__ bitfield) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const double* g = grid + (size_t)n * 8;
+    const double th = (double)thresh;
+    uint32_t bits = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; i++) bits |= g[i] > th ? (1u << i) : 0u;
+    bitfield[n] = (uint8_t)bits;
+}
+
+// ------------------------------------------------------------------------------------------------
+// compositing (raymarching.cu:488-661, 819-905): the reference's per-ray loops, one lane per ray
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_fwd(const double* __restrict__ sigmas, const double* __restrict__ rgbs,
+                                                                          const double* __restrict__ deltas, const int32_t* __restrict__ rays, uint32_t M,
+                                                                          uint32_t N, float T_thresh, double* __restrict__ weights_sum,
+                                                                          double* __restrict__ depth, double* __restrict__ image) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    const double th = (double)T_thresh;
+    double r = 0.0, g = 0.0, b = 0.0, ws = 0.0, d = 0.0, T = 1.0, t = 0.0;
+    if (num != 0u && offset + num <= M) {
+        for (uint32_t s = 0; s < num; s++) {
+            const size_t o = (size_t)offset + s;
+            const double alpha = 1.0 - exp(-sigmas[o] * deltas[o * 2]);
+            const double w = alpha * T;
+            r += w * rgbs[o * 3];
+            g += w * rgbs[o * 3 + 1];
+            b += w * rgbs[o * 3 + 2];
+            t += deltas[o * 2 + 1];
+            d += w * t;
+            ws += w;
+            T *= 1.0 - alpha;
+            if (T < th) break;  // the sample that drives T below the threshold is composited (raymarching.cu:557-560)
+        }
+    }
+    weights_sum[index] = ws;
+    depth[index] = d;
+    image[index * 3] = r;
+    image[index * 3 + 1] = g;
+    image[index * 3 + 2] = b;
+}
+
+__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_bwd(const double* __restrict__ grad_ws, const double* __restrict__ grad_image,
+                                                                          const double* __restrict__ sigmas, const double* __restrict__ rgbs,
+                                                                          const double* __restrict__ deltas, const int32_t* __restrict__ rays,
+                                                                          const double* __restrict__ weights_sum, const double* __restrict__ image,
+                                                                          uint32_t M, uint32_t N, float T_thresh, double* __restrict__ grad_sigmas,
+                                                                          double* __restrict__ grad_rgbs) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    if (num == 0u || offset + num > M) return;
+    const double th = (double)T_thresh;
+    const double gi0 = grad_image[index * 3], gi1 = grad_image[index * 3 + 1], gi2 = grad_image[index * 3 + 2], gw = grad_ws[index];
+    const double rf = image[index * 3], gf = image[index * 3 + 1], bf = image[index * 3 + 2], wsf = weights_sum[index];
+    double r = 0.0, g = 0.0, b = 0.0, T = 1.0;
+    for (uint32_t s = 0; s < num; s++) {
+        const size_t o = (size_t)offset + s;
+        const double d0 = deltas[o * 2];
+        const double cr = rgbs[o * 3], cg = rgbs[o * 3 + 1], cb = rgbs[o * 3 + 2];
+        const double alpha = 1.0 - exp(-sigmas[o] * d0);
+        const double w = alpha * T;
+        r += w * cr;
+        g += w * cg;
+        b += w * cb;
+        T *= 1.0 - alpha;  // transmittance after this sample
+        grad_rgbs[o * 3] = gi0 * w;
+        grad_rgbs[o * 3 + 1] = gi1 * w;
+        grad_rgbs[o * 3 + 2] = gi2 * w;
+        grad_sigmas[o] = d0 * (gi0 * (T * cr - (rf - r)) + gi1 * (T * cg - (gf - g)) + gi2 * (T * cb - (bf - b)) + gw * (1.0 - wsf));
+        if (T < th) break;
+    }
+}
+
+__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* __restrict__ rays_alive,
+                                                                     double* __restrict__ rays_t, const double* __restrict__ sigmas,
+                                                                     const double* __restrict__ rgbs, const double* __restrict__ deltas,
+                                                                     double* __restrict__ weights_sum, double* __restrict__ depth,
+                                                                     double* __restrict__ image) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= n_alive) return;
+    const uint32_t index = (uint32_t)rays_alive[n];
+    const double* sg = sigmas + (size_t)n * n_step;
+    const double* rg = rgbs + (size_t)n * n_step * 3;
+    const double* de = deltas + (size_t)n * n_step * 2;
+    const double th = (double)T_thresh;
+    double t = rays_t[index], ws = weights_sum[index], d = depth[index];
+    double r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
+    uint32_t step = 0;
+    while (step < n_step) {
+        const double d0 = de[step * 2];
+        if (d0 == 0.0) break;
+        const double alpha = 1.0 - exp(-sg[step] * d0);
+        const double T = 1.0 - ws;
+        const double w = alpha * T;
+        ws += w;
+        t += de[step * 2 + 1];
+        d += w * t;
+        r += w * rg[step * 3];
+        g += w * rg[step * 3 + 1];
+        b += w * rg[step * 3 + 2];
+        if (T < th) break;
+        step++;
+    }
+    if (step < n_step) rays_alive[n] = -1;
+    else rays_t[index] = t;
+    weights_sum[index] = ws;
+    depth[index] = d;
+    image[index * 3] = r;
+    image[index * 3 + 1] = g;
+    image[index * 3 + 2] = b;
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+#define NGP_F64_DISPATCH_DC(FN, ...)                                    \
+    switch (D * 16 + C) {                                               \
+        case 2 * 16 + 1: return FN<2, 1>(__VA_ARGS__);                  \
+        case 2 * 16 + 2: return FN<2, 2>(__VA_ARGS__);                  \
+        case 2 * 16 + 4: return FN<2, 4>(__VA_ARGS__);                  \
+        case 2 * 16 + 8: return FN<2, 8>(__VA_ARGS__);                  \
+        case 3 * 16 + 1: return FN<3, 1>(__VA_ARGS__);                  \
+        case 3 * 16 + 2: return FN<3, 2>(__VA_ARGS__);                  \
+        case 3 * 16 + 4: return FN<3, 4>(__VA_ARGS__);                  \
+        case 3 * 16 + 8: return FN<3, 8>(__VA_ARGS__);                  \
+        case 4 * 16 + 1: return FN<4, 1>(__VA_ARGS__);                  \
+        case 4 * 16 + 2: return FN<4, 2>(__VA_ARGS__);                  \
+        case 4 * 16 + 4: return FN<4, 4>(__VA_ARGS__);                  \
+        case 4 * 16 + 8: return FN<4, 8>(__VA_ARGS__);                  \
+        case 5 * 16 + 1: return FN<5, 1>(__VA_ARGS__);                  \
+        case 5 * 16 + 2: return FN<5, 2>(__VA_ARGS__);                  \
+        case 5 * 16 + 4: return FN<5, 4>(__VA_ARGS__);                  \
+        case 5 * 16 + 8: return FN<5, 8>(__VA_ARGS__);                  \
+        default: break;                                                 \
+    }
+
+static void f64_levels(GridLevels& lv, uint32_t L, float S, uint32_t H) { ngp_grid_level_table(L, S, H, lv.scale, lv.res); }
+
+template <int D, int C>
+static int launch_f64_forward(const float* inputs, const void* emb, const int32_t* offsets, void* outputs, uint32_t B, uint32_t L, const GridLevels& lv,
+                              void* dy_dx, uint32_t gridtype, bool ac, uint32_t interp, hipStream_t st) {
+    const dim3 grid(f64_blocks(B), L, 1);
+    if (dy_dx)
+        hipLaunchKernelGGL((k_f64_grid_fwd<D, C, true>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L, lv,
+                           (double*)dy_dx, gridtype, ac, interp);
+    else
+        hipLaunchKernelGGL((k_f64_grid_fwd<D, C, false>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L,
+                           lv, (double*)nullptr, gridtype, ac, interp);
+    return check_launch("grid_encode_forward(fp64)");
+}
+
+int f64_grid_forward(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                     float S, uint32_t H, void* dy_dx, uint32_t gridtype, bool align_corners, uint32_t interp, hipStream_t st) {
+    if (B == 0) return NGP_OK;
+    GridLevels lv;
+    f64_levels(lv, L, S, H);
+    NGP_F64_DISPATCH_DC(launch_f64_forward, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, align_corners, interp, st)
+    set_error("grid_encode_forward: unsupported (D=%u, C=%u)", D, C);
+    return NGP_ERR_INVALID;
+}
+
+// workspace: keys / values twice (ping-pong) for the B << D records of one level, then the digit counts and totals
+static size_t f64_array_bytes(uint64_t n) { return (n * sizeof(uint32_t) + 255) & ~(size_t)255; }
+
+size_t f64_grid_backward_workspace_bytes(uint32_t B, uint32_t D) {
+    if (B == 0 || D < 2 || D > 5) return 0;
+    return 4 * f64_array_bytes((uint64_t)B << D) + RADIX_COUNT_WORDS * sizeof(uint32_t);
+}
+
+template <int D, int C>
+static int launch_f64_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_emb, uint32_t B, uint32_t L,
+                               const GridLevels& lv, uint32_t gridtype, bool ac, uint32_t interp, void* workspace, hipStream_t st) {
+    const uint32_t n = B << D;
+    char* ws = (char*)workspace;
+    const size_t a = f64_array_bytes(n);
+    uint32_t* keys[2] = {(uint32_t*)ws, (uint32_t*)(ws + 2 * a)};
+    uint32_t* vals[2] = {(uint32_t*)(ws + a), (uint32_t*)(ws + 3 * a)};
+    uint32_t* hist = (uint32_t*)(ws + 4 * a);
+    uint32_t* totals = hist + 256 * RADIX_MAX_GROUPS;
+    const uint32_t tiles = cdiv(n, RADIX_TILE);
+    const uint32_t tiles_per_group = cdiv(tiles, RADIX_MAX_GROUPS);
+    const uint32_t groups = cdiv(tiles, tiles_per_group);
+    for (uint32_t level = 0; level < L; level++) {
+        hipLaunchKernelGGL((k_f64_grid_records<D>), dim3(f64_blocks(B)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, lv.scale[level],
+                           lv.res[level], gridtype, ac, interp, keys[0], vals[0]);
+        for (uint32_t pass = 0; pass < 4; pass++) {
+            const uint32_t src = pass & 1u, shift = 8u * pass;
+            hipLaunchKernelGGL(k_f64_radix_hist, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], n, shift, tiles_per_group, groups, hist);
+            hipLaunchKernelGGL(k_f64_radix_scan, dim3(256), dim3(RADIX_MAX_GROUPS), 0, st, hist, groups, totals);
+            hipLaunchKernelGGL(k_f64_radix_scatter, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], vals[src], n, shift, tiles_per_group, groups, hist,
+                               totals, keys[src ^ 1u], vals[src ^ 1u]);
+        }
+        // (an even number of passes: the sorted records are back in keys[0] / vals[0])
+        hipLaunchKernelGGL((k_f64_grid_sum<D, C>), dim3(f64_blocks(n)), dim3(F64_THREADS), 0, st, keys[0], vals[0], n, (const double*)grad, inputs,
+                           offsets, (double*)grad_emb, B, level, lv.scale[level], ac, interp);
+        const int rc = check_launch("grid_encode_backward(fp64)");
+        if (rc) return rc;
+    }
+    return NGP_OK;
+}
+
+int f64_grid_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C,
+                      uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, bool align_corners, uint32_t interp,
+                      void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (B == 0) return NGP_OK;
+    NGP_REQUIRE(((uint64_t)B << D) <= (1ull << 31), NGP_ERR_INVALID, "grid_encode_backward: fp64: B * 2^D must not exceed 2^31 (B=%u, D=%u)", B, D);
+    const size_t need = f64_grid_backward_workspace_bytes(B, D);
+    NGP_REQUIRE(workspace && workspace_bytes >= need, NGP_ERR_INVALID,
+                "grid_encode_backward: fp64 needs a workspace of %zu bytes (ngp_grid_backward_workspace_bytes), got %zu", need,
+                workspace ? workspace_bytes : (size_t)0);
+    NGP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, NGP_ERR_INVALID, "grid_encode_backward: fp64: workspace must be 256-byte aligned");
+    GridLevels lv;
+    f64_levels(lv, L, S, H);
+    int rc = NGP_ERR_INVALID;
+    bool dispatched = true;
+    switch (D * 16 + C) {
+#define NGP_F64_BWD_CASE(DD, CC)                                                                                                                  \
+        case DD * 16 + CC:                                                                                                                        \
+            rc = launch_f64_backward<DD, CC>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, align_corners, interp, workspace, st); \
+            break;
+        NGP_F64_BWD_CASE(2, 1) NGP_F64_BWD_CASE(2, 2) NGP_F64_BWD_CASE(2, 4) NGP_F64_BWD_CASE(2, 8)
+        NGP_F64_BWD_CASE(3, 1) NGP_F64_BWD_CASE(3, 2) NGP_F64_BWD_CASE(3, 4) NGP_F64_BWD_CASE(3, 8)
+        NGP_F64_BWD_CASE(4, 1) NGP_F64_BWD_CASE(4, 2) NGP_F64_BWD_CASE(4, 4) NGP_F64_BWD_CASE(4, 8)
+        NGP_F64_BWD_CASE(5, 1) NGP_F64_BWD_CASE(5, 2) NGP_F64_BWD_CASE(5, 4) NGP_F64_BWD_CASE(5, 8)
+#undef NGP_F64_BWD_CASE
+        default: dispatched = false; break;
+    }
+    if (!dispatched) {
+        set_error("grid_encode_backward: unsupported (D=%u, C=%u)", D, C);
+        return NGP_ERR_INVALID;
+    }
+    if (rc || !(dy_dx && grad_inputs)) return rc;
+    hipLaunchKernelGGL(k_f64_grid_input_bwd, dim3(cdiv(B * D, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, (const double*)dy_dx,
+                       (double*)grad_inputs, B, L, D, C);
+    return check_launch("grid_encode_backward(fp64 input)");
+}
+
+template <int D, int C>
+static int launch_f64_tv(const void* inputs, const void* emb, void* grad, const int32_t* offsets, float weight, uint32_t B, uint32_t L,
+                         const GridLevels& lv, uint32_t gridtype, bool ac, hipStream_t st) {
+    hipLaunchKernelGGL((k_f64_grad_tv<D, C>), dim3(f64_blocks(B), L, 1), dim3(F64_THREADS), 0, st, (const double*)inputs, (const double*)emb,
+                       (double*)grad, offsets, weight, B, lv, gridtype, ac);
+    return check_launch("grad_total_variation(fp64)");
+}
+
+int f64_grad_tv(const void* inputs, const void* embeddings, void* grad, const int32_t* offsets, float weight, uint32_t B, uint32_t D, uint32_t C,
+                uint32_t L, float S, uint32_t H, uint32_t gridtype, bool align_corners, hipStream_t st) {
+    if (B == 0) return NGP_OK;
+    GridLevels lv;
+    f64_levels(lv, L, S, H);
+    NGP_F64_DISPATCH_DC(launch_f64_tv, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, align_corners, st)
+    set_error("grad_total_variation: unsupported (D=%u, C=%u)", D, C);
+    return NGP_ERR_INVALID;
+}
+
+template <int BANDS>
+static int launch_f64_sh(const void* inputs, void* outputs, uint32_t B, void* dy_dx, hipStream_t st) {
+    const dim3 grid(cdiv(B, F64_THREADS));
+    if (dy_dx)
+        hipLaunchKernelGGL((k_f64_sh_fwd<BANDS, true>), grid, dim3(F64_THREADS), 0, st, (const double*)inputs, (double*)outputs, B, (double*)dy_dx);
+    else
+        hipLaunchKernelGGL((k_f64_sh_fwd<BANDS, false>), grid, dim3(F64_THREADS), 0, st, (const double*)inputs, (double*)outputs, B, (double*)nullptr);
+    return check_launch("sh_encode_forward(fp64)");
+}
+
+int f64_sh_forward(const void* inputs, void* outputs, uint32_t B, uint32_t C, void* dy_dx, hipStream_t st) {
+    if (B == 0) return NGP_OK;
+    switch (C) {
+        case 1: return launch_f64_sh<1>(inputs, outputs, B, dy_dx, st);
+        case 2: return launch_f64_sh<2>(inputs, outputs, B, dy_dx, st);
+        case 3: return launch_f64_sh<3>(inputs, outputs, B, dy_dx, st);
+        case 4: return launch_f64_sh<4>(inputs, outputs, B, dy_dx, st);
+        case 5: return launch_f64_sh<5>(inputs, outputs, B, dy_dx, st);
+        case 6: return launch_f64_sh<6>(inputs, outputs, B, dy_dx, st);
+        case 7: return launch_f64_sh<7>(inputs, outputs, B, dy_dx, st);
+        default: return launch_f64_sh<8>(inputs, outputs, B, dy_dx, st);
+    }
+}
+
+int f64_sh_backward(const void* grad, uint32_t B, uint32_t C, const void* dy_dx, void* grad_inputs, hipStream_t st) {
+    if (B == 0) return NGP_OK;
+    hipLaunchKernelGGL(k_f64_sh_bwd, dim3(cdiv(B * 3, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, B, C * C, (const double*)dy_dx,
+                       (double*)grad_inputs);
+    return check_launch("sh_encode_backward(fp64)");
+}
+
+}  // namespace ngp
+
+using namespace ngp;
+
+#define F64_LAUNCH_1D(kernel, count, st, ...) hipLaunchKernelGGL(kernel, dim3(cdiv((count), F64_THREADS)), dim3(F64_THREADS), 0, st, __VA_ARGS__)
+
+extern "C" int ngp_near_far_from_aabb_f64(const double* rays_o, const double* rays_d, const double* aabb, uint32_t N, float min_near, double* nears,
+                                          double* fars, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(rays_o && rays_d && aabb && nears && fars, NGP_ERR_INVALID, "near_far_from_aabb_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_near_far, N, as_stream(stream), rays_o, rays_d, aabb, N, min_near, nears, fars);
+    return check_launch("near_far_from_aabb_f64");
+}
+
+extern "C" int ngp_sph_from_ray_f64(const double* rays_o, const double* rays_d, float radius, uint32_t N, double* coords, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(rays_o && rays_d && coords, NGP_ERR_INVALID, "sph_from_ray_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_sph_from_ray, N, as_stream(stream), rays_o, rays_d, radius, N, coords);
+    return check_launch("sph_from_ray_f64");
+}
+
+extern "C" int ngp_packbits_f64(const double* grid, uint32_t N, float density_thresh, uint8_t* bitfield, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(grid && bitfield, NGP_ERR_INVALID, "packbits_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_packbits, N, as_stream(stream), grid, N, density_thresh, bitfield);
+    return check_launch("packbits_f64");
+}
+
+extern "C" int ngp_composite_rays_train_forward_f64(const double* sigmas, const double* rgbs, const double* deltas, const int32_t* rays, uint32_t M,
+                                                    uint32_t N, float T_thresh, double* weights_sum, double* depth, double* image,
+                                                    ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image, NGP_ERR_INVALID, "composite_rays_train_forward_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_composite_train_fwd, N, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image);
+    return check_launch("composite_rays_train_forward_f64");
+}
+
+extern "C" int ngp_composite_rays_train_backward_f64(const double* grad_weights_sum, const double* grad_image, const double* sigmas, const double* rgbs,
+                                                     const double* deltas, const int32_t* rays, const double* weights_sum, const double* image,
+                                                     uint32_t M, uint32_t N, float T_thresh, double* grad_sigmas, double* grad_rgbs,
+                                                     ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(grad_weights_sum && grad_image && sigmas && rgbs && deltas && rays && weights_sum && image && grad_sigmas && grad_rgbs, NGP_ERR_INVALID,
+                "composite_rays_train_backward_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_composite_train_bwd, N, as_stream(stream), grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
+                  T_thresh, grad_sigmas, grad_rgbs);
+    return check_launch("composite_rays_train_backward_f64");
+}
+
+extern "C" int ngp_composite_rays_f64(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* rays_alive, double* rays_t, const double* sigmas,
+                                      const double* rgbs, const double* deltas, double* weights_sum, double* depth, double* image,
+                                      ngp_stream_t stream) {
+    if (n_alive == 0) return NGP_OK;
+    NGP_REQUIRE(rays_alive && rays_t && sigmas && rgbs && deltas && weights_sum && depth && image, NGP_ERR_INVALID, "composite_rays_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_composite_rays, n_alive, as_stream(stream), n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum,
+                  depth, image);
+    return check_launch("composite_rays_f64");
+}

@@ -1,0 +1,116 @@
+// Grid-encoder indexing shared by the fp16/fp32 kernels (gridencoder.hip) and the fp64 ones (fp64.hip): the per-level table, the
+// corner-index rule and the position of a point inside a level.  One statement of each, so the fp64 path locates points and computes
+// interpolation weights exactly as the fp32 path does.
+#pragma once
+#include "common.h"
+
+namespace ngp {
+
+struct GridLevels {
+    float scale[NGP_MAX_LEVELS];
+    uint32_t res[NGP_MAX_LEVELS];
+};
+
+__constant__ const uint32_t kPrimes[7] = {1u, 2654435761u, 805459861u, 3674653429u,
+                                          2097192037u, 1434869437u, 2165219737u};
+
+// Wave-uniform description of how a level is indexed (gridencoder.cu:66-84, get_grid_index).
+template <int D>
+struct LevelIndexer {
+    uint32_t stride[D];  // dense strides of the dims that take part (0 for the others)
+    uint32_t size;       // hashmap_size
+    uint32_t mask;       // size-1 if size is a power of two else 0
+    bool hashed;
+    bool need_mod;       // false when a dense index is provably < size
+
+    __host__ __device__ __forceinline__ void init(uint32_t gridtype, bool align_corners, uint32_t hashmap_size,
+                                                  uint32_t resolution) {
+        uint32_t s = 1;
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+            if (s <= hashmap_size) {
+                stride[d] = s;
+                s *= align_corners ? resolution : (resolution + 1u);
+            } else {
+                stride[d] = 0;
+            }
+        }
+        hashed = (gridtype == 0u) && (s > hashmap_size);
+        // without align_corners every corner coordinate is <= resolution and the strides are powers of (resolution + 1):
+        // a dense index over all D dims is < (resolution+1)^D <= size.  With align_corners the stride base is
+        // `resolution` while a corner can sit AT `resolution`, so the index can wrap (gridencoder.cu:66-84).
+        need_mod = hashed || (s > hashmap_size) || align_corners;
+        size = hashmap_size;
+        mask = ((hashmap_size & (hashmap_size - 1u)) == 0u) ? hashmap_size - 1u : 0u;
+    }
+
+    // The same index from per-dimension terms: term(d, c) for the lower vertex coordinate c, step(d) to get the upper one
+    // ((c + 1) * k == c * k + k in uint32 arithmetic), combine() over one term per dimension.  A cell's 2^D corners then cost D
+    // multiplications instead of D * 2^D (v_mul_lo_u32 is a quarter-rate instruction).
+    __device__ __forceinline__ uint32_t term(int d, uint32_t c) const { return hashed ? c * kPrimes[d] : c * stride[d]; }
+    __device__ __forceinline__ uint32_t step(int d) const { return hashed ? kPrimes[d] : stride[d]; }
+    __device__ __forceinline__ uint32_t combine(const uint32_t (&t)[D]) const {
+        uint32_t idx = 0;
+        if (hashed) {
+#pragma unroll
+            for (int d = 0; d < D; d++) idx ^= t[d];
+        } else {
+#pragma unroll
+            for (int d = 0; d < D; d++) idx += t[d];
+        }
+        if (!need_mod) return idx;
+        return mask ? (idx & mask) : (idx % size);
+    }
+
+    __device__ __forceinline__ uint32_t operator()(const uint32_t (&pg)[D]) const {
+        uint32_t idx = 0;
+        if (hashed) {
+#pragma unroll
+            for (int d = 0; d < D; d++) idx ^= pg[d] * kPrimes[d];
+        } else {
+#pragma unroll
+            for (int d = 0; d < D; d++) idx += pg[d] * stride[d];
+        }
+        if (!need_mod) return idx;
+        return mask ? (idx & mask) : (idx % size);
+    }
+};
+
+// gridencoder.cu:146-159: position inside the level.  Returns false when the point is outside [0,1]^D.
+// Input mapping of the fused path: the module maps [-bound, bound] -> [0, 1] as (x + bound) * (1 / (2 bound)) in fp32
+// (grid.py:149 through PyTorch's scalar-division kernel); InputMap{shift = bound, scale = 1/(2 bound)} reproduces those two
+// roundings inside the kernel, scale == 0 means the inputs already are unit coordinates (the reference op contract).
+struct InputMap {
+    float shift, scale;
+};
+
+template <int D>
+__device__ __forceinline__ bool locate(const float* __restrict__ x, float scale, bool align_corners, uint32_t interp,
+                                       float (&frac)[D], float (&deriv)[D], uint32_t (&cell)[D], InputMap im = InputMap{0.0f, 0.0f}) {
+    float xv[D];
+    bool inside = true;
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        xv[d] = x[d];
+        if (im.scale != 0.0f) xv[d] = (xv[d] + im.shift) * im.scale;
+        inside = inside && !(xv[d] < 0.0f || xv[d] > 1.0f);
+    }
+    if (!inside) return false;
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        float p = __builtin_fmaf(xv[d], scale, align_corners ? 0.0f : 0.5f);
+        float fl = floorf(p);
+        cell[d] = (uint32_t)fl;
+        p -= (float)cell[d];
+        if (interp == 1u) {
+            deriv[d] = 6.0f * p * (1.0f - p);
+            p = p * p * (3.0f - 2.0f * p);
+        } else {
+            deriv[d] = 1.0f;
+        }
+        frac[d] = p;
+    }
+    return true;
+}
+
+}  // namespace ngp

@@ -18,6 +18,8 @@
 //   * the per-level scale/resolution table is computed on the host with a reproducible recipe (ngp_grid_level_table) and
 //     passed by value, so cell indices are bit-identical to the oracle; all per-level quantities are wave-uniform (SGPRs).
 #include "common.h"
+#include "grid_index.h"
+#include "fp64.h"
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,113 +27,6 @@
 #include <vector>
 
 namespace ngp {
-
-struct GridLevels {
-    float scale[NGP_MAX_LEVELS];
-    uint32_t res[NGP_MAX_LEVELS];
-};
-
-__constant__ const uint32_t kPrimes[7] = {1u, 2654435761u, 805459861u, 3674653429u,
-                                          2097192037u, 1434869437u, 2165219737u};
-
-// Wave-uniform description of how a level is indexed (gridencoder.cu:66-84, get_grid_index).
-template <int D>
-struct LevelIndexer {
-    uint32_t stride[D];  // dense strides of the dims that take part (0 for the others)
-    uint32_t size;       // hashmap_size
-    uint32_t mask;       // size-1 if size is a power of two else 0
-    bool hashed;
-    bool need_mod;       // false when a dense index is provably < size
-
-    __host__ __device__ __forceinline__ void init(uint32_t gridtype, bool align_corners, uint32_t hashmap_size,
-                                                  uint32_t resolution) {
-        uint32_t s = 1;
-#pragma unroll
-        for (int d = 0; d < D; d++) {
-            if (s <= hashmap_size) {
-                stride[d] = s;
-                s *= align_corners ? resolution : (resolution + 1u);
-            } else {
-                stride[d] = 0;
-            }
-        }
-        hashed = (gridtype == 0u) && (s > hashmap_size);
-        // without align_corners every corner coordinate is <= resolution and the strides are powers of (resolution + 1):
-        // a dense index over all D dims is < (resolution+1)^D <= size.  With align_corners the stride base is
-        // `resolution` while a corner can sit AT `resolution`, so the index can wrap (gridencoder.cu:66-84).
-        need_mod = hashed || (s > hashmap_size) || align_corners;
-        size = hashmap_size;
-        mask = ((hashmap_size & (hashmap_size - 1u)) == 0u) ? hashmap_size - 1u : 0u;
-    }
-
-    // The same index from per-dimension terms: term(d, c) for the lower vertex coordinate c, step(d) to get the upper one
-    // ((c + 1) * k == c * k + k in uint32 arithmetic), combine() over one term per dimension.  A cell's 2^D corners then cost D
-    // multiplications instead of D * 2^D (v_mul_lo_u32 is a quarter-rate instruction).
-    __device__ __forceinline__ uint32_t term(int d, uint32_t c) const { return hashed ? c * kPrimes[d] : c * stride[d]; }
-    __device__ __forceinline__ uint32_t step(int d) const { return hashed ? kPrimes[d] : stride[d]; }
-    __device__ __forceinline__ uint32_t combine(const uint32_t (&t)[D]) const {
-        uint32_t idx = 0;
-        if (hashed) {
-#pragma unroll
-            for (int d = 0; d < D; d++) idx ^= t[d];
-        } else {
-#pragma unroll
-            for (int d = 0; d < D; d++) idx += t[d];
-        }
-        if (!need_mod) return idx;
-        return mask ? (idx & mask) : (idx % size);
-    }
-
-    __device__ __forceinline__ uint32_t operator()(const uint32_t (&pg)[D]) const {
-        uint32_t idx = 0;
-        if (hashed) {
-#pragma unroll
-            for (int d = 0; d < D; d++) idx ^= pg[d] * kPrimes[d];
-        } else {
-#pragma unroll
-            for (int d = 0; d < D; d++) idx += pg[d] * stride[d];
-        }
-        if (!need_mod) return idx;
-        return mask ? (idx & mask) : (idx % size);
-    }
-};
-
-// gridencoder.cu:146-159: position inside the level.  Returns false when the point is outside [0,1]^D.
-// Input mapping of the fused path: the module maps [-bound, bound] -> [0, 1] as (x + bound) * (1 / (2 bound)) in fp32
-// (grid.py:149 through PyTorch's scalar-division kernel); InputMap{shift = bound, scale = 1/(2 bound)} reproduces those two
-// roundings inside the kernel, scale == 0 means the inputs already are unit coordinates (the reference op contract).
-struct InputMap {
-    float shift, scale;
-};
-
-template <int D>
-__device__ __forceinline__ bool locate(const float* __restrict__ x, float scale, bool align_corners, uint32_t interp,
-                                       float (&frac)[D], float (&deriv)[D], uint32_t (&cell)[D], InputMap im = InputMap{0.0f, 0.0f}) {
-    float xv[D];
-    bool inside = true;
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-        xv[d] = x[d];
-        if (im.scale != 0.0f) xv[d] = (xv[d] + im.shift) * im.scale;
-        inside = inside && !(xv[d] < 0.0f || xv[d] > 1.0f);
-    }
-    if (!inside) return false;
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-        float p = __builtin_fmaf(xv[d], scale, align_corners ? 0.0f : 0.5f);
-        float fl = floorf(p);
-        cell[d] = (uint32_t)fl;
-        p -= (float)cell[d];
-        if (interp == 1u) {
-            deriv[d] = 6.0f * p * (1.0f - p);
-            p = p * p * (3.0f - 2.0f * p);
-        } else {
-            deriv[d] = 1.0f;
-        }
-        frac[d] = p;
-    }
-    return true;
-}
 
 template <typename T, int C>
 struct Vec;  // C consecutive table features
@@ -2249,13 +2144,14 @@ static int launch_tv(const void* inputs, const void* emb, void* grad, const int3
         default: break;                                                                            \
     }
 
-static int check_grid_args(const char* fn, uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype) {
+static int check_grid_args(const char* fn, uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype, bool f64_ok = false) {
     (void)B;
     // the reference throws std::runtime_error{"GridEncoding: C must be 1, 2, 4, or 8."} for both (gridencoder.cu:381,398)
     NGP_REQUIRE(D >= 2 && D <= 5, NGP_ERR_INVALID, "%s: GridEncoding: input dim D must be 2, 3, 4 or 5 (got %u)", fn, D);
     NGP_REQUIRE(C == 1 || C == 2 || C == 4 || C == 8, NGP_ERR_INVALID, "%s: GridEncoding: C must be 1, 2, 4, or 8. (got %u)", fn, C);
     NGP_REQUIRE(L >= 1 && L <= NGP_MAX_LEVELS, NGP_ERR_INVALID, "%s: number of levels must be in [1, %d] (got %u)", fn, NGP_MAX_LEVELS, L);
-    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16, NGP_ERR_INVALID, "%s: embeddings must be float32 or float16", fn);
+    NGP_REQUIRE(dtype != NGP_F64 || f64_ok, NGP_ERR_INVALID, "%s: float64 is not provided by this entry point", fn);
+    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16 || dtype == NGP_F64, NGP_ERR_INVALID, "%s: embeddings must be float32 or float16", fn);
     return NGP_OK;
 }
 
@@ -2313,8 +2209,10 @@ static int grid_encode_forward_impl(const float* inputs, const void* embeddings,
                                     uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void* dy_dx,
                                     uint32_t gridtype, int align_corners, uint32_t interp, int dtype, float bound,
                                     const float* level_cost_host, ngp_stream_t stream) {
-    int rc = check_grid_args("grid_encode_forward", B, D, C, L, dtype);
+    int rc = check_grid_args("grid_encode_forward", B, D, C, L, dtype, true);
     NGP_REQUIRE(!(bound > 0.0f && dy_dx), NGP_ERR_INVALID, "grid_encode_forward: the fused input mapping does not provide dy_dx");
+    NGP_REQUIRE(dtype != NGP_F64 || (!(bound > 0.0f) && !sel.alt && !sel.rows), NGP_ERR_INVALID,
+                "grid_encode_forward: float64 is provided without the fused input mapping and the table selection only");
     const InputMap im = make_input_map(bound);
     if (rc) return rc;
     if (B == 0) return NGP_OK;
@@ -2323,6 +2221,8 @@ static int grid_encode_forward_impl(const float* inputs, const void* embeddings,
     fill_levels(lv, L, S, H);
     hipStream_t st = as_stream(stream);
     const bool ac = align_corners != 0;
+    if (dtype == NGP_F64)   // (fp64.hip; the level costs only steer the fp16/fp32 schedule)
+        return f64_grid_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype, ac, interp, st);
     const float* level_cost = level_cost_host;
     for (uint32_t l = 0; level_cost && l < L; l++)
         NGP_REQUIRE(level_cost[l] > 0.0f && level_cost[l] < 1e6f, NGP_ERR_INVALID, "grid_encode_forward: level_cost[%u] must be positive and finite", l);
@@ -2347,6 +2247,7 @@ extern "C" int ngp_grid_encode_forward_sel(const float* inputs, const void* embe
                                            const uint32_t* rows_dev, const int32_t* offsets, void* outputs, uint32_t B, uint32_t D, uint32_t C,
                                            uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
                                            float bound, const float* level_cost_host, ngp_stream_t stream) {
+    NGP_REQUIRE(dtype != NGP_F64, NGP_ERR_INVALID, "grid_encode_forward_sel: float64 is not provided by this entry point");
     NGP_REQUIRE(dtype == NGP_F16 || !(embeddings_alt && parity), NGP_ERR_INVALID, "grid_encode_forward_sel: the double-buffered table is fp16");
     TableSel sel = embeddings_alt && parity ? TableSel{reinterpret_cast<const _Float16*>(embeddings_alt), parity, nullptr} : TableSel{nullptr, nullptr, nullptr};
     sel.rows = rows_dev;
@@ -2393,6 +2294,7 @@ extern "C" int ngp_grid_encode_forward(const float* inputs, const void* embeddin
 
 extern "C" size_t ngp_grid_backward_workspace_bytes(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                                     uint32_t H, uint32_t gridtype, int align_corners, int dtype) {
+    if (dtype == NGP_F64) return L >= 1 && L <= NGP_MAX_LEVELS ? f64_grid_backward_workspace_bytes(B, D) : 0;   // (B and D only: no offsets needed)
     if (!offsets_host || L < 1 || L > NGP_MAX_LEVELS || D < 2 || D > 5) return 0;
     GridLevels lv;
     fill_levels(lv, L, S, H);
@@ -2550,6 +2452,16 @@ extern "C" int ngp_grid_encode_backward_ws(const void* grad, const float* inputs
                                            uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
                                            uint32_t interp, int dtype, float bound, const int32_t* offsets_host, void* workspace,
                                            size_t workspace_bytes, ngp_stream_t stream) {
+    if (dtype == NGP_F64) {   // the deterministic record-sort backward of fp64.hip
+        int rc = check_grid_args("grid_encode_backward", B, D, C, L, dtype, true);
+        if (rc) return rc;
+        NGP_REQUIRE(!(bound > 0.0f), NGP_ERR_INVALID, "grid_encode_backward: float64 is not provided with the fused input mapping");
+        if (B == 0) return NGP_OK;
+        NGP_REQUIRE(grad && inputs && offsets && grad_embeddings, NGP_ERR_INVALID, "grid_encode_backward: NULL tensor");
+        NGP_REQUIRE(!dy_dx == !grad_inputs, NGP_ERR_INVALID, "grid_encode_backward: dy_dx and grad_inputs must both be given or both be NULL");
+        return f64_grid_backward(grad, inputs, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners != 0, interp,
+                                 workspace, workspace_bytes, as_stream(stream));
+    }
     return ngp_grid_encode_backward_checked(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
                                             align_corners, interp, dtype, bound, offsets_host, workspace, workspace_bytes, nullptr, stream);
 }
@@ -2573,7 +2485,7 @@ extern "C" int ngp_grid_encode_backward(const void* grad, const float* inputs, c
 extern "C" int ngp_grad_total_variation(const void* inputs, const void* embeddings, void* grad, const int32_t* offsets,
                                         float weight, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                                         uint32_t gridtype, int align_corners, int dtype, ngp_stream_t stream) {
-    int rc = check_grid_args("grad_total_variation", B, D, C, L, dtype);
+    int rc = check_grid_args("grad_total_variation", B, D, C, L, dtype, true);
     if (rc) return rc;
     if (B == 0) return NGP_OK;
     NGP_REQUIRE(inputs && embeddings && grad && offsets, NGP_ERR_INVALID, "grad_total_variation: NULL tensor");
@@ -2581,6 +2493,7 @@ extern "C" int ngp_grad_total_variation(const void* inputs, const void* embeddin
     fill_levels(lv, L, S, H);
     hipStream_t st = as_stream(stream);
     const bool ac = align_corners != 0;
+    if (dtype == NGP_F64) return f64_grad_tv(inputs, embeddings, grad, offsets, weight, B, D, C, L, S, H, gridtype, ac, st);
     if (dtype == NGP_F16) {
         NGP_DISPATCH_DC(launch_tv, half_t, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st)
     } else {

@@ -12,6 +12,7 @@
 // stores per component.
 #include "common.h"
 #include "sh_poly.inc"
+#include "fp64.h"
 
 namespace ngp {
 
@@ -134,9 +135,10 @@ extern "C" int ngp_sh_encode_forward(const void* inputs, void* outputs, uint32_t
                                      ngp_stream_t stream) {
     NGP_REQUIRE(D == 3, NGP_ERR_INVALID, "sh_encode_forward: SH encoder only support input dim == 3 (got %u)", D);
     NGP_REQUIRE(C >= 1 && C <= 8, NGP_ERR_INVALID, "sh_encode_forward: SH encoder only supports degree in [1, 8] (got %u)", C);
-    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16, NGP_ERR_INVALID, "sh_encode_forward: inputs must be float32 or float16");
+    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16 || dtype == NGP_F64, NGP_ERR_INVALID, "sh_encode_forward: inputs must be float32, float16 or float64");
     if (B == 0) return NGP_OK;
     NGP_REQUIRE(inputs && outputs, NGP_ERR_INVALID, "sh_encode_forward: NULL tensor");
+    if (dtype == NGP_F64) return f64_sh_forward(inputs, outputs, B, C, dy_dx, as_stream(stream));   // (fp64.hip)
     return dtype == NGP_F16 ? dispatch_sh<half_t>(C, inputs, outputs, B, dy_dx, as_stream(stream))
                             : dispatch_sh<float>(C, inputs, outputs, B, dy_dx, as_stream(stream));
 }
@@ -146,9 +148,10 @@ extern "C" int ngp_sh_encode_backward(const void* grad, const void* inputs, uint
     (void)inputs;
     NGP_REQUIRE(D == 3, NGP_ERR_INVALID, "sh_encode_backward: SH encoder only support input dim == 3 (got %u)", D);
     NGP_REQUIRE(C >= 1 && C <= 8, NGP_ERR_INVALID, "sh_encode_backward: SH encoder only supports degree in [1, 8] (got %u)", C);
-    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16, NGP_ERR_INVALID, "sh_encode_backward: grad must be float32 or float16");
+    NGP_REQUIRE(dtype == NGP_F32 || dtype == NGP_F16 || dtype == NGP_F64, NGP_ERR_INVALID, "sh_encode_backward: grad must be float32, float16 or float64");
     if (B == 0) return NGP_OK;
     NGP_REQUIRE(grad && dy_dx && grad_inputs, NGP_ERR_INVALID, "sh_encode_backward: NULL tensor");
+    if (dtype == NGP_F64) return f64_sh_backward(grad, B, C, dy_dx, grad_inputs, as_stream(stream));
     hipStream_t st = as_stream(stream);
     if (dtype == NGP_F16)
         hipLaunchKernelGGL((k_sh_backward<half_t>), dim3(cdiv(B * 3, 256)), dim3(256), 0, st, (const half_t*)grad, B, C * C,

@@ -23,6 +23,7 @@ def _check_common(inputs, embeddings, offsets):
 def grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners, interp):
     _check_common(inputs, embeddings, offsets)
     capi.dense(outputs, 'outputs')
+    capi.float64_call((embeddings, 'embeddings'), (outputs, 'outputs'), (dy_dx, 'dy_dx'))
     code = capi.float_code(embeddings, 'embeddings')
     capi.check(capi.lib.ngp_grid_encode_forward(
         capi.ptr(inputs), capi.ptr(embeddings), capi.ptr(offsets), capi.ptr(outputs), B, D, C, L, float(S), H,
@@ -34,6 +35,7 @@ def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, 
     _check_common(inputs, embeddings, offsets)
     capi.dense(grad, 'grad')
     capi.dense(grad_embeddings, 'grad_embeddings')
+    capi.float64_call((grad, 'grad'), (embeddings, 'embeddings'), (grad_embeddings, 'grad_embeddings'), (dy_dx, 'dy_dx'), (grad_inputs, 'grad_inputs'))
     code = capi.float_code(grad, 'grad')
     # large fp16 batches: the binned, atomic-free scatter needs scratch memory (include/ngp_hip.h, ngp_grid_encode_backward_ws); the
     # reference signature has no workspace argument, so it is allocated here
@@ -49,6 +51,7 @@ def grad_total_variation(inputs, embeddings, grad, offsets, weight, B, D, C, L, 
     capi.dense(embeddings, 'embeddings')
     capi.dense(grad, 'grad')
     capi.dense(offsets, 'offsets')
+    capi.float64_call((inputs, 'inputs'), (embeddings, 'embeddings'), (grad, 'grad'))
     code = capi.float_code(embeddings, 'embeddings')
     if inputs.dtype != embeddings.dtype or grad.dtype != embeddings.dtype:
         raise RuntimeError("grad_total_variation: inputs, embeddings and grad must share one dtype")

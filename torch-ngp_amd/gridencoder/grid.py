@@ -145,7 +145,7 @@ class GridEncoder(nn.Module):
         if self.embeddings.grad is None:
             raise ValueError('grad is None, should be called after loss.backward() and before optimizer.step()!')
         if inputs is None:
-            pts = torch.rand(B, self.input_dim, device=self.embeddings.device)
+            pts = torch.rand(B, self.input_dim, device=self.embeddings.device, dtype=self.embeddings.dtype)   # (the op takes one dtype)
         else:
             pts = ((inputs + bound) / (2 * bound)).view(-1, self.input_dim)
             B = pts.shape[0]

@@ -15,6 +15,22 @@ def _f32(t, name):
     return t
 
 
+def _f64(pairs):
+    """float64 call of an entry with an fp64 twin (include/ngp_hip.h, *_f64): True when one floating tensor is float64 -- then all must be,
+    contiguous and on the device"""
+    if not capi.float64_call(*pairs):
+        return False
+    for t, n in pairs:
+        capi.dense(t, n)
+    return True
+
+
+def _f32_call(pairs, fn):
+    for t, n in pairs:
+        _f32(t, n)
+    return fn
+
+
 def _i32(t, name):
     capi.dense(t, name)
     capi.require_int32(t, name)
@@ -22,16 +38,15 @@ def _i32(t, name):
 
 
 def near_far_from_aabb(rays_o, rays_d, aabb, N, min_near, nears, fars):
-    for t, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (aabb, 'aabb'), (nears, 'nears'), (fars, 'fars')):
-        _f32(t, n)
-    capi.check(capi.lib.ngp_near_far_from_aabb(capi.ptr(rays_o), capi.ptr(rays_d), capi.ptr(aabb), N, float(min_near),
-                                               capi.ptr(nears), capi.ptr(fars), capi.stream()))
+    floats = ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (aabb, 'aabb'), (nears, 'nears'), (fars, 'fars'))
+    fn = capi.lib.ngp_near_far_from_aabb_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_near_far_from_aabb)
+    capi.check(fn(capi.ptr(rays_o), capi.ptr(rays_d), capi.ptr(aabb), N, float(min_near), capi.ptr(nears), capi.ptr(fars), capi.stream()))
 
 
 def sph_from_ray(rays_o, rays_d, radius, N, coords):
-    for t, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (coords, 'coords')):
-        _f32(t, n)
-    capi.check(capi.lib.ngp_sph_from_ray(capi.ptr(rays_o), capi.ptr(rays_d), float(radius), N, capi.ptr(coords), capi.stream()))
+    floats = ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (coords, 'coords'))
+    fn = capi.lib.ngp_sph_from_ray_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_sph_from_ray)
+    capi.check(fn(capi.ptr(rays_o), capi.ptr(rays_d), float(radius), N, capi.ptr(coords), capi.stream()))
 
 
 def morton3D(coords, N, indices):
@@ -45,11 +60,12 @@ def morton3D_invert(indices, N, coords):
 
 
 def packbits(grid, N, density_thresh, bitfield):
-    _f32(grid, 'grid')
+    floats = ((grid, 'grid'),)
+    fn = capi.lib.ngp_packbits_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_packbits)
     capi.dense(bitfield, 'bitfield')
     if bitfield.dtype != torch.uint8:
         raise RuntimeError("bitfield must be a uint8 tensor")
-    capi.check(capi.lib.ngp_packbits(capi.ptr(grid), N, float(density_thresh), capi.ptr(bitfield), capi.stream()))
+    capi.check(fn(capi.ptr(grid), N, float(density_thresh), capi.ptr(bitfield), capi.stream()))
 
 
 def packbits_capped(grid, N, density_thresh, thresh_cap, bitfield):
@@ -87,21 +103,20 @@ def march_rays_train(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, 
 
 
 def composite_rays_train_forward(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image):
-    for t, n in ((sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (depth, 'depth'), (image, 'image')):
-        _f32(t, n)
+    floats = ((sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (depth, 'depth'), (image, 'image'))
+    fn = capi.lib.ngp_composite_rays_train_forward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_composite_rays_train_forward)
     _i32(rays, 'rays')
-    capi.check(capi.lib.ngp_composite_rays_train_forward(capi.ptr(sigmas), capi.ptr(rgbs), capi.ptr(deltas), capi.ptr(rays), M, N,
-                                                         float(T_thresh), capi.ptr(weights_sum), capi.ptr(depth), capi.ptr(image),
-                                                         capi.stream()))
+    capi.check(fn(capi.ptr(sigmas), capi.ptr(rgbs), capi.ptr(deltas), capi.ptr(rays), M, N, float(T_thresh), capi.ptr(weights_sum), capi.ptr(depth),
+                  capi.ptr(image), capi.stream()))
 
 
 def composite_rays_train_backward(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh,
                                   grad_sigmas, grad_rgbs):
-    for t, n in ((grad_weights_sum, 'grad_weights_sum'), (grad_image, 'grad_image'), (sigmas, 'sigmas'), (rgbs, 'rgbs'),
-                 (deltas, 'deltas'), (weights_sum, 'weights_sum'), (image, 'image'), (grad_sigmas, 'grad_sigmas'), (grad_rgbs, 'grad_rgbs')):
-        _f32(t, n)
+    floats = ((grad_weights_sum, 'grad_weights_sum'), (grad_image, 'grad_image'), (sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'),
+              (weights_sum, 'weights_sum'), (image, 'image'), (grad_sigmas, 'grad_sigmas'), (grad_rgbs, 'grad_rgbs'))
+    fn = capi.lib.ngp_composite_rays_train_backward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_composite_rays_train_backward)
     _i32(rays, 'rays')
-    capi.check(capi.lib.ngp_composite_rays_train_backward(
+    capi.check(fn(
         capi.ptr(grad_weights_sum), capi.ptr(grad_image), capi.ptr(sigmas), capi.ptr(rgbs), capi.ptr(deltas), capi.ptr(rays),
         capi.ptr(weights_sum), capi.ptr(image), M, N, float(T_thresh), capi.ptr(grad_sigmas), capi.ptr(grad_rgbs), capi.stream()))
 
@@ -134,13 +149,12 @@ def march_rays_ex(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt
 
 
 def composite_rays(n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image):
-    for t, n in ((rays_t, 'rays_t'), (sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'), (weights_sum, 'weights_sum'),
-                 (depth, 'depth'), (image, 'image')):
-        _f32(t, n)
+    floats = ((rays_t, 'rays_t'), (sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (depth, 'depth'),
+              (image, 'image'))
+    fn = capi.lib.ngp_composite_rays_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_composite_rays)
     _i32(rays_alive, 'rays_alive')
-    capi.check(capi.lib.ngp_composite_rays(n_alive, n_step, float(T_thresh), capi.ptr(rays_alive), capi.ptr(rays_t), capi.ptr(sigmas),
-                                           capi.ptr(rgbs), capi.ptr(deltas), capi.ptr(weights_sum), capi.ptr(depth), capi.ptr(image),
-                                           capi.stream()))
+    capi.check(fn(n_alive, n_step, float(T_thresh), capi.ptr(rays_alive), capi.ptr(rays_t), capi.ptr(sigmas), capi.ptr(rgbs), capi.ptr(deltas),
+                  capi.ptr(weights_sum), capi.ptr(depth), capi.ptr(image), capi.stream()))
 
 
 def compact_rays(rays_alive, n_alive, out_alive, out_count):

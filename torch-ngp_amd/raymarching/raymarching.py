@@ -43,7 +43,8 @@ class _near_far_from_aabb(Function):
     @staticmethod
     @_f32_fwd
     def forward(ctx, rays_o, rays_d, aabb, min_near=0.2):
-        """rays_o/d [N,3], aabb [6] (xmin,ymin,zmin,xmax,ymax,zmax) -> nears, fars [N]; a miss yields FLT_MAX for both"""
+        """rays_o/d [N,3], aabb [6] (xmin,ymin,zmin,xmax,ymax,zmax) -> nears, fars [N]; a miss yields FLT_MAX for both
+        (DBL_MAX for float64 tensors)"""
         rays_o, rays_d = _rays(rays_o), _rays(rays_d)
         n_rays = rays_o.shape[0]
         nears = torch.empty(n_rays, dtype=rays_o.dtype, device=rays_o.device)
