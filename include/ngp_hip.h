@@ -97,6 +97,27 @@ int ngp_grid_corner_indices(const float* inputs, const int32_t* offsets, uint32_
  * Restates gridencoder.cu:137-139 with a reproducible exp2. */
 int ngp_grid_level_table(uint32_t L, float S, uint32_t H, float* scale_out, uint32_t* resolution_out);
 
+/* Second order (no reference counterpart): the backward of ngp_grid_encode_backward's two outputs with respect to the
+ * upstream gradient `u` of grad_inputs (what torch.autograd.grad(..., create_graph=True) on a loss of d enc / d x needs;
+ * DESIGN.md "Second order through the grid encoder").  With a_k = sum_d u[b,d] dw_k/dx_d per level, point and corner:
+ *   grad_embeddings[i_k,c] += a_k * grad[l,b,c]                      accumulated, pre-zeroed by the caller
+ *   grad_grad[l,b,c]        = sum_k a_k * embeddings[i_k,c]           [L,B,C] table dtype, written (NULL: not computed)
+ *   grad_inputs2[b,e]       = sum_{l,c} grad[l,b,c] sum_k da_k/dx_e embeddings[i_k,c]   [B,D] table dtype, written (NULL: not computed)
+ * grad [L,B,C], grad_grad_inputs (u) [B,D] and the outputs in the table dtype; inputs fp32 in [0,1] (points outside contribute
+ * nothing; kinks at cell faces are ignored as in the first backward).  grad_grad and grad_inputs2 are deterministic in every dtype.
+ * grad_embeddings: F32 global float atomics; F16 packed fp16 atomics, even C only (odd C: NGP_ERR_INVALID -- autocast only makes
+ * fp16 tables for even C); F64 bit-reproducible (record sort, no float atomics), needs a 256-byte aligned workspace of
+ * ngp_grid_backward_backward_workspace_bytes(...) bytes and B * 2^D <= 2^31.  NULL grad / inputs / embeddings / offsets /
+ * grad_grad_inputs / grad_embeddings: NGP_ERR_INVALID (B == 0 is a no-op).  The v-terms (the backward with respect to the
+ * upstream gradient of grad_embeddings) are ngp_grid_encode_forward and the first backward's input term on that table. */
+int ngp_grid_encode_backward_backward(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                      const void* grad_grad_inputs, void* grad_grad, void* grad_embeddings, void* grad_inputs2,
+                                      uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                                      int align_corners, uint32_t interp, int dtype, void* workspace, size_t workspace_bytes,
+                                      ngp_stream_t stream);
+/* scratch of ngp_grid_encode_backward_backward: 0 for F32 / F16; for F64 a function of B and D alone (offsets_host may be NULL) */
+size_t ngp_grid_backward_backward_workspace_bytes(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype);
+
 /* ---------------------------------------------------------------------------------------------
  * shencoder        (reference: shencoder/src/shencoder.h:9-10, bindings.cpp:5-8)
  * --------------------------------------------------------------------------------------------- */

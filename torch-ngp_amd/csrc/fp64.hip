@@ -628,9 +628,12 @@ size_t f64_grid_backward_workspace_bytes(uint32_t B, uint32_t D) {
     return 4 * f64_array_bytes((uint64_t)B << D) + RADIX_COUNT_WORDS * sizeof(uint32_t);
 }
 
-template <int D, int C>
-static int launch_f64_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_emb, uint32_t B, uint32_t L,
-                               const GridLevels& lv, uint32_t gridtype, bool ac, uint32_t interp, void* workspace, hipStream_t st) {
+// the records of one level sorted by entry (k_f64_grid_records, then four stable radix passes) -> keys[0] / vals[0] of the workspace: the
+// first-order backward below and the second-order one (grid_second.hip: f64_grid_sort_level) sum the same runs in the same order
+template <int D>
+static void f64_sort_level(const float* inputs, const int32_t* offsets, uint32_t B, uint32_t level, float scale, uint32_t resolution,
+                           uint32_t gridtype, bool ac, uint32_t interp, void* workspace, const uint32_t** keys_out, const uint32_t** vals_out,
+                           hipStream_t st) {
     const uint32_t n = B << D;
     char* ws = (char*)workspace;
     const size_t a = f64_array_bytes(n);
@@ -641,18 +644,39 @@ static int launch_f64_backward(const void* grad, const float* inputs, const int3
     const uint32_t tiles = cdiv(n, RADIX_TILE);
     const uint32_t tiles_per_group = cdiv(tiles, RADIX_MAX_GROUPS);
     const uint32_t groups = cdiv(tiles, tiles_per_group);
+    hipLaunchKernelGGL((k_f64_grid_records<D>), dim3(f64_blocks(B)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, scale, resolution,
+                       gridtype, ac, interp, keys[0], vals[0]);
+    for (uint32_t pass = 0; pass < 4; pass++) {
+        const uint32_t src = pass & 1u, shift = 8u * pass;
+        hipLaunchKernelGGL(k_f64_radix_hist, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], n, shift, tiles_per_group, groups, hist);
+        hipLaunchKernelGGL(k_f64_radix_scan, dim3(256), dim3(RADIX_MAX_GROUPS), 0, st, hist, groups, totals);
+        hipLaunchKernelGGL(k_f64_radix_scatter, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], vals[src], n, shift, tiles_per_group, groups, hist,
+                           totals, keys[src ^ 1u], vals[src ^ 1u]);
+    }
+    // (an even number of passes: the sorted records are back in keys[0] / vals[0])
+    *keys_out = keys[0];
+    *vals_out = vals[0];
+}
+
+void f64_grid_sort_level(uint32_t D, const float* inputs, const int32_t* offsets, uint32_t B, uint32_t level, float scale, uint32_t resolution,
+                         uint32_t gridtype, bool align_corners, uint32_t interp, void* workspace, const uint32_t** keys, const uint32_t** vals,
+                         hipStream_t st) {
+    switch (D) {
+        case 2: f64_sort_level<2>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
+        case 3: f64_sort_level<3>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
+        case 4: f64_sort_level<4>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
+        default: f64_sort_level<5>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
+    }
+}
+
+template <int D, int C>
+static int launch_f64_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_emb, uint32_t B, uint32_t L,
+                               const GridLevels& lv, uint32_t gridtype, bool ac, uint32_t interp, void* workspace, hipStream_t st) {
+    const uint32_t n = B << D;
     for (uint32_t level = 0; level < L; level++) {
-        hipLaunchKernelGGL((k_f64_grid_records<D>), dim3(f64_blocks(B)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, lv.scale[level],
-                           lv.res[level], gridtype, ac, interp, keys[0], vals[0]);
-        for (uint32_t pass = 0; pass < 4; pass++) {
-            const uint32_t src = pass & 1u, shift = 8u * pass;
-            hipLaunchKernelGGL(k_f64_radix_hist, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], n, shift, tiles_per_group, groups, hist);
-            hipLaunchKernelGGL(k_f64_radix_scan, dim3(256), dim3(RADIX_MAX_GROUPS), 0, st, hist, groups, totals);
-            hipLaunchKernelGGL(k_f64_radix_scatter, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], vals[src], n, shift, tiles_per_group, groups, hist,
-                               totals, keys[src ^ 1u], vals[src ^ 1u]);
-        }
-        // (an even number of passes: the sorted records are back in keys[0] / vals[0])
-        hipLaunchKernelGGL((k_f64_grid_sum<D, C>), dim3(f64_blocks(n)), dim3(F64_THREADS), 0, st, keys[0], vals[0], n, (const double*)grad, inputs,
+        const uint32_t *keys, *vals;
+        f64_sort_level<D>(inputs, offsets, B, level, lv.scale[level], lv.res[level], gridtype, ac, interp, workspace, &keys, &vals, st);
+        hipLaunchKernelGGL((k_f64_grid_sum<D, C>), dim3(f64_blocks(n)), dim3(F64_THREADS), 0, st, keys, vals, n, (const double*)grad, inputs,
                            offsets, (double*)grad_emb, B, level, lv.scale[level], ac, interp);
         const int rc = check_launch("grid_encode_backward(fp64)");
         if (rc) return rc;

@@ -113,4 +113,36 @@ __device__ __forceinline__ bool locate(const float* __restrict__ x, float scale,
     return true;
 }
 
+// locate() for the second-order backward (grid_second.hip): the same position, cell, phi and phi', plus phi'' of the raw fraction
+// (0 for linear interpolation, 6 - 12 f for smoothstep).  Unit inputs only (no InputMap).
+template <int D>
+__device__ __forceinline__ bool locate_d2(const float* __restrict__ x, float scale, bool align_corners, uint32_t interp, float (&frac)[D],
+                                          float (&deriv)[D], float (&deriv2)[D], uint32_t (&cell)[D]) {
+    float xv[D];
+    bool inside = true;
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        xv[d] = x[d];
+        inside = inside && !(xv[d] < 0.0f || xv[d] > 1.0f);
+    }
+    if (!inside) return false;
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        float p = __builtin_fmaf(xv[d], scale, align_corners ? 0.0f : 0.5f);
+        float fl = floorf(p);
+        cell[d] = (uint32_t)fl;
+        p -= (float)cell[d];
+        if (interp == 1u) {
+            deriv[d] = 6.0f * p * (1.0f - p);
+            deriv2[d] = 6.0f - 12.0f * p;
+            p = p * p * (3.0f - 2.0f * p);
+        } else {
+            deriv[d] = 1.0f;
+            deriv2[d] = 0.0f;
+        }
+        frac[d] = p;
+    }
+    return true;
+}
+
 }  // namespace ngp

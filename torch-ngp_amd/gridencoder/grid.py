@@ -17,6 +17,8 @@ import torch.nn as nn
 from torch.autograd import Function
 from torch.amp import custom_bwd, custom_fwd
 
+import _ngp_capi as _capi
+
 try:  # the compiled binding first, as the reference does (gridencoder/grid.py:9-12); the ctypes binding of the same C ABI otherwise
     import os as _os
     if _os.environ.get('NGP_HIP_LIBRARY'):  # a variant library is selected: the compiled module links the in-tree one, the ctypes binding follows the variable
@@ -46,6 +48,7 @@ class _grid_encode(Function):
     def forward(ctx, inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs=False, gridtype=0,
                 align_corners=False, interpolation=0):
         # inputs [B, D] fp32 in [0, 1]; embeddings [n_entries, C]; offsets [L+1] int32 -> [B, L*C]
+        inputs_src, table_src = inputs, embeddings
         inputs = inputs.contiguous()
         n_points, dim = inputs.shape
         n_levels = offsets.shape[0] - 1
@@ -64,6 +67,10 @@ class _grid_encode(Function):
                                      base_resolution, dy_dx, gridtype, align_corners, interpolation)
 
         ctx.save_for_backward(inputs, embeddings, offsets, dy_dx)
+        # a copy made here (the half table of autocast, a contiguous copy of the inputs) is not part of the graph: a differentiable first
+        # backward (create_graph=True) routes its gradients to the tensors the caller passed.  Plain references, not saved tensors: the
+        # first-order backward neither reads them nor checks their version
+        ctx.sources = (None if inputs_src is inputs else inputs_src, None if table_src is embeddings else table_src)
         ctx.geometry = (n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners)
         return level_major.permute(1, 0, 2).reshape(n_points, n_levels * feat)
 
@@ -72,6 +79,10 @@ class _grid_encode(Function):
     def backward(ctx, grad):
         inputs, embeddings, offsets, dy_dx = ctx.saved_tensors
         n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = ctx.geometry
+        if torch.is_grad_enabled():
+            # create_graph=True (eikonal / SDF losses on d enc / d x): the same backend calls as a differentiable op
+            grad_inputs, grad_embeddings = _grid_encode_backward.apply(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry, *ctx.sources)
+            return grad_inputs, grad_embeddings, None, None, None, None, None, None, None
 
         grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
         grad_embeddings = torch.zeros_like(embeddings)
@@ -83,6 +94,126 @@ class _grid_encode(Function):
         if grad_inputs is not None:
             grad_inputs = grad_inputs.to(inputs.dtype)
         return grad_inputs, grad_embeddings, None, None, None, None, None, None, None
+
+
+class _grid_encode_backward(Function):
+    """The first backward of the grid encoder as an op of its own, so that its outputs (grad_inputs, grad_embeddings) can be differentiated:
+    forward issues exactly the calls of _grid_encode.backward (the same bits), backward is the second order (_grid_encode_second, DESIGN.md
+    3.6)."""
+
+    @staticmethod
+    def forward(ctx, grad, inputs, embeddings, offsets, dy_dx, geometry, inputs_src=None, table_src=None):
+        # inputs_src / table_src: the tensors the encoder was called with when `inputs` / `embeddings` are copies of them (the half table of
+        # autocast): the second-order gradients go there
+        n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
+
+        grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
+        grad_embeddings = torch.zeros_like(embeddings)
+        grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
+
+        _backend.grid_encode_backward(grad_level_major, inputs, embeddings, offsets, grad_embeddings, n_points, dim, feat,
+                                      n_levels, log2_scale, base_resolution, dy_dx, grad_inputs, gridtype, align_corners,
+                                      interpolation)
+        if grad_inputs is not None:
+            grad_inputs = grad_inputs.to(inputs.dtype)
+        ctx.save_for_backward(grad, inputs, embeddings, offsets)
+        ctx.geometry = geometry
+        ctx.sources = (inputs_src, table_src)
+        # an output nobody differentiates (grad_embeddings in an eikonal loss, grad_inputs in a gradgradcheck over the table) reaches
+        # backward as None, and its terms are skipped
+        ctx.set_materialize_grads(False)
+        return grad_inputs, grad_embeddings
+
+    @staticmethod
+    def backward(ctx, grad_grad_inputs, grad_grad_embeddings):
+        grad, inputs, embeddings, offsets = ctx.saved_tensors
+        inputs_src, table_src = ctx.sources
+        need = ctx.needs_input_grad
+        needs = (need[0], need[1] or need[6], need[2] or need[7])
+        d_grad, d_inputs, d_embeddings = _grid_encode_second.apply(
+            grad_grad_inputs, grad_grad_embeddings, grad, inputs if inputs_src is None else inputs_src,
+            embeddings if table_src is None else table_src, inputs, embeddings, offsets, ctx.geometry, needs)
+        inputs_copied, table_copied = inputs_src is not None, table_src is not None
+        return (d_grad, None if inputs_copied else d_inputs, None if table_copied else d_embeddings, None, None, None,
+                d_inputs if inputs_copied else None, d_embeddings if table_copied else None)
+
+
+class _grid_encode_second(Function):
+    """Second order of the grid encoder.  With u = d loss / d grad_inputs and v = d loss / d grad_embeddings (either may be None):
+      u-terms: ngp_grid_encode_backward_backward (one HIP pass: d/d table, d/d grad, d/d inputs);
+      v-terms: the encoder forward on the table v (d/d grad) and the first backward's input term on the table v (d/d inputs).
+    Its inputs include the upstream gradient, the points and the table the caller differentiates (inputs_anchor / table_anchor), so that
+    differentiating its results once more reaches backward, which refuses third order."""
+
+    @staticmethod
+    def forward(ctx, grad_grad_inputs, grad_grad_embeddings, grad, inputs_anchor, table_anchor, inputs, embeddings, offsets, geometry, needs):
+        n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
+        need_grad, need_inputs, need_embeddings = needs
+        dtype = embeddings.dtype
+        d_grad = d_inputs = d_embeddings = None
+        grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
+
+        if grad_grad_inputs is not None and (need_grad or need_inputs or need_embeddings):
+            # u-terms: one pass of the new kernels
+            u = grad_grad_inputs.to(dtype).contiguous()
+            d_embeddings = torch.zeros_like(embeddings)
+            d_grad = torch.empty(n_levels, n_points, feat, device=inputs.device, dtype=dtype) if need_grad else None
+            d_inputs = torch.empty(n_points, dim, device=inputs.device, dtype=dtype) if need_inputs else None
+            grid_encode_backward_backward(grad_level_major, inputs, embeddings, offsets, u, d_grad, d_embeddings, d_inputs, n_points, dim,
+                                          feat, n_levels, log2_scale, base_resolution, gridtype, align_corners, interpolation)
+            if not need_embeddings:
+                d_embeddings = None
+
+        if grad_grad_embeddings is not None and (need_grad or need_inputs):
+            # v-terms: the encoder on the table v (and its dy_dx), then the first backward's input term on that table
+            v = grad_grad_embeddings.to(dtype).contiguous()
+            enc_v = torch.empty(n_levels, n_points, feat, device=inputs.device, dtype=dtype)
+            dy_dx_v = torch.empty(n_points, n_levels * dim * feat, device=inputs.device, dtype=dtype) if need_inputs else None
+            _backend.grid_encode_forward(inputs, v, offsets, enc_v, n_points, dim, feat, n_levels, log2_scale, base_resolution, dy_dx_v,
+                                         gridtype, align_corners, interpolation)
+            if need_grad:
+                d_grad = enc_v if d_grad is None else d_grad + enc_v
+            if need_inputs:
+                gx_v = torch.zeros(n_points, dim, device=inputs.device, dtype=dtype)
+                unused = torch.zeros_like(v)   # (the entry also scatters w * grad into a table: not needed here)
+                _backend.grid_encode_backward(grad_level_major, inputs, v, offsets, unused, n_points, dim, feat, n_levels, log2_scale,
+                                              base_resolution, dy_dx_v, gx_v, gridtype, align_corners, interpolation)
+                d_inputs = gx_v if d_inputs is None else d_inputs + gx_v
+
+        if d_grad is not None:
+            d_grad = d_grad.permute(1, 0, 2).reshape(n_points, n_levels * feat).to(grad.dtype)
+        if d_inputs is not None:
+            d_inputs = d_inputs.to(inputs.dtype)
+        return d_grad, d_inputs, d_embeddings
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError("grid_encode: third-order gradients are not provided (the grid encoder's second-order backward is not "
+                           "differentiable)")
+
+
+def grid_encode_backward_backward(grad, inputs, embeddings, offsets, u, grad_grad, grad_embeddings, grad_inputs2, B, D, C, L, S, H, gridtype,
+                                  align_corners, interp):
+    """ngp_grid_encode_backward_backward (include/ngp_hip.h) on tensors: grad [L,B,C], u [B,D] in the table dtype; grad_grad [L,B,C] and
+    grad_inputs2 [B,D] written (None: not computed), grad_embeddings accumulated"""
+    for t, name in ((grad, 'grad'), (inputs, 'inputs'), (embeddings, 'embeddings'), (offsets, 'offsets'), (u, 'grad_grad_inputs'),
+                    (grad_embeddings, 'grad_embeddings'), (grad_grad, 'grad_grad'), (grad_inputs2, 'grad_inputs2')):
+        if t is not None:
+            _capi.dense(t, name)
+    _capi.require_int32(offsets, 'offsets')
+    if inputs.dtype != torch.float32:
+        raise RuntimeError("expected scalar type Float for inputs but found " + str(inputs.dtype))
+    for t, name in ((grad, 'grad'), (u, 'grad_grad_inputs'), (grad_embeddings, 'grad_embeddings'), (grad_grad, 'grad_grad'),
+                    (grad_inputs2, 'grad_inputs2')):
+        if t is not None and t.dtype != embeddings.dtype:
+            raise RuntimeError(f"{name} must have the table's dtype {embeddings.dtype} (got {t.dtype})")
+    code = _capi.float_code(embeddings, 'embeddings')
+    nbytes = int(_capi.lib.ngp_grid_backward_backward_workspace_bytes(None, B, D, C, L, code))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=inputs.device) if nbytes else None
+    _capi.check(_capi.lib.ngp_grid_encode_backward_backward(
+        _capi.ptr(grad), _capi.ptr(inputs), _capi.ptr(embeddings), _capi.ptr(offsets), _capi.ptr(u), _capi.ptr(grad_grad),
+        _capi.ptr(grad_embeddings), _capi.ptr(grad_inputs2), B, D, C, L, float(S), H, gridtype, int(bool(align_corners)), interp, code,
+        _capi.ptr(ws), nbytes, _capi.stream()))
 
 
 grid_encode = _grid_encode.apply
