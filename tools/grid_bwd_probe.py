@@ -60,11 +60,3 @@ gc = g.clone(); gc[10:] = 0
 print(f'levels 0-9 only      : {run(gc):7.1f} us')
 gf = g.clone(); gf[:10] = 0
 print(f'levels 10-15 only    : {run(gf):7.1f} us')
-if hasattr(capi.lib, 'ngp_debug_bin_probe') or os.environ.get('NGP_BIN_PROBE'):
-    buf = (ctypes.c_uint64 * 16)()
-    capi.lib.ngp_debug_bin_probe(buf, 1)
-    run(g, reps=5)
-    capi.lib.ngp_debug_bin_probe(buf, 0)
-    n = max(1, buf[15])
-    names = ['loop head', 'fetch+params', 'slots', 'wait B2', 'scan+desc', 'zero+staging', 'wait B3', 'copy-out', 'cur=nxt wait']
-    print('sort item phases (cycles per item, wave 0):', ', '.join(f'{names[i]} {buf[i] / n:.0f}' for i in range(9)), f'| items {n}')

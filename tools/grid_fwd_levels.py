@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""grid_encode_forward per level: the lego-shaped marched batch (ray-ordered samples) through ngp_grid_encode_forward_sched, all 16 levels
-(balanced by the cost model / whole levels per XCD) and, with a library built with -DNGP_FWD_LEVEL_MASK_PROBE (tools/build_variant.sh),
-ONE level at a time (one level = one XCD = 32 CUs) -- the figures the per-level cost model of _ngp_capi.ray_level_costs is fitted to.
+"""grid_encode_forward on the lego-shaped marched batch (ray-ordered samples) through ngp_grid_encode_forward_sched, all 16 levels: balanced
+by the cost model of _ngp_capi.ray_level_costs against whole levels per XCD, and uniform points for comparison.  (The one-level-at-a-time
+figures the cost model was fitted to came from a probe build that is gone: EXPERIMENTS.md names the commit that still has it.)
 NGP_HIP_LIBRARY selects the library; prints HIP-event medians and a CRC of the output (identical across scheduling variants and kernels)."""
 import os, sys, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,12 +45,6 @@ def run(x, costs, reps=8):
 
 print('library', capi.LIB_PATH, 'samples', m)
 costs = capi.ray_level_costs(16, S, 16, 3.0 ** 0.5 / 1024)
-os.environ.pop('NGP_FWD_LEVEL_MASK', None)
 t = run(xr, costs); print(f'rays, all levels, balanced       {t:7.1f} us   crc {zlib.crc32(out.cpu().numpy().tobytes())}')
 t = run(xr, None); print(f'rays, all levels, whole levels   {t:7.1f} us   crc {zlib.crc32(out.cpu().numpy().tobytes())}')
 t = run(xu, None); print(f'uniform points, whole levels     {t:7.1f} us')
-if '--levels' in sys.argv:
-    for lv in (0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 15):
-        os.environ['NGP_FWD_LEVEL_MASK'] = hex(1 << lv)
-        print(f'level {lv:2d} alone  {run(xr, None, reps=6):7.1f} us')
-    os.environ.pop('NGP_FWD_LEVEL_MASK', None)

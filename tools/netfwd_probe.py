@@ -38,7 +38,7 @@ def run(M, training, reps):
         call()
     e1.record()
     torch.cuda.synchronize()
-    assert os.environ.get('NGP_PROBE_NOCHECK') or (torch.isfinite(sigma).all() and torch.isfinite(rgb).all())
+    assert torch.isfinite(sigma).all() and torch.isfinite(rgb).all()
     return e0.elapsed_time(e1) / reps * 1e3
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """grid_encode_backward on the lego-shaped marched batch with and without the table's Adam sweep in the accumulate's flush
 (ngp_table_adam_t): HIP-event time per call, next to k_adam over the stored gradient.  NGP_HIP_LIBRARY selects a compile-time variant
-(tools/build_variant.sh ... -DNGP_TADAM_PROBE=<bits>)."""
+(tools/build_variant.sh)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'torch-ngp_amd')); sys.path.insert(0, ROOT)

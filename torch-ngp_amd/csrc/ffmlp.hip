@@ -207,12 +207,10 @@ __device__ void build_forward_image_coalesced(half8_t* img, const half_t* __rest
 template <int WIDTH>
 __device__ void build_forward_image(half8_t* img, const half_t* __restrict__ w, uint32_t in_dim, uint32_t num_layers, uint32_t first_frag = 0,
                                     uint32_t n_frags = 0xFFFFFFFFu) {
-#ifndef NGP_FF_IMAGE_GATHER
     if (first_frag == 0u && n_frags == 0xFFFFFFFFu && (in_dim & 15u) == 0u) {
         build_forward_image_coalesced<WIDTH>(img, w, in_dim, num_layers);
         return;
     }
-#endif
     const uint32_t all = fwd_frag_count<WIDTH>(in_dim, num_layers);
     const uint32_t total = (n_frags == 0xFFFFFFFFu ? all : n_frags) * 64;
     const uint32_t shift = first_frag * 64;
@@ -306,11 +304,6 @@ template <int WIDTH, bool TRAIN, bool PLAIN /* ReLU hidden layers, no output act
 __device__ __forceinline__ void ffmlp_forward_body(const half_t* __restrict__ inputs, const half_t* __restrict__ weights,
                                                    half_t* __restrict__ forward_buffer, half_t* __restrict__ outputs, uint32_t n_tiles,
                                                    uint32_t in_dim, uint32_t num_layers, uint32_t act, uint32_t out_act, bool in_planar) {
-#ifdef NGP_FF_DIAG  // timing experiments of tools/bench_kernels.py (compile-time only) -- bit 0: no activation/output stores, bit 1: no input loads
-    const uint32_t diag = NGP_FF_DIAG;
-#else
-    constexpr uint32_t diag = 0u;
-#endif
     constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half8_t* img = reinterpret_cast<half8_t*>(smem);
@@ -332,7 +325,7 @@ __device__ __forceinline__ void ffmlp_forward_body(const half_t* __restrict__ in
 #pragma unroll
         for (int ib = 0; ib < NIB; ib++) acc[ib] = zero16();
         for (uint32_t kb = 0; kb < in_kb; kb++) {
-            const half8_t x = (diag & 2u) ? img_l0[kb * 64] : load_features8(inputs, in_planar, rows, srow, in_dim, 16 * kb + 8 * h);
+            const half8_t x = load_features8(inputs, in_planar, rows, srow, in_dim, 16 * kb + 8 * h);
 #pragma unroll
             for (int ib = 0; ib < NIB; ib++) acc[ib] = mfma(img_l0[(ib * in_kb + kb) * 64], x, acc[ib]);
         }
@@ -350,7 +343,7 @@ __device__ __forceinline__ void ffmlp_forward_body(const half_t* __restrict__ in
                 }
                 pack_hidden<WIDTH>(acc, hid);
             }
-            if (TRAIN && !(diag & 1u)) {
+            if (TRAIN) {
                 half8_t* dst = reinterpret_cast<half8_t*>(forward_buffer) + l * layer_stride + (size_t)tile * NKB * 64 + lane;
 #pragma unroll
                 for (int kb = 0; kb < NKB; kb++) stream_store(dst + kb * 64, hid[kb]);
@@ -375,10 +368,8 @@ __device__ __forceinline__ void ffmlp_forward_body(const half_t* __restrict__ in
             hi[c] = (half_t)(PLAIN ? o[4 + c] : act_forward(out_act, o[4 + c]));  // out features 8 + 4h + c
         }
         half_t* orow = outputs + ((size_t)tile * FF_TILE + n) * 16 + 4 * h;
-        if (!(diag & 1u) || tile == 0) {
-            *reinterpret_cast<half4_t*>(orow) = lo;
-            *reinterpret_cast<half4_t*>(orow + 8) = hi;
-        }
+        *reinterpret_cast<half4_t*>(orow) = lo;
+        *reinterpret_cast<half4_t*>(orow + 8) = hi;
     }
 }
 
@@ -410,29 +401,6 @@ __global__ __launch_bounds__(FF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 // Same MFMA sequence and the same fp16 rounding points as the separate kernels: bit-identical sigma / rgb / stored activations.
 // TRAIN additionally stores what the backward kernels read: both forward buffers (fragment order), h16 and the colour input (row-major).
 // ------------------------------------------------------------------------------------------------
-#ifdef NGP_NETFWD_DIAG  // timing experiments of tools/netfwd_probe.py (compile-time only, results are garbage): bit 0: no MFMA (one dependent vector
-                        // instruction instead), bit 1: no ReLU / pack, bit 2: no SH polynomials, bit 3: no exp / sigmoid epilogue
-__device__ __forceinline__ float16_t net_mfma(half8_t a, half8_t b, float16_t c) {
-    if (NGP_NETFWD_DIAG & 1) { c[0] += (float)a[0] * (float)b[0]; return c; }
-    return mfma(a, b, c);
-}
-template <int WIDTH>
-__device__ __forceinline__ void net_pack(const float16_t (&acc)[Shape<WIDTH>::NIB], half8_t (&frag)[Shape<WIDTH>::NKB]) {
-    if (NGP_NETFWD_DIAG & 2) {
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int kb = 0; kb < Shape<WIDTH>::NKB; kb++) {
-            f32x4 w = {acc[kb >> 1][(kb & 1) * 8], acc[kb >> 1][(kb & 1) * 8 + 2], acc[kb >> 1][(kb & 1) * 8 + 4], acc[kb >> 1][(kb & 1) * 8 + 6]};
-            frag[kb] = __builtin_bit_cast(half8_t, w);
-        }
-        return;
-    }
-    pack_hidden_relu<WIDTH>(acc, frag);
-}
-#else
-#define net_mfma mfma
-#define net_pack pack_hidden_relu
-#endif
 // hidden layers + output layer of a 64-wide ReLU network for the NT tiles a wave works on together: first-layer accumulators in, output
 // accumulators out; the hidden post-activations are streamed to `fb` (fragment order) when TRAIN.  Every weight fragment is read from
 // the LDS image ONCE and multiplied into all NT tiles: NT independent accumulator chains per wave (the vector work of one tile issues
@@ -446,7 +414,7 @@ __device__ __forceinline__ void relu_network_tail(float16_t (&acc)[NT][2], float
     for (uint32_t l = 0;; l++) {
 #pragma unroll
         for (int t = 0; t < NT; t++) {
-            net_pack<WIDTH>(acc[t], hid[t]);
+            pack_hidden_relu<WIDTH>(acc[t], hid[t]);
             if (TRAIN && fb && live[t]) {  // (fb == NULL: the backward recomputes the activations, NGP_FF_RECOMPUTE)
                 half8_t* dst = reinterpret_cast<half8_t*>(fb) + l * layer_stride + (size_t)tile[t] * NKB * 64 + lane;
 #pragma unroll
@@ -463,7 +431,7 @@ __device__ __forceinline__ void relu_network_tail(float16_t (&acc)[NT][2], float
             for (int kb = 0; kb < NKB; kb++) {
                 const half8_t a = wl[(ib * NKB + kb) * 64];
 #pragma unroll
-                for (int t = 0; t < NT; t++) acc[t][ib] = net_mfma(a, hid[t][kb], acc[t][ib]);
+                for (int t = 0; t < NT; t++) acc[t][ib] = mfma(a, hid[t][kb], acc[t][ib]);
             }
         }
     }
@@ -473,7 +441,7 @@ __device__ __forceinline__ void relu_network_tail(float16_t (&acc)[NT][2], float
     for (int kb = 0; kb < NKB; kb++) {
         const half8_t a = out_img[kb * 64];
 #pragma unroll
-        for (int t = 0; t < NT; t++) o[t] = net_mfma(a, hid[t][kb], o[t]);
+        for (int t = 0; t < NT; t++) o[t] = mfma(a, hid[t][kb], o[t]);
     }
 }
 
@@ -556,7 +524,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
             for (int ib = 0; ib < NIB; ib++) {
                 const half8_t a = s_l0[(ib * in_kb + kb) * 64];
 #pragma unroll
-                for (int t = 0; t < NT; t++) acc[t][ib] = net_mfma(a, x_cur[t][kb], acc[t][ib]);
+                for (int t = 0; t < NT; t++) acc[t][ib] = mfma(a, x_cur[t][kb], acc[t][ib]);
             }
         relu_network_tail<TRAIN, NT>(acc, o, s_hid, s_out, nl_s, fb_s, layer_stride, tile, live, lane);
         half8_t cin[NT][2];
@@ -571,11 +539,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
                 *reinterpret_cast<half4_t*>(hrow) = lo;
                 *reinterpret_cast<half4_t*>(hrow + 8) = hi;
             }
-#if defined(NGP_NETFWD_DIAG) && (NGP_NETFWD_DIAG & 8)
-            if (h == 0 && live[t]) sigma[srow[t]] = density_scale * (float)lo[0];
-#else
-            if (h == 0 && live[t]) sigma[srow[t]] = density_scale * expf((float)lo[0]);
-#endif  // trunc_exp forward on the fp16 output (activation.py:9-10)
+            if (h == 0 && live[t]) sigma[srow[t]] = density_scale * expf((float)lo[0]);  // trunc_exp forward on the fp16 output (activation.py:9-10)
             // ---- colour-net input: k block 0 = half(SH_4(dir))[8h .. 8h+7], k block 1 = h16[1 + 8h + j] (j < 8; feature 16 -> the zero pad) ----
             const float x = dir_x[t], y = dir_y[t], z = dir_z[t];
             // component i goes to half-wave i >> 3, slot i & 7: all 16 polynomials as fp32 values (pinned: the conversion must round the
@@ -583,14 +547,10 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
             // the first version -- compiled to sixteen divergent branches per tile, both sides taken by every wave.)
             float sh_0, sh_1, sh_2, sh_3, sh_4, sh_5, sh_6, sh_7, sh_8, sh_9, sh_10, sh_11, sh_12, sh_13, sh_14, sh_15;
 #define SH_OUT(i, v) { sh_##i = (v); asm volatile("" : "+v"(sh_##i)); }
-#if defined(NGP_NETFWD_DIAG) && (NGP_NETFWD_DIAG & 4)
-            sh_0 = sh_1 = sh_2 = sh_3 = sh_4 = sh_5 = sh_6 = sh_7 = x; sh_8 = sh_9 = sh_10 = sh_11 = sh_12 = sh_13 = sh_14 = sh_15 = y + z;
-#else
             SH_BAND_0_VALUES;
             SH_BAND_1_VALUES;
             SH_BAND_2_VALUES;
             SH_BAND_3_VALUES;
-#endif
 #undef SH_OUT
             typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define SH_PAIR(q, a0, a1, b0, b1) { const half2_t pr = __builtin_convertvector(f32x2{h ? b0 : a0, h ? b1 : a1}, half2_t); cin[t][0][2 * (q)] = pr.x; cin[t][0][2 * (q) + 1] = pr.y; }
@@ -634,7 +594,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
             for (int ib = 0; ib < NIB; ib++) {
                 const half8_t a = c_l0[(ib * in_kb + kb) * 64];
 #pragma unroll
-                for (int t = 0; t < NT; t++) acc[t][ib] = net_mfma(a, cin[t][kb], acc[t][ib]);
+                for (int t = 0; t < NT; t++) acc[t][ib] = mfma(a, cin[t][kb], acc[t][ib]);
             }
         relu_network_tail<TRAIN, NT>(acc, o, c_hid, c_out, nl_c, fb_c, layer_stride, tile, live, lane);
 #pragma unroll
@@ -644,11 +604,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     const float v = (float)(half_t)o[t][c];
-#if defined(NGP_NETFWD_DIAG) && (NGP_NETFWD_DIAG & 8)
-                    prgb[c] = v;
-#else
                     prgb[c] = (float)to_half_rne(1.0f / (1.0f + expf(-v)));
-#endif
                 }
             }
         }
@@ -913,11 +869,6 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
                                                                uint32_t n_tiles, uint32_t in_dim, uint32_t num_layers, uint32_t act,
                                                                bool with_dx, half_t* __restrict__ grad_inputs, float* __restrict__ slabs,
                                                                half_t* __restrict__ grad_weights_direct, bool in_planar, bool dx_planar, uint32_t pf_depth) {
-#ifdef NGP_FF_BWD_DIAG  // timing experiments (compile-time only): 1 = no loads after the first tile, 2 = loads only
-    constexpr uint32_t diag = NGP_FF_BWD_DIAG;
-#else
-    constexpr uint32_t diag = 0u;
-#endif
     constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half8_t* img = reinterpret_cast<half8_t*>(smem);
@@ -966,13 +917,12 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
     for (uint32_t tile = blockIdx.x * FF_WAVES + wid; tile < n_tiles; tile += tile_step) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's operands have landed in buffer `cur`
         const unsigned char* tb = pf_base + (size_t)cur * tile_frags * 1024;
-        if (pf_depth > 1 && diag != 1u) {
+        if (pf_depth > 1) {
             cur ^= 1u;
             if (tile + tile_step < n_tiles)
                 prefetch_tile<WIDTH>(pf_base + (size_t)cur * tile_frags * 1024, tile + tile_step, grad, fb, inputs, num_layers, layer_stride,
                                      rows, in_dim, in_planar, lane, n, h);
         }
-        if (diag == 2u) continue;
         const half8_t* tfrag = reinterpret_cast<const half8_t*>(tb) + lane;
         // ---- output layer -------------------------------------------------------------------
         const half8_t dy = tfrag[0];

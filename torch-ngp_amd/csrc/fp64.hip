@@ -24,11 +24,6 @@ namespace ngp {
 
 constexpr int F64_THREADS = 256;
 
-static uint32_t f64_blocks(uint64_t n) {
-    const uint64_t nb = cdiv64(n, F64_THREADS);
-    return nb < 1 ? 1u : (nb > 65535u ? 65535u : (uint32_t)nb);
-}
-
 // interpolation weight of corner k (bit d set: the upper vertex in dimension d) -- the fp32 product of k_grid_forward, same order
 template <int D>
 __device__ __forceinline__ float corner_weight(const float (&frac)[D], uint32_t k) {
@@ -574,33 +569,10 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_rays(uint32_t n_a
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-#define NGP_F64_DISPATCH_DC(FN, ...)                                    \
-    switch (D * 16 + C) {                                               \
-        case 2 * 16 + 1: return FN<2, 1>(__VA_ARGS__);                  \
-        case 2 * 16 + 2: return FN<2, 2>(__VA_ARGS__);                  \
-        case 2 * 16 + 4: return FN<2, 4>(__VA_ARGS__);                  \
-        case 2 * 16 + 8: return FN<2, 8>(__VA_ARGS__);                  \
-        case 3 * 16 + 1: return FN<3, 1>(__VA_ARGS__);                  \
-        case 3 * 16 + 2: return FN<3, 2>(__VA_ARGS__);                  \
-        case 3 * 16 + 4: return FN<3, 4>(__VA_ARGS__);                  \
-        case 3 * 16 + 8: return FN<3, 8>(__VA_ARGS__);                  \
-        case 4 * 16 + 1: return FN<4, 1>(__VA_ARGS__);                  \
-        case 4 * 16 + 2: return FN<4, 2>(__VA_ARGS__);                  \
-        case 4 * 16 + 4: return FN<4, 4>(__VA_ARGS__);                  \
-        case 4 * 16 + 8: return FN<4, 8>(__VA_ARGS__);                  \
-        case 5 * 16 + 1: return FN<5, 1>(__VA_ARGS__);                  \
-        case 5 * 16 + 2: return FN<5, 2>(__VA_ARGS__);                  \
-        case 5 * 16 + 4: return FN<5, 4>(__VA_ARGS__);                  \
-        case 5 * 16 + 8: return FN<5, 8>(__VA_ARGS__);                  \
-        default: break;                                                 \
-    }
-
-static void f64_levels(GridLevels& lv, uint32_t L, float S, uint32_t H) { ngp_grid_level_table(L, S, H, lv.scale, lv.res); }
-
 template <int D, int C>
 static int launch_f64_forward(const float* inputs, const void* emb, const int32_t* offsets, void* outputs, uint32_t B, uint32_t L, const GridLevels& lv,
                               void* dy_dx, uint32_t gridtype, bool ac, uint32_t interp, hipStream_t st) {
-    const dim3 grid(f64_blocks(B), L, 1);
+    const dim3 grid(grid_blocks(B, F64_THREADS), L, 1);
     if (dy_dx)
         hipLaunchKernelGGL((k_f64_grid_fwd<D, C, true>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L, lv,
                            (double*)dy_dx, gridtype, ac, interp);
@@ -614,8 +586,8 @@ int f64_grid_forward(const float* inputs, const void* embeddings, const int32_t*
                      float S, uint32_t H, void* dy_dx, uint32_t gridtype, bool align_corners, uint32_t interp, hipStream_t st) {
     if (B == 0) return NGP_OK;
     GridLevels lv;
-    f64_levels(lv, L, S, H);
-    NGP_F64_DISPATCH_DC(launch_f64_forward, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, align_corners, interp, st)
+    fill_levels(lv, L, S, H);
+    NGP_DISPATCH_DC(D, C, launch_f64_forward<D_, C_>(inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, align_corners, interp, st))
     set_error("grid_encode_forward: unsupported (D=%u, C=%u)", D, C);
     return NGP_ERR_INVALID;
 }
@@ -644,7 +616,7 @@ static void f64_sort_level(const float* inputs, const int32_t* offsets, uint32_t
     const uint32_t tiles = cdiv(n, RADIX_TILE);
     const uint32_t tiles_per_group = cdiv(tiles, RADIX_MAX_GROUPS);
     const uint32_t groups = cdiv(tiles, tiles_per_group);
-    hipLaunchKernelGGL((k_f64_grid_records<D>), dim3(f64_blocks(B)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, scale, resolution,
+    hipLaunchKernelGGL((k_f64_grid_records<D>), dim3(grid_blocks(B, F64_THREADS)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, scale, resolution,
                        gridtype, ac, interp, keys[0], vals[0]);
     for (uint32_t pass = 0; pass < 4; pass++) {
         const uint32_t src = pass & 1u, shift = 8u * pass;
@@ -676,7 +648,7 @@ static int launch_f64_backward(const void* grad, const float* inputs, const int3
     for (uint32_t level = 0; level < L; level++) {
         const uint32_t *keys, *vals;
         f64_sort_level<D>(inputs, offsets, B, level, lv.scale[level], lv.res[level], gridtype, ac, interp, workspace, &keys, &vals, st);
-        hipLaunchKernelGGL((k_f64_grid_sum<D, C>), dim3(f64_blocks(n)), dim3(F64_THREADS), 0, st, keys, vals, n, (const double*)grad, inputs,
+        hipLaunchKernelGGL((k_f64_grid_sum<D, C>), dim3(grid_blocks(n, F64_THREADS)), dim3(F64_THREADS), 0, st, keys, vals, n, (const double*)grad, inputs,
                            offsets, (double*)grad_emb, B, level, lv.scale[level], ac, interp);
         const int rc = check_launch("grid_encode_backward(fp64)");
         if (rc) return rc;
@@ -695,25 +667,12 @@ int f64_grid_backward(const void* grad, const float* inputs, const int32_t* offs
                 workspace ? workspace_bytes : (size_t)0);
     NGP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, NGP_ERR_INVALID, "grid_encode_backward: fp64: workspace must be 256-byte aligned");
     GridLevels lv;
-    f64_levels(lv, L, S, H);
-    int rc = NGP_ERR_INVALID;
-    bool dispatched = true;
-    switch (D * 16 + C) {
-#define NGP_F64_BWD_CASE(DD, CC)                                                                                                                  \
-        case DD * 16 + CC:                                                                                                                        \
-            rc = launch_f64_backward<DD, CC>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, align_corners, interp, workspace, st); \
-            break;
-        NGP_F64_BWD_CASE(2, 1) NGP_F64_BWD_CASE(2, 2) NGP_F64_BWD_CASE(2, 4) NGP_F64_BWD_CASE(2, 8)
-        NGP_F64_BWD_CASE(3, 1) NGP_F64_BWD_CASE(3, 2) NGP_F64_BWD_CASE(3, 4) NGP_F64_BWD_CASE(3, 8)
-        NGP_F64_BWD_CASE(4, 1) NGP_F64_BWD_CASE(4, 2) NGP_F64_BWD_CASE(4, 4) NGP_F64_BWD_CASE(4, 8)
-        NGP_F64_BWD_CASE(5, 1) NGP_F64_BWD_CASE(5, 2) NGP_F64_BWD_CASE(5, 4) NGP_F64_BWD_CASE(5, 8)
-#undef NGP_F64_BWD_CASE
-        default: dispatched = false; break;
-    }
-    if (!dispatched) {
+    fill_levels(lv, L, S, H);
+    const int rc = [&]() -> int {
+        NGP_DISPATCH_DC(D, C, launch_f64_backward<D_, C_>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, align_corners, interp, workspace, st))
         set_error("grid_encode_backward: unsupported (D=%u, C=%u)", D, C);
         return NGP_ERR_INVALID;
-    }
+    }();
     if (rc || !(dy_dx && grad_inputs)) return rc;
     hipLaunchKernelGGL(k_f64_grid_input_bwd, dim3(cdiv(B * D, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, (const double*)dy_dx,
                        (double*)grad_inputs, B, L, D, C);
@@ -723,7 +682,7 @@ int f64_grid_backward(const void* grad, const float* inputs, const int32_t* offs
 template <int D, int C>
 static int launch_f64_tv(const void* inputs, const void* emb, void* grad, const int32_t* offsets, float weight, uint32_t B, uint32_t L,
                          const GridLevels& lv, uint32_t gridtype, bool ac, hipStream_t st) {
-    hipLaunchKernelGGL((k_f64_grad_tv<D, C>), dim3(f64_blocks(B), L, 1), dim3(F64_THREADS), 0, st, (const double*)inputs, (const double*)emb,
+    hipLaunchKernelGGL((k_f64_grad_tv<D, C>), dim3(grid_blocks(B, F64_THREADS), L, 1), dim3(F64_THREADS), 0, st, (const double*)inputs, (const double*)emb,
                        (double*)grad, offsets, weight, B, lv, gridtype, ac);
     return check_launch("grad_total_variation(fp64)");
 }
@@ -732,8 +691,8 @@ int f64_grad_tv(const void* inputs, const void* embeddings, void* grad, const in
                 uint32_t L, float S, uint32_t H, uint32_t gridtype, bool align_corners, hipStream_t st) {
     if (B == 0) return NGP_OK;
     GridLevels lv;
-    f64_levels(lv, L, S, H);
-    NGP_F64_DISPATCH_DC(launch_f64_tv, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, align_corners, st)
+    fill_levels(lv, L, S, H);
+    NGP_DISPATCH_DC(D, C, launch_f64_tv<D_, C_>(inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, align_corners, st))
     set_error("grad_total_variation: unsupported (D=%u, C=%u)", D, C);
     return NGP_ERR_INVALID;
 }

@@ -1,6 +1,7 @@
-// Grid-encoder indexing shared by the fp16/fp32 kernels (gridencoder.hip) and the fp64 ones (fp64.hip): the per-level table, the
-// corner-index rule and the position of a point inside a level.  One statement of each, so the fp64 path locates points and computes
-// interpolation weights exactly as the fp32 path does.
+// Grid-encoder indexing shared by the fp16/fp32 kernels (gridencoder.hip), the fp64 ones (fp64.hip) and the second-order backward
+// (grid_second.hip): the per-level table, the corner-index rule and the position of a point inside a level.  One statement of each, so
+// the fp64 path locates points and computes interpolation weights exactly as the fp32 path does.  Also the host plumbing the three units
+// share: the level table of a call, the launch-grid cap and the (D, C) dispatch.
 #pragma once
 #include "common.h"
 
@@ -10,6 +11,29 @@ struct GridLevels {
     float scale[NGP_MAX_LEVELS];
     uint32_t res[NGP_MAX_LEVELS];
 };
+
+// host: the per-level scale / resolution table of a call (ngp_grid_level_table: the reproducible recipe shared with the oracle)
+inline void fill_levels(GridLevels& lv, uint32_t L, float S, uint32_t H) { ngp_grid_level_table(L, S, H, lv.scale, lv.res); }
+
+// host: workgroups of a grid-stride launch over n items, capped so that a (blocks, level) grid stays level-major
+inline uint32_t grid_blocks(uint64_t n, uint32_t threads) {
+    const uint64_t nb = cdiv64(n, threads);
+    return nb < 1 ? 1u : (nb > 65535u ? 65535u : (uint32_t)nb);
+}
+
+// host: `return <expression>;` with the run-time pair (D, C) as the compile-time constants D_, C_ of the expression; falls through for a
+// pair outside D in [2, 5], C in {1, 2, 4, 8}
+#define NGP_DC_CASE_(DD, CC, ...) \
+    case DD * 16 + CC: {          \
+        constexpr int D_ = DD, C_ = CC; \
+        return __VA_ARGS__;       \
+    }
+#define NGP_DC_ROW_(DD, ...) NGP_DC_CASE_(DD, 1, __VA_ARGS__) NGP_DC_CASE_(DD, 2, __VA_ARGS__) NGP_DC_CASE_(DD, 4, __VA_ARGS__) NGP_DC_CASE_(DD, 8, __VA_ARGS__)
+#define NGP_DISPATCH_DC(D, C, ...)                                                                                                  \
+    switch ((D) * 16 + (C)) {                                                                                                       \
+        NGP_DC_ROW_(2, __VA_ARGS__) NGP_DC_ROW_(3, __VA_ARGS__) NGP_DC_ROW_(4, __VA_ARGS__) NGP_DC_ROW_(5, __VA_ARGS__)             \
+        default: break;                                                                                                             \
+    }
 
 __constant__ const uint32_t kPrimes[7] = {1u, 2654435761u, 805459861u, 3674653429u,
                                           2097192037u, 1434869437u, 2165219737u};

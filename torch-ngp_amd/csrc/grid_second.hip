@@ -289,11 +289,6 @@ __global__ __launch_bounds__(GG_THREADS) void k_f64_grid_bwd_bwd_sum(const uint3
 // ------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------
-static uint32_t gg_blocks(uint64_t n) {
-    const uint64_t nb = cdiv64(n, GG_THREADS);
-    return nb < 1 ? 1u : (nb > 65535u ? 65535u : (uint32_t)nb);
-}
-
 struct GGArgs {
     const void* grad;
     const float* inputs;
@@ -329,7 +324,7 @@ static int launch_bwd_bwd(const GGArgs& a, hipStream_t st) {
                 const uint32_t *keys, *vals;
                 f64_grid_sort_level((uint32_t)D, a.inputs, a.offsets, a.B, level, a.lv.scale[level], a.lv.res[level], a.gridtype, a.align_corners,
                                     a.interp, a.workspace, &keys, &vals, st);
-                hipLaunchKernelGGL((k_f64_grid_bwd_bwd_sum<D, C>), dim3(gg_blocks(n)), dim3(GG_THREADS), 0, st, keys, vals, n, (const double*)a.grad,
+                hipLaunchKernelGGL((k_f64_grid_bwd_bwd_sum<D, C>), dim3(grid_blocks(n, GG_THREADS)), dim3(GG_THREADS), 0, st, keys, vals, n, (const double*)a.grad,
                                    a.inputs, (const double*)a.u, a.offsets, (double*)a.grad_embeddings, a.B, level, a.lv.scale[level], a.align_corners,
                                    a.interp);
                 const int rc = check_launch("grid_encode_backward_backward(fp64)");
@@ -342,16 +337,7 @@ static int launch_bwd_bwd(const GGArgs& a, hipStream_t st) {
 
 template <typename T>
 static int dispatch_bwd_bwd(uint32_t D, uint32_t C, const GGArgs& a, hipStream_t st) {
-    switch (D * 16 + C) {
-#define NGP_GG_CASE(DD, CC) \
-        case DD * 16 + CC: return launch_bwd_bwd<T, DD, CC>(a, st);
-        NGP_GG_CASE(2, 1) NGP_GG_CASE(2, 2) NGP_GG_CASE(2, 4) NGP_GG_CASE(2, 8)
-        NGP_GG_CASE(3, 1) NGP_GG_CASE(3, 2) NGP_GG_CASE(3, 4) NGP_GG_CASE(3, 8)
-        NGP_GG_CASE(4, 1) NGP_GG_CASE(4, 2) NGP_GG_CASE(4, 4) NGP_GG_CASE(4, 8)
-        NGP_GG_CASE(5, 1) NGP_GG_CASE(5, 2) NGP_GG_CASE(5, 4) NGP_GG_CASE(5, 8)
-#undef NGP_GG_CASE
-        default: break;
-    }
+    NGP_DISPATCH_DC(D, C, launch_bwd_bwd<T, D_, C_>(a, st))
     set_error("grid_encode_backward_backward: unsupported (D=%u, C=%u)", D, C);
     return NGP_ERR_INVALID;
 }
@@ -406,7 +392,7 @@ extern "C" int ngp_grid_encode_backward_backward(const void* grad, const float* 
     a.interp = interp;
     a.align_corners = align_corners != 0;
     a.workspace = workspace;
-    ngp_grid_level_table(L, S, H, a.lv.scale, a.lv.res);
+    fill_levels(a.lv, L, S, H);
     const hipStream_t st = as_stream(stream);
     if (dtype == NGP_F16) return dispatch_bwd_bwd<half_t>(D, C, a, st);
     if (dtype == NGP_F32) return dispatch_bwd_bwd<float>(D, C, a, st);

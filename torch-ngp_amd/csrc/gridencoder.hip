@@ -21,7 +21,6 @@
 #include "grid_index.h"
 #include "fp64.h"
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -336,9 +335,6 @@ struct FwdPos3 {
     }
 };
 
-#ifndef NGP_FWD_FAST
-#define NGP_FWD_FAST 1
-#endif
 // (measured and dropped, EXPERIMENTS.md round 5: non-temporal table gathers on the fine hashed levels -- no effect: 58.0 / 58.1 vs 57.5 us)
 template <bool SMOOTH /* interp == 1 (smoothstep) */, bool MAPPED /* inputs are world coordinates: InputMap */>
 __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward_fast(const float* __restrict__ inputs, const half_t* __restrict__ grid_a,
@@ -400,7 +396,7 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward_fast(const float* 
         return ok;
     };
 
-    if (NGP_FWD_FAST && dense) {
+    if (dense) {
         // ---- one lane per point, x-pairs by 8-byte loads ----
         const uint32_t s1 = indexer.stride[1], s2 = indexer.stride[2];
         constexpr uint32_t STEP = FWD_THREADS;  // points per workgroup step
@@ -440,7 +436,7 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward_fast(const float* 
         }
         return;
     }
-    if (NGP_FWD_FAST && hashed_pow2) {
+    if (hashed_pow2) {
         // ---- corner pairs on neighbouring lanes, index = (x ^ y p1 ^ z p2) & mask ----
         const uint32_t mask = indexer.mask;
         const int pl = lane >> 1;
@@ -642,9 +638,10 @@ __device__ __forceinline__ float row_shr_f(float src) {
     return __builtin_bit_cast(float, row_shr<N>(__builtin_bit_cast(uint32_t, src)));
 }
 
-// MERGE: 0 = every sample issues its own contribution; 1 = runs of equal table address over the whole wave (cross-lane reads through
-// ds_bpermute: ~15 clk of the CU's LDS pipe each, measured -- affordable only where the alternative is a fabric atomic); 2 = runs
-// inside a 16-lane row (8 samples of the fp16 C = 2 layout) with DPP row shifts: pure VALU.
+// MERGE: how runs of equal table address over the whole wave are summed.  3 = two lanes per sample (BwdLanes::LPP == 2: fp16 tables with
+// C <= 2, fp32 with C = 1): DPP only, pure VALU; 1 = every other lane layout: cross-lane reads through ds_bpermute (~15 clk of the CU's
+// LDS pipe each, measured -- affordable only where the alternative is a fabric atomic).  (Measured and dropped, EXPERIMENTS.md: no
+// merge, merge inside 16-lane rows.)
 template <typename T, int D, int C, int MERGE>
 __device__ __forceinline__ void corner_runs(const BwdSample<T, D, C>& smp, float scale, bool align_corners, uint32_t interp,
                                             const LevelIndexer<D>& indexer, InputMap im, int pl, uint32_t xb,
@@ -694,29 +691,22 @@ __device__ __forceinline__ void corner_runs(const BwdSample<T, D, C>& smp, float
     }
 #pragma unroll
     for (int j = 0; j < NJ; j++) issue[j] = live;
-    if constexpr (MERGE == 2 || MERGE == 3) {
-        // Segmented scan with DPP only (VALU; no LDS crossbar).  MERGE == 2: runs inside a 16-lane row (8 samples).  MERGE == 3: runs
-        // over the whole wave -- the links to the neighbouring sample cross rows with wave_shr/shl:1 (twice: two lanes per sample), the
-        // scan runs inside the rows, and the rows are then chained by three carry rounds (row_bcast:15 hands the last sample of a row
-        // to the next row; the class-0 lane first moves into lane 15 with row_shr:1).
-        static_assert((MERGE != 2 && MERGE != 3) || LPP == 2, "the DPP merges are written for two lanes per sample");
-        auto prev2 = [](uint32_t x) {  // value of the lane two below (0 for a sample without predecessor)
-            if constexpr (MERGE == 2) return row_shr<2>(x);
-            else return wave_shr1(wave_shr1(x));
-        };
-        auto next2 = [](uint32_t x) {
-            if constexpr (MERGE == 2) return row_shl<2>(x);
-            else return wave_shl1(wave_shl1(x));
-        };
+    static_assert(MERGE == 1 || MERGE == 3, "MERGE is 1 (ds_bpermute) or 3 (DPP)");
+    if constexpr (MERGE == 3) {
+        // Segmented scan with DPP only (VALU; no LDS crossbar) over the whole wave -- the links to the neighbouring sample cross rows
+        // with wave_shr/shl:1 (twice: two lanes per sample), the scan runs inside the rows, and the rows are then chained by three carry
+        // rounds (row_bcast:15 hands the last sample of a row to the next row; the class-0 lane first moves into lane 15 with row_shr:1).
+        static_assert(LPP == 2, "the DPP merge is written for two lanes per sample");
+        auto prev2 = [](uint32_t x) { return wave_shr1(wave_shr1(x)); };  // value of the lane two below (0 for a sample without predecessor)
+        auto next2 = [](uint32_t x) { return wave_shl1(wave_shl1(x)); };
         const uint32_t prev_live = prev2((uint32_t)live);
         const uint32_t row = (uint32_t)(threadIdx.x & 63) >> 4;
 #pragma unroll
         for (int j = 0; j < NJ; j++) {
             const uint32_t prev_addr1 = prev2(addr[j] + 1u);
             const bool same = live & (prev_live != 0u) & (prev_addr1 == addr[j] + 1u);
-            // the record sort merges only when a fair share of the wave continues a run (fine levels: almost never);
-            // in front of a fabric atomic every merged lane pays
-            if (__popcll(__ballot(same)) >= (MERGE == 2 ? 12 : 1)) {
+            // (in front of a fabric atomic every merged lane pays: one continuing lane is enough -- the record sort asks for a fair share)
+            if (__any(same)) {
                 uint32_t closed = same ? 0u : 1u;  // the scan of this lane has reached the head of its run
                 // inside the row, distances 1, 2, 4 samples; a lane without a source reads 0: adds nothing and stays open
 #define NGP_ROW_SCAN_STEP(N)                                                                                  \
@@ -731,27 +721,24 @@ __device__ __forceinline__ void corner_runs(const BwdSample<T, D, C>& smp, float
                 NGP_ROW_SCAN_STEP(4)
                 NGP_ROW_SCAN_STEP(8)
 #undef NGP_ROW_SCAN_STEP
-                if constexpr (MERGE == 3) {
 #pragma unroll
-                    for (uint32_t r = 1; r < 4; r++) {  // carry of row r-1 (its last sample, already carrying its own) into row r
-                        const uint32_t c1 = row_bcast15(closed), c0 = row_bcast15(row_shr<1>(closed));
-                        const uint32_t cc = xb ? c1 : c0;
-                        const bool take = (row == r) && !closed;
+                for (uint32_t r = 1; r < 4; r++) {  // carry of row r-1 (its last sample, already carrying its own) into row r
+                    const uint32_t c1 = row_bcast15(closed), c0 = row_bcast15(row_shr<1>(closed));
+                    const uint32_t cc = xb ? c1 : c0;
+                    const bool take = (row == r) && !closed;
 #pragma unroll
-                        for (int c = 0; c < CPL; c++) {
-                            const float t1 = __builtin_bit_cast(float, row_bcast15(__builtin_bit_cast(uint32_t, v[j][c])));
-                            const float t0 = __builtin_bit_cast(float, row_bcast15(row_shr<1>(__builtin_bit_cast(uint32_t, v[j][c]))));
-                            v[j][c] += take ? (xb ? t1 : t0) : 0.0f;
-                        }
-                        closed = take ? cc : closed;
+                    for (int c = 0; c < CPL; c++) {
+                        const float t1 = __builtin_bit_cast(float, row_bcast15(__builtin_bit_cast(uint32_t, v[j][c])));
+                        const float t0 = __builtin_bit_cast(float, row_bcast15(row_shr<1>(__builtin_bit_cast(uint32_t, v[j][c]))));
+                        v[j][c] += take ? (xb ? t1 : t0) : 0.0f;
                     }
+                    closed = take ? cc : closed;
                 }
                 const uint32_t next_same = next2((uint32_t)same);
                 issue[j] = live && !next_same;  // the last lane of a run holds the run total
             }
         }
-    }
-    if constexpr (MERGE == 1) {
+    } else {
         // (every shuffle is executed by all lanes: no short-circuit in front of a cross-lane read)
         const int prev_live = __shfl_up((int)live, LPP, 64);
 #pragma unroll
@@ -932,12 +919,6 @@ __device__ __forceinline__ uint32_t bcast31_rows23(uint32_t src) {
 //     workgroups per CU.  Second barrier, coalesced copy of the sorted chunk (16 bytes per lane).
 //   * Workgroups are persistent over a contiguous range of (chunk, level) items, level fastest: positions are loaded once per chunk,
 //     the gradient of the next item is in flight while the current one is sorted, per-level constants are scalar loads from the plan.
-#ifdef NGP_BIN_PHASE_PROBE  // timing probe only: shader-clock cycles per phase of the sort's item loop, summed over wave 0 of every workgroup
-__device__ unsigned long long g_bin_probe[16];
-#define NGP_PROBE_T(i) { const unsigned long long t_now = __builtin_amdgcn_s_memtime(); t_acc[i] += t_now - t_probe; t_probe = t_now; }
-#else
-#define NGP_PROBE_T(i)
-#endif
 #ifndef NGP_BIN_MERGE_MIN
 #define NGP_BIN_MERGE_MIN 8
 #endif
@@ -1202,7 +1183,7 @@ __device__ __forceinline__ uint32_t bin_offsets(const uint32_t* __restrict__ his
 #ifndef NGP_BIN_WAVES_PER_EU
 #define NGP_BIN_WAVES_PER_EU 6
 #endif
-template <int D, int AMERGE /* run merge of the atomic workgroups: 3 = DPP over the wave, 1 = ds_bpermute */,
+template <int D, int AMERGE /* run merge of the atomic workgroups (corner_runs): always 3, two lanes per sample */,
           int BPL /* bin counters per lane and wave: 2 (levels of <= 128 bins, 40 KiB of LDS) or 8 (<= 512 bins, 64 KiB) */>
 __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(BPL == 2 ? NGP_BIN_WAVES_PER_EU : 4, BPL == 2 ? NGP_BIN_WAVES_PER_EU : 4)))
 void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restrict__ inputs, const int32_t* __restrict__ offsets,
@@ -1270,11 +1251,7 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
     };
     if (item < item_end) g_cur = fetch_g(it.chunk_x, it.li);
     __syncthreads();
-#ifdef NGP_BIN_PHASE_PROBE
-    unsigned long long t_probe = __builtin_amdgcn_s_memtime(), t_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     for (; item < item_end; item++) {
-        NGP_PROBE_T(0)
         const uint32_t b = it.chunk_x * BIN_PPB + (uint32_t)tid;
         const bool in_range = b < B;
         if (it.chunk_x != chunk_loaded) {  // (wave-uniform) the positions: once per chunk
@@ -1310,22 +1287,16 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
             it.plan_ok = size_dev <= (it.n_bins << BIN_SLICE_BITS);
             it.gtable = grad_grid + (size_t)off0 * C;
         }
-        NGP_PROBE_T(1)
         BinLane<D> bl;
         LaneMask live_mask;
         const bool fast = indexer.hashed && indexer.mask != 0u && !it.interleaved && it.plan_ok;
         if (fast) bin_pass_count<D, true>(x, g_cur, in_range, it, indexer, align_corners, interp, im, hrow_base, bl, live_mask);
         else bin_pass_count<D, false>(x, g_cur, in_range, it, indexer, align_corners, interp, im, hrow_base, bl, live_mask);
-        NGP_PROBE_T(2)
         __syncthreads();  // all counts of this item are in
-        NGP_PROBE_T(3)
         const uint32_t total_units = bin_offsets<BPL, WAVES>(hist, prow, lane, wid, it, plan.n_chunks, descriptors, staging_base);
-        NGP_PROBE_T(4)
         if (fast) bin_pass_place<D, true>(g_cur, it, bl, live_mask, prow_base, staging_base);
         else bin_pass_place<D, false>(g_cur, it, bl, live_mask, prow_base, staging_base);
-        NGP_PROBE_T(5)
         __syncthreads();  // the sorted chunk is complete in LDS (and every wave has read every counter row)
-        NGP_PROBE_T(6)
         for (uint32_t i = lane; i < cap; i += 64) hrow[i] = 0u;  // own counters for the next item
         // copy-out: records 2u, 2u + 1 of the staging area (16 bytes) become pair unit u of the chunk (12 bytes: the two 16-bit keys share a word)
         uint32_t* __restrict__ chunk = reinterpret_cast<uint32_t*>(records + ((size_t)it.li * plan.n_chunks + it.chunk_x) * MAX_REC);
@@ -1337,23 +1308,11 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
             const uint32_t unit[3] = {keys, q.y, q.w};
             __builtin_memcpy(dst, unit, sizeof(unit));  // 4-byte aligned: global_store_dwordx3
         }
-        NGP_PROBE_T(7)
         g_cur = g_next;
         it.li = li_next;
         it.chunk_x = chunk_next;
-#ifdef NGP_BIN_PHASE_PROBE
-        asm volatile("" ::"v"(g_cur));
-        NGP_PROBE_T(8)
-        t_acc[9] += 1ull;
-#endif
         // (the next item's staging stores come after ITS first barrier, i.e. after every wave has finished this copy)
     }
-#ifdef NGP_BIN_PHASE_PROBE
-    if (tid == 0) {
-        for (int i = 0; i < 9; i++) atomicAdd(&g_bin_probe[i], t_acc[i]);
-        atomicAdd(&g_bin_probe[15], t_acc[9]);
-    }
-#endif
 }
 
 // Pass 2, round 4: DENSE lanes.  The kernel is bound by its instruction stream (34 M VALU per launch, PMC), and the round-3 walk -- a group
@@ -1368,12 +1327,6 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
 // table that used to follow (k_adam: 61 us, HBM-bound) is exactly the kind of stream that fits under a latency-bound kernel.  The update is
 // speculative -- parameters / moments of buffer set state[5] are read, the OTHER set is written; the commit flips the parity only when no
 // gradient of the step was non-finite -- and uses the fp16-rounded gradient, i.e. the bits k_adam would have read from the stored table.
-#ifndef NGP_TADAM_STORE_GRADIENT
-#define NGP_TADAM_STORE_GRADIENT 0
-#endif
-#ifndef NGP_TADAM_PROBE
-#define NGP_TADAM_PROBE 0   // timing probes only (tools/table_adam_probe.py): 1 = no Adam on the round-robin bins of the dense levels, 2 = no stores, 4 = no loads
-#endif
 template <int D, bool ADAM>
 __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_grid_backward_accumulate(const int32_t* __restrict__ offsets, half_t* __restrict__ grad_grid,
                                                                           BinPlan plan, const uint32_t* __restrict__ descriptors,
@@ -1437,7 +1390,7 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
                 const uint32_t e0 = bin * BIN_SLICE + 2u * ((uint32_t)tid + (uint32_t)k * ACC_THREADS);
                 wide[k] = e0 + 1u < size_ && ((off0_ + e0) & 1u) == 0u;   // a 16-byte aligned pair of entries inside the level
                 pp[k] = pm[k] = pv[k] = float4_t{0.0f, 0.0f, 0.0f, 0.0f};
-                if (wide[k] && !(NGP_TADAM_PROBE & 4)) {
+                if (wide[k]) {
                     pp[k] = __builtin_nontemporal_load(reinterpret_cast<const float4_t*>(p_in + (size_t)e0 * 2));
                     pm[k] = __builtin_nontemporal_load(reinterpret_cast<const float4_t*>(m_in + (size_t)e0 * 2));
                     pv[k] = __builtin_nontemporal_load(reinterpret_cast<const float4_t*>(v_in + (size_t)e0 * 2));
@@ -1620,28 +1573,24 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
                     pm[k][c] = m_; pv[k][c] = v_; pp[k][c] = p_;
                     h16[c] = (half_t)p_;
                 }
-                if ((NGP_TADAM_PROBE & 2) && pp[k][0] != 123.456f) continue;
                 if (wide[k]) {
                     __builtin_nontemporal_store(pm[k], reinterpret_cast<float4_t*>(m_out + (size_t)e0 * 2));
                     __builtin_nontemporal_store(pv[k], reinterpret_cast<float4_t*>(v_out + (size_t)e0 * 2));
                     __builtin_nontemporal_store(pp[k], reinterpret_cast<float4_t*>(p_out + (size_t)e0 * 2));
                     *reinterpret_cast<half4_t*>(h_out + (size_t)e0 * 2) = h16;
-                    // (the gradient is consumed right here: it is not stored -- 23 MB of writes per step; -DNGP_TADAM_STORE_GRADIENT for debugging)
-                    if (NGP_TADAM_STORE_GRADIENT && grad_grid) *reinterpret_cast<half4_t*>(gtable + e0) = g16;
+                    // (the gradient is consumed right here: it is not stored -- 23 MB of writes per step)
                 } else {
                     if (ok0) {
                         *reinterpret_cast<float2_t*>(m_out + (size_t)e0 * 2) = float2_t{pm[k].x, pm[k].y};
                         *reinterpret_cast<float2_t*>(v_out + (size_t)e0 * 2) = float2_t{pv[k].x, pv[k].y};
                         *reinterpret_cast<float2_t*>(p_out + (size_t)e0 * 2) = float2_t{pp[k].x, pp[k].y};
                         *reinterpret_cast<half2_t*>(h_out + (size_t)e0 * 2) = half2_t{h16[0], h16[1]};
-                        if (NGP_TADAM_STORE_GRADIENT && grad_grid) gtable[e0] = half2_t{g16[0], g16[1]};
                     }
                     if (ok1) {
                         *reinterpret_cast<float2_t*>(m_out + (size_t)e0 * 2 + 2) = float2_t{pm[k].z, pm[k].w};
                         *reinterpret_cast<float2_t*>(v_out + (size_t)e0 * 2 + 2) = float2_t{pv[k].z, pv[k].w};
                         *reinterpret_cast<float2_t*>(p_out + (size_t)e0 * 2 + 2) = float2_t{pp[k].z, pp[k].w};
                         *reinterpret_cast<half2_t*>(h_out + (size_t)e0 * 2 + 2) = half2_t{h16[2], h16[3]};
-                        if (NGP_TADAM_STORE_GRADIENT && grad_grid) gtable[e0 + 1u] = half2_t{g16[2], g16[3]};
                     }
                 }
             }
@@ -1774,19 +1723,6 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grad_tv(const T* __restrict__ i
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static void fill_levels(GridLevels& lv, uint32_t L, float S, uint32_t H) {
-    ngp_grid_level_table(L, S, H, lv.scale, lv.res);
-}
-
-static uint32_t fwd_blocks(uint32_t B) {
-    // >= 256 workgroups per level already at B = 64k; cap so the level-major order stays meaningful
-    uint32_t nb = cdiv(B, FWD_THREADS);
-    return nb < 1 ? 1 : (nb > 65535u ? 65535u : nb);
-}
-
-#ifndef NGP_FWD_BALANCE
-#define NGP_FWD_BALANCE 1
-#endif
 // level_cost[l]: relative time of one tile of level l (nullptr: unknown -> every level costs the same -> whole levels only, the plain
 // (level mod 8) placement).  Returns the number of slots of the longest work list.
 static_assert(NGP_MAX_LEVELS <= 8 * FWD_MAX_SEG, "whole levels alone must fit the per-XCD work lists");
@@ -1799,13 +1735,10 @@ static uint32_t build_forward_schedule(FwdSchedule& sc, uint32_t L, uint32_t til
     double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto cost = [&](uint32_t l) { return level_cost ? (double)level_cost[l] : 1.0; };
     for (uint32_t l = 0; l < L; l++) {
-#ifdef NGP_FWD_LEVEL_MASK_PROBE  // timing probe only (profiles/r03_grid_forward_levels.txt): launch only the levels of a bit mask
-        if (const char* mk = getenv("NGP_FWD_LEVEL_MASK")) { if (!((strtoul(mk, nullptr, 0) >> l) & 1ul)) continue; }
-#endif
         list[l & 7u].push_back({l, 0u, tiles});
         load[l & 7u] += cost(l) * tiles;
     }
-    if (NGP_FWD_BALANCE && level_cost && L > 8) {
+    if (level_cost && L > 8) {
         double target = 0.0;
         for (int x = 0; x < 8; x++) target += load[x] / 8.0;
         for (int round = 0; round < 16; round++) {
@@ -1856,7 +1789,7 @@ static int launch_forward(const float* inputs, const void* emb, const int32_t* o
             set_error("grid_encode_forward: the double-buffered table selection does not serve the dy_dx kernel");
             return NGP_ERR_INVALID;
         }
-        dim3 grid(fwd_blocks(B), L, 1);
+        dim3 grid(grid_blocks(B, FWD_THREADS), L, 1);
         hipLaunchKernelGGL((k_grid_forward<T, D, C, true>), grid, dim3(FWD_THREADS), 0, st, inputs, (const T*)emb, offsets,
                            (T*)outputs, B, L, lv, (T*)dy_dx, gridtype, ac, interp);
         return check_launch("grid_encode_forward(dy_dx)");
@@ -1870,14 +1803,14 @@ static int launch_forward(const float* inputs, const void* emb, const int32_t* o
     if constexpr (sizeof(T) == 2 && D == 3 && C == 2) {
         if (!ac) {  // the instant-ngp shape: index mode resolved per workgroup, dense levels one lane per point (k_grid_forward_fast)
             const bool smooth = interp == 1u, mapped = im.scale != 0.0f;
-#define NGP_FWD_FAST_LAUNCH(S, M)                                                                                                        \
+#define NGP_LAUNCH_FWD_FAST(S, M)                                                                                                        \
             hipLaunchKernelGGL((k_grid_forward_fast<S, M>), dim3(8u * max_slots), dim3(FWD_THREADS), 0, st, inputs, (const half_t*)emb, \
                                offsets, (half_t*)outputs, B, L, lv, gridtype, interp, sched, ppb, im, sel)
-            if (smooth && mapped) NGP_FWD_FAST_LAUNCH(true, true);
-            else if (smooth) NGP_FWD_FAST_LAUNCH(true, false);
-            else if (mapped) NGP_FWD_FAST_LAUNCH(false, true);
-            else NGP_FWD_FAST_LAUNCH(false, false);
-#undef NGP_FWD_FAST_LAUNCH
+            if (smooth && mapped) NGP_LAUNCH_FWD_FAST(true, true);
+            else if (smooth) NGP_LAUNCH_FWD_FAST(true, false);
+            else if (mapped) NGP_LAUNCH_FWD_FAST(false, true);
+            else NGP_LAUNCH_FWD_FAST(false, false);
+#undef NGP_LAUNCH_FWD_FAST
             return check_launch("grid_encode_forward");
         }
     }
@@ -1885,21 +1818,6 @@ static int launch_forward(const float* inputs, const void* emb, const int32_t* o
                        (T*)outputs, B, L, lv, gridtype, ac, interp, sched, ppb, im, sel);
     return check_launch("grid_encode_forward");
 }
-
-// Compile-time experiment knobs of the backward (no run-time switches in the product path):
-//   -DNGP_GRID_BWD_VARIANT=1 no run merge in the atomic kernel, 2 merge inside 16-lane rows, 3 wave-wide merge through ds_bpermute; 0 = default
-//   -DNGP_GRID_BWD_BIN_FROM=<level> first level that may be binned (99 = never); -1 = every eligible level
-//   -DNGP_GRID_BWD_SEPARATE=1 atomic levels in a launch of their own instead of riding in the record sort's
-#ifndef NGP_GRID_BWD_VARIANT
-#define NGP_GRID_BWD_VARIANT 0
-#endif
-#ifndef NGP_GRID_BWD_BIN_FROM
-#define NGP_GRID_BWD_BIN_FROM -1
-#endif
-#ifndef NGP_GRID_BWD_SEPARATE
-#define NGP_GRID_BWD_SEPARATE 0
-#endif
-static constexpr int grid_backward_variant() { return NGP_GRID_BWD_VARIANT; }
 
 struct BackwardPlan {
     LevelList atomic_levels;
@@ -1921,20 +1839,27 @@ struct BackwardPlan {
 constexpr uint32_t BIN_MIN_SAMPLES = 16384;       // below this the launch overheads of the two extra kernels win
 constexpr uint32_t BIN_MAX_SAMPLES = 1u << 24;
 
-static constexpr int bin_first_level() { return NGP_GRID_BWD_BIN_FROM; }
-
-// Every level of an eligible call is binned: hashed levels in contiguous slices, dense levels in round-robin bins.
 static uint32_t float_bits(float v) {
     uint32_t u;
     memcpy(&u, &v, sizeof(u));
     return u;
 }
 
+// the indexer's words of a binned level's plan entry (BinPlan::lc), from the indexer the kernels of the other paths build on the device
+template <int D>
+static void plan_indexer_words(uint32_t* lc, uint32_t gridtype, bool align_corners, uint32_t size, uint32_t resolution) {
+    LevelIndexer<D> ix;
+    ix.init(gridtype, align_corners, size, resolution);
+    lc[2] |= (ix.hashed ? 4u : 0u) | (ix.need_mod ? 8u : 0u);
+    lc[5] = ix.mask;
+    for (int d = 0; d < D; d++) lc[8 + d] = ix.stride[d];
+}
+
+// Every level of an eligible call is binned: hashed levels in contiguous slices, dense levels in round-robin bins.
 static void plan_backward(BackwardPlan& p, const int32_t* offsets_host, const GridLevels& lv, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                           int dtype, uint32_t gridtype, bool align_corners, bool have_workspace) {
     const bool eligible = have_workspace && offsets_host && dtype == NGP_F16 && C == 2 && (D == 2 || D == 3) && B >= BIN_MIN_SAMPLES &&
                           B <= BIN_MAX_SAMPLES;
-    const int first = bin_first_level();
     p.bins.n_chunks = cdiv(B, (uint32_t)BIN_PPB);
     for (uint32_t l = 0; l < L; l++) {
         const uint32_t size = eligible ? (uint32_t)(offsets_host[l + 1] - offsets_host[l]) : 0u;
@@ -1944,7 +1869,7 @@ static void plan_backward(BackwardPlan& p, const int32_t* offsets_host, const Gr
         // hashed levels: contiguous 4096-entry slices (records spread evenly by construction); dense levels: 128 round-robin bins
         const bool interleave = !hashed && size <= (uint32_t)BIN_DENSE_BINS * BIN_SLICE;
         const uint32_t n_bins = interleave ? (uint32_t)BIN_DENSE_BINS : (size + BIN_SLICE - 1) >> BIN_SLICE_BITS;
-        const bool binned = eligible && size >= 1 && n_bins <= (uint32_t)BIN_MAX_BINS && (first >= 0 ? (int)l >= first : (hashed || interleave));
+        const bool binned = eligible && size >= 1 && n_bins <= (uint32_t)BIN_MAX_BINS && (hashed || interleave);
         if (!binned) {
             p.atomic_levels.level[p.n_atomic++] = (uint8_t)l;
             continue;
@@ -1954,33 +1879,23 @@ static void plan_backward(BackwardPlan& p, const int32_t* offsets_host, const Gr
         for (int k = 0; k < BIN_LC_WORDS; k++) lc[k] = 0u;
         lc[0] = l;
         lc[1] = n_bins;
+        lc[2] = interleave ? 1u : 0u;
         lc[3] = size;
         lc[4] = float_bits(lv.scale[l]);
         lc[7] = p.total_desc;
-        {   // the indexer's constants exactly as LevelIndexer::init derives them on the device (32-bit arithmetic)
-            uint32_t s = 1, stride[3] = {0u, 0u, 0u};
-            for (uint32_t d = 0; d < D && d < 3; d++) {
-                if (s <= size) {
-                    stride[d] = s;
-                    s *= align_corners ? lv.res[l] : (lv.res[l] + 1u);
-                }
-            }
-            const bool hashed_dev = gridtype == 0u && s > size;
-            const bool need_mod = hashed_dev || s > size || align_corners;
-            lc[2] = (interleave ? 1u : 0u) | (hashed_dev ? 4u : 0u) | (need_mod ? 8u : 0u);
-            lc[5] = ((size & (size - 1u)) == 0u) ? size - 1u : 0u;
-            lc[8] = stride[0]; lc[9] = stride[1]; lc[10] = stride[2];
-        }
+        if (D == 2) plan_indexer_words<2>(lc, gridtype, align_corners, size, lv.res[l]);   // (eligible: D is 2 or 3)
+        else plan_indexer_words<3>(lc, gridtype, align_corners, size, lv.res[l]);
         p.total_desc += n_bins * p.bins.n_chunks;
         p.total_records += (uint64_t)p.bins.n_chunks * BIN_PPB * (1u << D);
         p.max_bins = n_bins > p.max_bins ? n_bins : p.max_bins;
     }
 }
 
-template <int D, int AMERGE>
+template <int D>
 static int launch_backward_bins(const void* grad, const float* inputs, const int32_t* offsets, void* grad_emb, uint32_t B,
                                 const GridLevels& lv, uint32_t gridtype, bool ac, uint32_t interp, InputMap im, const BackwardPlan& p,
-                                void* workspace, bool with_atomic_levels, hipStream_t st) {
+                                void* workspace, hipStream_t st) {
+    constexpr int AMERGE = 3;  // the atomic levels ride in the sort's launch: two lanes per sample (fp16, C = 2), DPP run merge
     constexpr size_t acc_smem = sizeof(unsigned long long) * 2 * BIN_SLICE + sizeof(uint32_t) * (BIN_SLICE / 16) +
                                 (ACC_THREADS / 64) * 64 * (sizeof(uint2) + sizeof(uint32_t)) + 4 * sizeof(float);
     const uint32_t bins_cap = p.max_bins <= 128u ? 128u : (uint32_t)BIN_MAX_BINS;
@@ -2007,7 +1922,7 @@ static int launch_backward_bins(const void* grad, const float* inputs, const int
     ap.levels = p.atomic_levels;
     ap.points_per_block = 1024;
     ap.blocks_per_level = cdiv(B, ap.points_per_block);
-    ap.n_blocks = with_atomic_levels ? ap.blocks_per_level * p.n_atomic : 0u;
+    ap.n_blocks = ap.blocks_per_level * p.n_atomic;
     // persistent sort workgroups: as many as are resident at once (LDS and registers allow BIN_RESIDENT per CU), never more than items
     static int n_cus = 0;
     if (!n_cus) {
@@ -2052,43 +1967,21 @@ static int launch_backward(const void* grad, const float* inputs, const int32_t*
                            bool ac, uint32_t interp, InputMap im, const BackwardPlan& plan, void* workspace, hipStream_t st) {
     int rc = NGP_OK;
     constexpr bool can_bin = sizeof(T) == 2 && C == 2 && (D == 2 || D == 3);
-    // the atomic levels ride in the launch of the record sort when there is one (and the merge variant is the default one)
-    const int variant = grid_backward_variant();
-    const bool mixed = can_bin && plan.n_binned > 0 && (variant == 0 || variant == 3) && !NGP_GRID_BWD_SEPARATE;
-    if (plan.n_atomic && !mixed) {
+    const bool sorted = can_bin && plan.n_binned > 0;  // the atomic levels then ride in the launch of the record sort
+    if (plan.n_atomic && !sorted) {
         // one block covers `ppb` consecutive points of one level; >= ~4 blocks per CU over all levels fills the chip
         uint32_t ppb = 2048;
         while (ppb > 128 && (uint64_t)cdiv(B, ppb) * plan.n_atomic < 2048) ppb >>= 1;
         dim3 grid(cdiv(B, ppb), plan.n_atomic, 1);
-        if constexpr (BwdLanes<T, C>::LPP == 2) {  // two lanes per sample: the run merge is pure DPP (default: over the whole wave)
-            if (variant == 2 || variant == 0) {
-                if (variant == 2)
-                    hipLaunchKernelGGL((k_grid_backward<T, D, C, 2>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets,
-                                       (T*)grad_emb, B, plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
-                else
-                    hipLaunchKernelGGL((k_grid_backward<T, D, C, 3>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets,
-                                       (T*)grad_emb, B, plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
-                rc = check_launch("grid_encode_backward");
-                if (rc) return rc;
-                goto atomic_done;
-            }
-        }
-        if (variant == 1)
-            hipLaunchKernelGGL((k_grid_backward<T, D, C, 0>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets,
-                               (T*)grad_emb, B, plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
-        else
-            hipLaunchKernelGGL((k_grid_backward<T, D, C, 1>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets,
-                               (T*)grad_emb, B, plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
+        constexpr int MERGE = BwdLanes<T, C>::LPP == 2 ? 3 : 1;  // two lanes per sample: the run merge is pure DPP
+        hipLaunchKernelGGL((k_grid_backward<T, D, C, MERGE>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets, (T*)grad_emb, B,
+                           plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
         rc = check_launch("grid_encode_backward");
         if (rc) return rc;
     }
-atomic_done:
-    if (plan.n_binned) {
-        if constexpr (can_bin) {
-            rc = variant == 3 ? launch_backward_bins<D, 1>(grad, inputs, offsets, grad_emb, B, lv, gridtype, ac, interp, im, plan, workspace,
-                                                           mixed && plan.n_atomic > 0, st)
-                              : launch_backward_bins<D, 3>(grad, inputs, offsets, grad_emb, B, lv, gridtype, ac, interp, im, plan, workspace,
-                                                           mixed && plan.n_atomic > 0, st);
+    if constexpr (can_bin) {
+        if (sorted) {
+            rc = launch_backward_bins<D>(grad, inputs, offsets, grad_emb, B, lv, gridtype, ac, interp, im, plan, workspace, st);
             if (rc) return rc;
         }
     }
@@ -2117,32 +2010,11 @@ __global__ __launch_bounds__(256) void k_flag_nonfinite(const T* __restrict__ g,
 template <typename T, int D, int C>
 static int launch_tv(const void* inputs, const void* emb, void* grad, const int32_t* offsets, float weight, uint32_t B,
                      uint32_t L, const GridLevels& lv, uint32_t gridtype, bool ac, hipStream_t st) {
-    dim3 grid(fwd_blocks(B), L, 1);
+    dim3 grid(grid_blocks(B, FWD_THREADS), L, 1);
     hipLaunchKernelGGL((k_grad_tv<T, D, C>), grid, dim3(FWD_THREADS), 0, st, (const T*)inputs, (const T*)emb, (T*)grad,
                        offsets, weight, B, lv, gridtype, ac);
     return check_launch("grad_total_variation");
 }
-
-#define NGP_DISPATCH_DC(FN, T, ...)                                                               \
-    switch (D * 16 + C) {                                                                         \
-        case 2 * 16 + 1: return FN<T, 2, 1>(__VA_ARGS__);                                          \
-        case 2 * 16 + 2: return FN<T, 2, 2>(__VA_ARGS__);                                          \
-        case 2 * 16 + 4: return FN<T, 2, 4>(__VA_ARGS__);                                          \
-        case 2 * 16 + 8: return FN<T, 2, 8>(__VA_ARGS__);                                          \
-        case 3 * 16 + 1: return FN<T, 3, 1>(__VA_ARGS__);                                          \
-        case 3 * 16 + 2: return FN<T, 3, 2>(__VA_ARGS__);                                          \
-        case 3 * 16 + 4: return FN<T, 3, 4>(__VA_ARGS__);                                          \
-        case 3 * 16 + 8: return FN<T, 3, 8>(__VA_ARGS__);                                          \
-        case 4 * 16 + 1: return FN<T, 4, 1>(__VA_ARGS__);                                          \
-        case 4 * 16 + 2: return FN<T, 4, 2>(__VA_ARGS__);                                          \
-        case 4 * 16 + 4: return FN<T, 4, 4>(__VA_ARGS__);                                          \
-        case 4 * 16 + 8: return FN<T, 4, 8>(__VA_ARGS__);                                          \
-        case 5 * 16 + 1: return FN<T, 5, 1>(__VA_ARGS__);                                          \
-        case 5 * 16 + 2: return FN<T, 5, 2>(__VA_ARGS__);                                          \
-        case 5 * 16 + 4: return FN<T, 5, 4>(__VA_ARGS__);                                          \
-        case 5 * 16 + 8: return FN<T, 5, 8>(__VA_ARGS__);                                          \
-        default: break;                                                                            \
-    }
 
 static int check_grid_args(const char* fn, uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype, bool f64_ok = false) {
     (void)B;
@@ -2158,14 +2030,6 @@ static int check_grid_args(const char* fn, uint32_t B, uint32_t D, uint32_t C, u
 }  // namespace ngp
 
 using namespace ngp;
-
-#ifdef NGP_BIN_PHASE_PROBE
-extern "C" int ngp_debug_bin_probe(unsigned long long* out16, int reset) {
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(ngp::g_bin_probe), 16 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(ngp::g_bin_probe), z, sizeof(z)) != hipSuccess) return 1; }
-    return 0;
-}
-#endif
 
 extern "C" int ngp_grid_level_table(uint32_t L, float S, uint32_t H, float* scale_out, uint32_t* resolution_out) {
     NGP_REQUIRE(scale_out && resolution_out, NGP_ERR_INVALID, "ngp_grid_level_table: NULL output");
@@ -2227,9 +2091,9 @@ static int grid_encode_forward_impl(const float* inputs, const void* embeddings,
     for (uint32_t l = 0; level_cost && l < L; l++)
         NGP_REQUIRE(level_cost[l] > 0.0f && level_cost[l] < 1e6f, NGP_ERR_INVALID, "grid_encode_forward: level_cost[%u] must be positive and finite", l);
     if (dtype == NGP_F16) {
-        NGP_DISPATCH_DC(launch_forward, half_t, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, im, level_cost, sel, st)
+        NGP_DISPATCH_DC(D, C, launch_forward<half_t, D_, C_>(inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, im, level_cost, sel, st))
     } else {
-        NGP_DISPATCH_DC(launch_forward, float, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, im, level_cost, sel, st)
+        NGP_DISPATCH_DC(D, C, launch_forward<float, D_, C_>(inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, im, level_cost, sel, st))
     }
     set_error("grid_encode_forward: unsupported (D=%u, C=%u)", D, C);
     return NGP_ERR_INVALID;
@@ -2292,24 +2156,27 @@ extern "C" int ngp_grid_encode_forward(const float* inputs, const void* embeddin
                                       dtype, 0.0f, stream);
 }
 
+// the plan of a backward call that has a workspace, for the host-only queries below; false: arguments no call would accept
+static bool plan_for_query(BackwardPlan& plan, const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                           uint32_t gridtype, int align_corners, int dtype) {
+    if (!offsets_host || L < 1 || L > NGP_MAX_LEVELS || D < 2 || D > 5) return false;
+    GridLevels lv;
+    fill_levels(lv, L, S, H);
+    plan_backward(plan, offsets_host, lv, B, D, C, L, dtype, gridtype, align_corners != 0, true);
+    return true;
+}
+
 extern "C" size_t ngp_grid_backward_workspace_bytes(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                                     uint32_t H, uint32_t gridtype, int align_corners, int dtype) {
     if (dtype == NGP_F64) return L >= 1 && L <= NGP_MAX_LEVELS ? f64_grid_backward_workspace_bytes(B, D) : 0;   // (B and D only: no offsets needed)
-    if (!offsets_host || L < 1 || L > NGP_MAX_LEVELS || D < 2 || D > 5) return 0;
-    GridLevels lv;
-    fill_levels(lv, L, S, H);
     BackwardPlan plan;
-    plan_backward(plan, offsets_host, lv, B, D, C, L, dtype, gridtype, align_corners != 0, true);
-    return plan.workspace_bytes();
+    return plan_for_query(plan, offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) ? plan.workspace_bytes() : 0;
 }
 
 extern "C" uint32_t ngp_grid_table_adam_prefix(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                                                uint32_t gridtype, int align_corners, int dtype) {
-    if (!offsets_host || L < 1 || L > NGP_MAX_LEVELS || D < 2 || D > 5) return 0xffffffffu;
-    GridLevels lv;
-    fill_levels(lv, L, S, H);
     BackwardPlan plan;
-    plan_backward(plan, offsets_host, lv, B, D, C, L, dtype, gridtype, align_corners != 0, true);
+    if (!plan_for_query(plan, offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype)) return 0xffffffffu;
     if (plan.n_atomic != 0 || plan.n_binned != L || dtype != NGP_F16 || C != 2) return 0xffffffffu;
     uint32_t k = 0;
     while (k < L && plan.bins.interleaved(k)) k++;
@@ -2322,7 +2189,8 @@ template <typename T>
 static int dispatch_backward(uint32_t D, uint32_t C, const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B,
                              uint32_t L, const GridLevels& lv, const void* dy_dx, void* grad_inputs, uint32_t gridtype, bool ac, uint32_t interp,
                              InputMap im, const BackwardPlan& plan, void* workspace, hipStream_t st) {
-    NGP_DISPATCH_DC(launch_backward, T, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, im, plan, workspace, st)
+    NGP_DISPATCH_DC(D, C, launch_backward<T, D_, C_>(grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, im, plan,
+                                                     workspace, st))
     set_error("grid_encode_backward: unsupported (D=%u, C=%u)", D, C);
     return NGP_ERR_INVALID;
 }
@@ -2495,9 +2363,9 @@ extern "C" int ngp_grad_total_variation(const void* inputs, const void* embeddin
     const bool ac = align_corners != 0;
     if (dtype == NGP_F64) return f64_grad_tv(inputs, embeddings, grad, offsets, weight, B, D, C, L, S, H, gridtype, ac, st);
     if (dtype == NGP_F16) {
-        NGP_DISPATCH_DC(launch_tv, half_t, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st)
+        NGP_DISPATCH_DC(D, C, launch_tv<half_t, D_, C_>(inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st))
     } else {
-        NGP_DISPATCH_DC(launch_tv, float, inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st)
+        NGP_DISPATCH_DC(D, C, launch_tv<float, D_, C_>(inputs, embeddings, grad, offsets, weight, B, L, lv, gridtype, ac, st))
     }
     set_error("grad_total_variation: unsupported (D=%u, C=%u)", D, C);
     return NGP_ERR_INVALID;
@@ -2513,7 +2381,7 @@ extern "C" int ngp_grid_corner_indices(const float* inputs, const int32_t* offse
     GridLevels lv;
     fill_levels(lv, L, S, H);
     hipStream_t st = as_stream(stream);
-    dim3 grid(fwd_blocks(B), L, 1);
+    dim3 grid(grid_blocks(B, FWD_THREADS), L, 1);
     const bool ac = align_corners != 0;
     switch (D) {
         case 2: hipLaunchKernelGGL((k_grid_corner_indices<2>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;

@@ -42,6 +42,21 @@ def level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_
     return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
 
 
+def _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, geometry):
+    """d loss / d inputs (None without dy_dx) and d loss / d embeddings from the upstream gradient [B, L*C]"""
+    n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
+    grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
+    grad_embeddings = torch.zeros_like(embeddings)
+    grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
+
+    _backend.grid_encode_backward(grad_level_major, inputs, embeddings, offsets, grad_embeddings, n_points, dim, feat,
+                                  n_levels, log2_scale, base_resolution, dy_dx, grad_inputs, gridtype, align_corners,
+                                  interpolation)
+    if grad_inputs is not None:
+        grad_inputs = grad_inputs.to(inputs.dtype)
+    return grad_inputs, grad_embeddings
+
+
 class _grid_encode(Function):
     @staticmethod
     @custom_fwd(device_type='cuda')
@@ -78,44 +93,24 @@ class _grid_encode(Function):
     @custom_bwd(device_type='cuda')
     def backward(ctx, grad):
         inputs, embeddings, offsets, dy_dx = ctx.saved_tensors
-        n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = ctx.geometry
         if torch.is_grad_enabled():
             # create_graph=True (eikonal / SDF losses on d enc / d x): the same backend calls as a differentiable op
             grad_inputs, grad_embeddings = _grid_encode_backward.apply(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry, *ctx.sources)
-            return grad_inputs, grad_embeddings, None, None, None, None, None, None, None
-
-        grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
-        grad_embeddings = torch.zeros_like(embeddings)
-        grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
-
-        _backend.grid_encode_backward(grad_level_major, inputs, embeddings, offsets, grad_embeddings, n_points, dim, feat,
-                                      n_levels, log2_scale, base_resolution, dy_dx, grad_inputs, gridtype, align_corners,
-                                      interpolation)
-        if grad_inputs is not None:
-            grad_inputs = grad_inputs.to(inputs.dtype)
+        else:
+            grad_inputs, grad_embeddings = _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry)
         return grad_inputs, grad_embeddings, None, None, None, None, None, None, None
 
 
 class _grid_encode_backward(Function):
     """The first backward of the grid encoder as an op of its own, so that its outputs (grad_inputs, grad_embeddings) can be differentiated:
-    forward issues exactly the calls of _grid_encode.backward (the same bits), backward is the second order (_grid_encode_second, DESIGN.md
+    forward is _first_order_backward, as _grid_encode.backward (the same bits), backward is the second order (_grid_encode_second, DESIGN.md
     3.6)."""
 
     @staticmethod
     def forward(ctx, grad, inputs, embeddings, offsets, dy_dx, geometry, inputs_src=None, table_src=None):
         # inputs_src / table_src: the tensors the encoder was called with when `inputs` / `embeddings` are copies of them (the half table of
         # autocast): the second-order gradients go there
-        n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
-
-        grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
-        grad_embeddings = torch.zeros_like(embeddings)
-        grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
-
-        _backend.grid_encode_backward(grad_level_major, inputs, embeddings, offsets, grad_embeddings, n_points, dim, feat,
-                                      n_levels, log2_scale, base_resolution, dy_dx, grad_inputs, gridtype, align_corners,
-                                      interpolation)
-        if grad_inputs is not None:
-            grad_inputs = grad_inputs.to(inputs.dtype)
+        grad_inputs, grad_embeddings = _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, geometry)
         ctx.save_for_backward(grad, inputs, embeddings, offsets)
         ctx.geometry = geometry
         ctx.sources = (inputs_src, table_src)
