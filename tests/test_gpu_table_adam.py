@@ -40,12 +40,12 @@ def _backward(enc, g_enc, x, opt, fused_adam):
     fused._grid_backward(g_enc, x, enc.offsets, emb._ngp_grad16, M, 16, S, 16, enc.gridtype_id, 0, enc.interp_id, 0.0, capi.stream(),
                          found_inf=opt.scalars[2:3], slabs=None, overwrite=True, table_adam=opt.table_adam() if fused_adam else None)
     emb._ngp_deposit_overwritten = True
-    if fused_adam:   # (what fused._mark_table_adam leaves for the optimizer's closing launch: the dense-level prefix is its part)
+    if fused_adam:   # (what the fused iteration announces to the optimizer's closing launch: the dense-level prefix is its part)
         arr = capi.host_offsets(enc.offsets)
         prefix = int(capi.lib.ngp_grid_table_adam_prefix(ctypes.cast(arr, ctypes.c_void_p), M, 3, 2, 16, S, 16, enc.gridtype_id, 0, capi.NGP_F16))
         assert 0 < prefix < 0xffffffff and prefix == int(enc.offsets[5])     # levels 0-4 of the lego table are dense
-        emb._ngp_table_adam_prefix = prefix
-        emb._ngp_table_adam_done = True
+        from optim import announce_overwrite
+        announce_overwrite(emb, table_adam_prefix=prefix)
 
 
 def test_fused_flush_is_the_separate_adam_sweep_bit_for_bit():

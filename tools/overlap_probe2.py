@@ -51,7 +51,7 @@ def split_with_box():
     box = {}
     cfg = fused.network_cfg(model.encoder, model.sigma_net, model.color_net, model.bound, True)
     bg_t, rcfg = fused._render_cfg(model, cap, 1, True, 0, 1024, 1e-4)
-    bufs = fused._optimizer_buffers((model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights))
+    bufs = fused._operands((model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights), deposit=True)
     def m():
         box['m'] = fused._render_train_march(o, d, model.density_bitfield, model.aabb_train, counter, cfg, rcfg, opt.scalars[3:4])
     def r():

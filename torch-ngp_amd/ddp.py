@@ -64,10 +64,9 @@ def broadcast_parameters(module, src=0):
     # an optim.NGPAdam built before this call holds fp16 shadow copies of the OLD values, and a write through `.data` does not bump the
     # autograd version counter the fused path watches: refresh them here so that every rank starts from the broadcast weights
     for p in module.parameters():
-        sh = getattr(p, '_ngp_fp16', None)
-        if sh is not None:
-            sh.copy_(p.detach())
-            p._ngp_version = p._version
+        if getattr(p, '_ngp_fp16', None) is not None:
+            from optim import refresh_shadow   # (only where an optim.NGPAdam exists: this module does not need the native library)
+            refresh_shadow(p)
 
 
 @torch.no_grad()

@@ -19,19 +19,26 @@ marchers pad to 128, raymarching.py:200-203).  Everything else takes the module-
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 from torch.autograd import Function
 
 import _ngp_capi as capi
+from optim import announce_overwrite, clean_deposits, resync_stale_shadows
 
 _PLANAR_IN = capi.NGP_FF_INPUT_PLANAR
 _PLANAR_DX = capi.NGP_FF_DX_PLANAR
 
-
-def _check(rc):
-    capi.check(rc)
+# The state the launches of one call share, by name.
+NetCfg = namedtuple('NetCfg', 'bound L S H gridtype align interp nl_sigma nl_color training')   # network_cfg(); S = log2(per_level_scale)
+RenderCfg = namedtuple('RenderCfg', 'cascade grid_size min_near capacity perturb dt_gamma max_steps T_thresh density_scale bg_scalar')
+Marched = namedtuple('Marched', 'xyzs dirs deltas rays nears fars ws')   # outputs of the march (ws: its workspace, rows_used in word 0)
+# what the backward launches read; all tensors or None (ctx.save_for_backward).  weights_sum / image_raw: composite outputs, None without it
+Saved = namedtuple('Saved', 'xyzs offsets enc ws16 wc16 fb_s fb_c h16 color_in rgb sigma deltas rays weights_sum image_raw bg march_ws')
+# fp16 operands the kernels read + fp16 gradient buffers the backward deposits into (None: the gradients go to autograd)
+Bufs = namedtuple('Bufs', 'emb16 ws16 wc16 g_emb g_ws g_wc')
 
 
 def _grid_forward(x, emb16, offsets, enc, M, L, S, H, gridtype, align, interp, bound, costs, st):
@@ -40,11 +47,11 @@ def _grid_forward(x, emb16, offsets, enc, M, L, S, H, gridtype, align, interp, b
     shadow tensor (`_ngp_sel`): the kernel then picks the current copy itself (ngp_grid_encode_forward_sel) -- valid under graph replay."""
     sel = getattr(emb16, '_ngp_sel', None)
     if sel is not None:
-        _check(capi.lib.ngp_grid_encode_forward_sel(x.data_ptr(), emb16.data_ptr(), sel[0].data_ptr(), sel[1].data_ptr(), None, offsets.data_ptr(),
-                                                    enc.data_ptr(), M, 3, 2, L, S, H, gridtype, align, interp, capi.NGP_F16, float(bound), costs, st))
+        capi.check(capi.lib.ngp_grid_encode_forward_sel(x.data_ptr(), emb16.data_ptr(), sel[0].data_ptr(), sel[1].data_ptr(), None, offsets.data_ptr(),
+                                                         enc.data_ptr(), M, 3, 2, L, S, H, gridtype, align, interp, capi.NGP_F16, float(bound), costs, st))
     else:
-        _check(capi.lib.ngp_grid_encode_forward_sched(x.data_ptr(), emb16.data_ptr(), offsets.data_ptr(), enc.data_ptr(), M, 3, 2, L, S, H,
-                                                      None, gridtype, align, interp, capi.NGP_F16, float(bound), costs, st))
+        capi.check(capi.lib.ngp_grid_encode_forward_sched(x.data_ptr(), emb16.data_ptr(), offsets.data_ptr(), enc.data_ptr(), M, 3, 2, L, S, H,
+                                                           None, gridtype, align, interp, capi.NGP_F16, float(bound), costs, st))
 
 
 class _fused_ngp(Function):
@@ -53,22 +60,20 @@ class _fused_ngp(Function):
         """x [M,3] fp32 in [-bound,bound], d [M,3] fp32; embeddings [n,2] fp32 param; w_* flat fp32 params -> sigma [M] fp32, rgb [M,3] fp32.
         density_scale (inference only): sigma comes out multiplied by it -- the kernel's `scale * exp(h)` is the fp32 product the renderer's
         `self.density_scale * sigmas` would compute in a launch of its own"""
-        (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, training) = cfg
         M = x.shape[0]
         dev = x.device
         st = capi.stream()
         x = x.contiguous()
         d = d.contiguous()
-        emb16, ws16, wc16 = _half_weights(embeddings, w_sigma, w_color, bufs)
         half = dict(device=dev, dtype=torch.half)
 
-        enc = torch.empty(L, M, 2, **half)
+        enc = torch.empty(cfg.L, M, 2, **half)
         # work lists balanced over the XCDs by the per-level cost model (without one, level l goes whole to XCD l % 8 and the launch lasts as long
         # as levels 7 + 15 take).  The rows of the eval loop are rays' consecutive samples / neighbouring pixels' samples: about a march
         # step apart, as in training -- the same model (half / twice / four times that spacing: the same frame time); for points without any
         # order it still says "fine hashed levels cost more than dense ones".  800x800 frame: 14.4 -> 13.6 ms / 1.42 -> 1.35 ms, same box.
-        costs = capi.ray_level_costs(L, S, H, 3.0 ** 0.5 / (1024.0 * max(float(bound), 1e-6))) if USE_BALANCED_FORWARD else None
-        _grid_forward(x, emb16, offsets, enc, M, L, S, H, gridtype, align, interp, bound, costs, st)
+        costs = capi.ray_level_costs(cfg.L, cfg.S, cfg.H, 3.0 ** 0.5 / (1024.0 * max(float(cfg.bound), 1e-6))) if USE_BALANCED_FORWARD else None
+        _grid_forward(x, bufs.emb16, offsets, enc, M, cfg.L, cfg.S, cfg.H, cfg.gridtype, cfg.align, cfg.interp, cfg.bound, costs, st)
         h16 = torch.empty(M, 16, **half)
         color_in = torch.empty(M, 32, **half)
         out16 = torch.empty(M, 16, **half)
@@ -77,15 +82,16 @@ class _fused_ngp(Function):
         # sigma MLP -> trunc_exp / SH / feature shuffle -> colour MLP -> sigmoid in ONE launch (ngp_network_forward); USE_FUSED_NETWORK = False
         # issues the four kernels it replaces (bit-identical, tests/test_gpu_pipeline.py)
         d_valid = d.shape[0]
-        if training:
-            fb_s = torch.empty(nl_sigma, M, 64, **half)
-            fb_c = torch.empty(nl_color, M, 64, **half)
+        if cfg.training:
+            fb_s = torch.empty(cfg.nl_sigma, M, 64, **half)
+            fb_c = torch.empty(cfg.nl_color, M, 64, **half)
         else:
             fb_s = fb_c = None
-        assert not training or density_scale == 1.0, 'the backward of _fused_ngp knows no density scale (the fused training render folds it itself)'
-        _network_forward(enc, d, d_valid, ws16, wc16, nl_sigma, nl_color, float(density_scale), training, fb_s, h16, sigma, color_in, fb_c, out16, rgb, M, st)
-        if training:
-            ctx.save_for_backward(x, offsets, enc, ws16, wc16, fb_s, fb_c, h16, color_in, rgb)
+        assert not cfg.training or density_scale == 1.0, 'the backward of _fused_ngp knows no density scale (the fused training render folds it itself)'
+        _network_forward(enc, d, d_valid, bufs.ws16, bufs.wc16, cfg.nl_sigma, cfg.nl_color, float(density_scale), cfg.training, fb_s, h16, sigma,
+                         color_in, fb_c, out16, rgb, M, st)
+        if cfg.training:
+            ctx.save_for_backward(x, offsets, enc, bufs.ws16, bufs.wc16, fb_s, fb_c, h16, color_in, rgb)
             ctx.cfg = cfg
             ctx.n_emb = embeddings.shape[0]
             ctx.bufs = bufs
@@ -94,7 +100,8 @@ class _fused_ngp(Function):
     @staticmethod
     def backward(ctx, grad_sigma, grad_rgb):
         x, offsets, enc, ws16, wc16, fb_s, fb_c, h16, color_in, rgb = ctx.saved_tensors
-        (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, _) = ctx.cfg
+        cfg = ctx.cfg
+        nl_sigma, nl_color = cfg.nl_sigma, cfg.nl_color
         M = x.shape[0]
         dev = x.device
         st = capi.stream()
@@ -103,19 +110,19 @@ class _fused_ngp(Function):
         grad_rgb = torch.zeros(M, 3, device=dev) if grad_rgb is None else grad_rgb.contiguous().float()
 
         g_out16 = torch.empty(M, 16, **half)
-        _check(capi.lib.ngp_pipeline_rgb_backward(grad_rgb.data_ptr(), rgb.data_ptr(), g_out16.data_ptr(), M, st))
+        capi.check(capi.lib.ngp_pipeline_rgb_backward(grad_rgb.data_ptr(), rgb.data_ptr(), g_out16.data_ptr(), M, st))
         g_color_in = torch.empty(M, 32, **half)
-        g_emb, g_ws, g_wc, deposited = _grad_targets(ctx.bufs, ctx.n_emb, ws16, wc16, dev)
+        g_emb, g_ws, g_wc, deposited = _grad_targets(ctx.bufs, ctx.n_emb, dev)
         scratch_c = torch.empty(nl_color, M, 64, **half)  # per-workgroup fp32 weight-gradient slabs live here
-        _check(capi.lib.ngp_ffmlp_backward_ex(g_out16.data_ptr(), color_in.data_ptr(), wc16.data_ptr(), fb_c.data_ptr(), M, 32, 16, 64,
-                                              nl_color, 0, 6, 1, scratch_c.data_ptr(), g_color_in.data_ptr(), g_wc.data_ptr(), 0, st))
+        capi.check(capi.lib.ngp_ffmlp_backward_ex(g_out16.data_ptr(), color_in.data_ptr(), wc16.data_ptr(), fb_c.data_ptr(), M, 32, 16, 64,
+                                                   nl_color, 0, 6, 1, scratch_c.data_ptr(), g_color_in.data_ptr(), g_wc.data_ptr(), 0, st))
         g_h16 = g_out16  # reuse: [M,16] fp16
-        _check(capi.lib.ngp_pipeline_mid_backward(grad_sigma.data_ptr(), h16.data_ptr(), g_color_in.data_ptr(), g_h16.data_ptr(), M, 1.0, st))
-        g_enc = torch.empty(L, M, 2, **half)
+        capi.check(capi.lib.ngp_pipeline_mid_backward(grad_sigma.data_ptr(), h16.data_ptr(), g_color_in.data_ptr(), g_h16.data_ptr(), M, 1.0, st))
+        g_enc = torch.empty(cfg.L, M, 2, **half)
         scratch_s = scratch_c[:nl_sigma]
-        _check(capi.lib.ngp_ffmlp_backward_ex(g_h16.data_ptr(), enc.data_ptr(), ws16.data_ptr(), fb_s.data_ptr(), M, 32, 16, 64, nl_sigma,
-                                              0, 6, 1, scratch_s.data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(), _PLANAR_IN | _PLANAR_DX, st))
-        _grid_backward(g_enc, x, offsets, g_emb, M, L, S, H, gridtype, align, interp, bound, st)
+        capi.check(capi.lib.ngp_ffmlp_backward_ex(g_h16.data_ptr(), enc.data_ptr(), ws16.data_ptr(), fb_s.data_ptr(), M, 32, 16, 64, nl_sigma,
+                                                   0, 6, 1, scratch_s.data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(), _PLANAR_IN | _PLANAR_DX, st))
+        _grid_backward(g_enc, x, offsets, g_emb, M, cfg.L, cfg.S, cfg.H, cfg.gridtype, cfg.align, cfg.interp, cfg.bound, st)
         if deposited:
             return None, None, None, None, None, None, None, None, None
         return None, None, g_emb, g_ws, g_wc, None, None, None, None
@@ -127,21 +134,21 @@ USE_FUSED_NETWORK = True  # one launch for the whole network behind the encoder 
 def _network_forward(enc, dirs, d_valid, ws16, wc16, nl_sigma, nl_color, density_scale, training, fb_s, h16, sigma, color_in, fb_c, out16, rgb, M, st):
     """enc [L,M,2] fp16 (planar) + dirs -> sigma [M] fp32, rgb [M,3] fp32 (+ the activations the backward reads when training)"""
     if USE_FUSED_NETWORK:
-        _check(capi.lib.ngp_network_forward(enc.data_ptr(), dirs.data_ptr(), M, d_valid, ws16.data_ptr(), wc16.data_ptr(), nl_sigma, nl_color,
-                                            float(density_scale), 1 if training else 0, capi.ptr(fb_s), capi.ptr(h16) if training else None,
-                                            sigma.data_ptr(), capi.ptr(color_in) if training else None, capi.ptr(fb_c), rgb.data_ptr(), _PLANAR_IN, st))
+        capi.check(capi.lib.ngp_network_forward(enc.data_ptr(), dirs.data_ptr(), M, d_valid, ws16.data_ptr(), wc16.data_ptr(), nl_sigma, nl_color,
+                                                 float(density_scale), 1 if training else 0, capi.ptr(fb_s), capi.ptr(h16) if training else None,
+                                                 sigma.data_ptr(), capi.ptr(color_in) if training else None, capi.ptr(fb_c), rgb.data_ptr(), _PLANAR_IN, st))
         return
     if training:
-        _check(capi.lib.ngp_ffmlp_forward_ex(enc.data_ptr(), ws16.data_ptr(), M, 32, 16, 64, nl_sigma, 0, 6, fb_s.data_ptr(), h16.data_ptr(),
-                                             _PLANAR_IN, st))
+        capi.check(capi.lib.ngp_ffmlp_forward_ex(enc.data_ptr(), ws16.data_ptr(), M, 32, 16, 64, nl_sigma, 0, 6, fb_s.data_ptr(), h16.data_ptr(),
+                                                  _PLANAR_IN, st))
     else:
-        _check(capi.lib.ngp_ffmlp_inference_ex(enc.data_ptr(), ws16.data_ptr(), M, 32, 16, 64, nl_sigma, 0, 6, None, h16.data_ptr(), _PLANAR_IN, st))
-    _check(capi.lib.ngp_pipeline_mid_forward(h16.data_ptr(), dirs.data_ptr(), sigma.data_ptr(), color_in.data_ptr(), M, d_valid, float(density_scale), st))
+        capi.check(capi.lib.ngp_ffmlp_inference_ex(enc.data_ptr(), ws16.data_ptr(), M, 32, 16, 64, nl_sigma, 0, 6, None, h16.data_ptr(), _PLANAR_IN, st))
+    capi.check(capi.lib.ngp_pipeline_mid_forward(h16.data_ptr(), dirs.data_ptr(), sigma.data_ptr(), color_in.data_ptr(), M, d_valid, float(density_scale), st))
     if training:
-        _check(capi.lib.ngp_ffmlp_forward_ex(color_in.data_ptr(), wc16.data_ptr(), M, 32, 16, 64, nl_color, 0, 6, fb_c.data_ptr(), out16.data_ptr(), 0, st))
+        capi.check(capi.lib.ngp_ffmlp_forward_ex(color_in.data_ptr(), wc16.data_ptr(), M, 32, 16, 64, nl_color, 0, 6, fb_c.data_ptr(), out16.data_ptr(), 0, st))
     else:
-        _check(capi.lib.ngp_ffmlp_inference_ex(color_in.data_ptr(), wc16.data_ptr(), M, 32, 16, 64, nl_color, 0, 6, None, out16.data_ptr(), 0, st))
-    _check(capi.lib.ngp_pipeline_rgb_forward(out16.data_ptr(), rgb.data_ptr(), M, st))
+        capi.check(capi.lib.ngp_ffmlp_inference_ex(color_in.data_ptr(), wc16.data_ptr(), M, 32, 16, 64, nl_color, 0, 6, None, out16.data_ptr(), 0, st))
+    capi.check(capi.lib.ngp_pipeline_rgb_forward(out16.data_ptr(), rgb.data_ptr(), M, st))
 
 
 def _grid_backward(g_enc, x, offsets, g_emb, M, L, S, H, gridtype, align, interp, bound, st, found_inf=None, slabs=None, overwrite=False,
@@ -165,67 +172,50 @@ def _grid_backward(g_enc, x, offsets, g_emb, M, L, S, H, gridtype, align, interp
     if found_inf is not None and arr is None:
         raise RuntimeError('fused: the in-kernel non-finite sweep needs the host copy of the encoder offsets (call iteration_checks_gradients '
                            'outside stream capture first)')
-    _check(capi.lib.ngp_grid_encode_backward_checked_slabs(g_enc.data_ptr(), x.data_ptr(), None, offsets.data_ptr(), capi.ptr(g_emb), M, 3, 2, L, S,
-                                                            H, None, None, gridtype, align, interp, capi.NGP_F16, float(bound),
-                                                            None if arr is None else ctypes.cast(arr, ctypes.c_void_p), capi.ptr(ws), nbytes,
-                                                            capi.ptr(found_inf), None if slabs is None else ctypes.cast(ctypes.pointer(slabs), ctypes.c_void_p),
-                                                            st))
+    capi.check(capi.lib.ngp_grid_encode_backward_checked_slabs(g_enc.data_ptr(), x.data_ptr(), None, offsets.data_ptr(), capi.ptr(g_emb), M, 3, 2, L, S,
+                                                                 H, None, None, gridtype, align, interp, capi.NGP_F16, float(bound),
+                                                                 None if arr is None else ctypes.cast(arr, ctypes.c_void_p), capi.ptr(ws), nbytes,
+                                                                 capi.ptr(found_inf), None if slabs is None else ctypes.cast(ctypes.pointer(slabs), ctypes.c_void_p),
+                                                                 st))
 
 
-def _half_weights(embeddings, w_sigma, w_color, bufs):
-    """fp16 operands of the kernels: the optimizer's shadow copies when optim.NGPAdam maintains them, else a cast (grid.py:43-44)"""
-    if bufs is not None:
-        return bufs[0], bufs[1], bufs[2]
-    return embeddings.detach().to(torch.half), w_sigma.detach().to(torch.half), w_color.detach().to(torch.half)
+def _half_weights(params, cast=True):
+    """the fp16 copy of each parameter that the kernels read: the one pinned for the duration of a render call (pinned_half_weights), else
+    the optimizer's shadow (optim.NGPAdam; resynced first), else -- `cast` -- a cast of the parameter (grid.py:43-44), without it None"""
+    sh = [getattr(p, '_ngp_fp16_pin', None) for p in params]
+    if any(t is None for t in sh):
+        resync_stale_shadows(params)
+        sh = [t if t is not None else getattr(p, '_ngp_fp16', None) for t, p in zip(sh, params)]
+    if cast:
+        sh = [t if t is not None else p.detach().to(torch.half) for t, p in zip(sh, params)]
+    return sh
 
 
-def _grad_targets(bufs, n_emb, ws16, wc16, dev):
-    """where the backward kernels write: the optimizer's fp16 gradient buffers (already zero; nothing is returned to autograd) or fresh
-    tensors handed to autograd (which casts them to the fp32 .grad)"""
-    if bufs is not None:
-        return bufs[3], bufs[4].view(-1), bufs[5].view(-1), True
-    return torch.zeros(n_emb, 2, device=dev, dtype=torch.half), torch.empty_like(ws16), torch.empty_like(wc16), False
-
-
-def _optimizer_buffers(params, overwrite_table=False):
-    """(fp16 shadows..., fp16 gradient buffers...) of the three parameters when every one of them is managed by optim.NGPAdam.
-    A gradient buffer that an overwriting producer left stale (optim.NGPAdam._entries) is zeroed first -- except the table's when this
-    producer is going to overwrite it again (overwrite_table)"""
+def _operands(params, deposit, overwrite_table=False):
+    """-> Bufs of the three parameters.  `deposit` and every one of them managed by optim.NGPAdam: its fp16 shadows and fp16 gradient
+    buffers -- a buffer that an overwriting producer left stale is zeroed first (optim: the deposit hand-off), except the table's when
+    this producer is going to overwrite it again (overwrite_table).  Otherwise the fp16 operands alone: the gradients go to autograd"""
     sh = [getattr(p, '_ngp_fp16', None) for p in params]
     gr = [getattr(p, '_ngp_grad16', None) for p in params]
-    if any(t is None for t in sh + gr):
-        return None
-    _resync_stale_shadows(params)
-    for k, p in enumerate(params):
-        if getattr(p, '_ngp_grad16_stale', False) and not (overwrite_table and k == 0):
-            p._ngp_grad16.zero_()
-            p._ngp_grad16_stale = False
-    return tuple(sh) + tuple(gr)
+    if not deposit or any(t is None for t in sh + gr):
+        return Bufs(*_half_weights(params), None, None, None)
+    resync_stale_shadows(params)
+    clean_deposits(params[1:] if overwrite_table else params)
+    return Bufs(*sh, *gr)
 
 
-def _resync_stale_shadows(params):
-    """NGPAdam updates parameters and fp16 shadows together through raw pointers (no autograd version bump); any OTHER in-place write
-    to a parameter (load_state_dict, manual init) bumps `p._version` -- refresh the shadow then, instead of silently using stale weights"""
-    for p in params:
-        if getattr(p, '_ngp_fp16', None) is not None and getattr(p, '_ngp_version', None) != p._version:
-            with torch.no_grad():
-                p._ngp_fp16.copy_(p.detach())
-            p._ngp_version = p._version
+def _grad_targets(bufs, n_emb, dev):
+    """where the backward kernels write: the optimizer's fp16 gradient buffers (already zero; nothing is returned to autograd) or fresh
+    tensors handed to autograd (which casts them to the fp32 .grad)"""
+    if bufs.g_emb is not None:
+        return bufs.g_emb, bufs.g_ws.view(-1), bufs.g_wc.view(-1), True
+    return torch.zeros(n_emb, 2, device=dev, dtype=torch.half), torch.empty_like(bufs.ws16), torch.empty_like(bufs.wc16), False
 
 
 def fused_ngp(x, d, encoder, sigma_net, color_net, bound, training, density_scale=1.0):
     cfg = network_cfg(encoder, sigma_net, color_net, bound, training)
     params = (encoder.embeddings, sigma_net.weights, color_net.weights)
-    bufs = _optimizer_buffers(params) if training else None
-    if bufs is None and not training:
-        # inference: fp16 copies pinned for the duration of a render call (pinned_half_weights) or the optimizer's shadows
-        sh = [getattr(p, '_ngp_fp16_pin', None) for p in params]
-        if any(t is None for t in sh):
-            _resync_stale_shadows(params)
-            sh = [getattr(p, '_ngp_fp16', None) for p in params]
-        if all(t is not None for t in sh):
-            bufs = tuple(sh) + (None, None, None)
-    return _fused_ngp.apply(x, d, encoder.embeddings, sigma_net.weights, color_net.weights, encoder.offsets, cfg, bufs, density_scale)
+    return _fused_ngp.apply(x, d, *params, encoder.offsets, cfg, _operands(params, deposit=training), density_scale)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -236,21 +226,13 @@ def fused_ngp(x, d, encoder, sigma_net, color_net, bound, training, density_scal
 # 14 launches forward, 11 backward; same arithmetic and rounding points as the module-by-module path (tests/test_gpu_pipeline.py).
 # Only used when the sample buffer is sized from the running `mean_count` estimate (no host read-back).
 # ------------------------------------------------------------------------------------------------------------------
-def _render_train_forward(rays_o, rays_d, emb16, ws16, wc16, bg, offsets, bitfield, aabb, counter, cfg, rcfg, noise_seed=None):
-    """-> (image, depth, weights_sum, saved): the forward launches of the fused training render on the current stream"""
-    marched = _render_train_march(rays_o, rays_d, bitfield, aabb, counter, cfg, rcfg, noise_seed)
-    return _render_train_network(marched, emb16, ws16, wc16, bg, offsets, cfg, rcfg)
-
-
 def _render_train_march(rays_o, rays_d, bitfield, aabb, counter, cfg, rcfg, noise_seed=None, into=None):
-    """the parameter-independent front of the iteration: near/far + march_rays_train (one C call, three launches).  Needs neither the table nor the MLP weights, so
+    """-> Marched.  The parameter-independent front of the iteration: near/far + march_rays_train (one C call, three launches).  Needs neither the table nor the MLP weights, so
     in data-parallel training it overlaps the all-gather of the freshly updated fp16 shadows (optim.NGPAdam.gather_shadows).
-    into: the tuple an earlier call returned -- the same march issued again INTO THE SAME buffers (a second captured graph that feeds the
+    into: the Marched an earlier call returned -- the same march issued again INTO THE SAME buffers (a second captured graph that feeds the
     consumers of the first one: graph.GraphedTrainStep's folded march of the next batch)."""
-    (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, _) = cfg
-    (cascade, grid_size, min_near, capacity, perturb, dt_gamma, max_steps, T_thresh, density_scale, bg_scalar) = rcfg
     N = rays_o.shape[0]
-    M = capacity
+    M = rcfg.capacity
     dev = rays_o.device
     st = capi.stream()
     f32 = dict(device=dev, dtype=torch.float32)
@@ -265,32 +247,33 @@ def _render_train_march(rays_o, rays_d, bitfield, aabb, counter, cfg, rcfg, nois
         rays = torch.empty(N, 3, device=dev, dtype=torch.int32)
         ws = torch.empty(capi.lib.ngp_march_rays_train_workspace_bytes(N), dtype=torch.uint8, device=dev)
     march_flags = capi.NGP_MARCH_RESET_COUNTER | capi.NGP_MARCH_ZERO_TAIL | (0 if USE_FUSED_SCAN else capi.NGP_MARCH_SCAN_LAUNCH)
-    if perturb and noise_seed is not None:
+    if rcfg.perturb and noise_seed is not None:
         # start offsets drawn in-kernel from (ray index, *noise_seed): no rand launch, no generator bookkeeping in a captured graph
         noises, march_flags = noise_seed, march_flags | capi.NGP_MARCH_NOISE_FROM_SEED
     else:
-        noises = torch.rand(N, **f32) if perturb else torch.zeros(N, **f32)
+        noises = torch.rand(N, **f32) if rcfg.perturb else torch.zeros(N, **f32)
     # near_far_from_aabb rides in the marcher's first pass (nears / fars are outputs)
-    _check(capi.lib.ngp_march_rays_train_aabb(rays_o.data_ptr(), rays_d.data_ptr(), bitfield.data_ptr(), float(bound), float(dt_gamma),
-                                              max_steps, N, cascade, grid_size, M, aabb.data_ptr(), float(min_near), nears.data_ptr(),
-                                              fars.data_ptr(), xyzs.data_ptr(), dirs.data_ptr(), deltas.data_ptr(), rays.data_ptr(),
-                                              counter.data_ptr(), noises.data_ptr(), ws.data_ptr(), march_flags, st))
-    return (xyzs, dirs, deltas, rays, nears, fars, ws)
+    capi.check(capi.lib.ngp_march_rays_train_aabb(rays_o.data_ptr(), rays_d.data_ptr(), bitfield.data_ptr(), float(cfg.bound), float(rcfg.dt_gamma),
+                                                   rcfg.max_steps, N, rcfg.cascade, rcfg.grid_size, M, aabb.data_ptr(), float(rcfg.min_near),
+                                                   nears.data_ptr(), fars.data_ptr(), xyzs.data_ptr(), dirs.data_ptr(), deltas.data_ptr(),
+                                                   rays.data_ptr(), counter.data_ptr(), noises.data_ptr(), ws.data_ptr(), march_flags, st))
+    return Marched(xyzs, dirs, deltas, rays, nears, fars, ws)
 
 
-def _render_train_network(marched, emb16, ws16, wc16, bg, offsets, cfg, rcfg, composite=True):
-    (xyzs, dirs, deltas, rays, nears, fars, ws) = marched
-    (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, _) = cfg
-    (cascade, grid_size, min_near, capacity, perturb, dt_gamma, max_steps, T_thresh, density_scale, bg_scalar) = rcfg
-    N, M = rays.shape[0], capacity
+def _render_train_network(marched, bufs, bg, offsets, cfg, rcfg, composite=True):
+    """encode + network on the marched samples and -- `composite` -- composite_rays_train with the renderer's epilogue.
+    -> (image, depth, weights_sum, Saved), or the Saved alone (its composite outputs None) when the caller composites itself"""
+    xyzs, rays = marched.xyzs, marched.rays
+    nl_sigma, nl_color = cfg.nl_sigma, cfg.nl_color
+    N, M = rays.shape[0], rcfg.capacity
     dev = xyzs.device
     st = capi.stream()
     f32 = dict(device=dev, dtype=torch.float32)
     half = dict(device=dev, dtype=torch.half)
     # ---- network ----
-    enc = torch.empty(L, M, 2, **half)
-    _grid_forward(xyzs, emb16, offsets, enc, M, L, S, H, gridtype, align, interp, bound,
-                  capi.ray_level_costs(L, S, H, 3.0 ** 0.5 / (max_steps * max(float(bound), 1e-6))) if USE_BALANCED_FORWARD else None, st)
+    enc = torch.empty(cfg.L, M, 2, **half)
+    costs = capi.ray_level_costs(cfg.L, cfg.S, cfg.H, 3.0 ** 0.5 / (rcfg.max_steps * max(float(cfg.bound), 1e-6))) if USE_BALANCED_FORWARD else None
+    _grid_forward(xyzs, bufs.emb16, offsets, enc, M, cfg.L, cfg.S, cfg.H, cfg.gridtype, cfg.align, cfg.interp, cfg.bound, costs, st)
     h16 = torch.empty(M, 16, **half)
     color_in = torch.empty(M, 32, **half)
     out16 = torch.empty(M, 16, **half)
@@ -301,9 +284,12 @@ def _render_train_network(marched, emb16, ws16, wc16, bg, offsets, cfg, rcfg, co
     else:
         fb_s = torch.empty(nl_sigma, M, 64, **half)
         fb_c = torch.empty(nl_color, M, 64, **half)
-    _network_forward(enc, dirs, M, ws16, wc16, nl_sigma, nl_color, float(density_scale), True, fb_s, h16, sigma, color_in, fb_c, out16, rgb, M, st)
+    _network_forward(enc, marched.dirs, M, bufs.ws16, bufs.wc16, nl_sigma, nl_color, float(rcfg.density_scale), True, fb_s, h16, sigma, color_in, fb_c,
+                     out16, rgb, M, st)
+    saved = Saved(xyzs, offsets, enc, bufs.ws16, bufs.wc16, fb_s, fb_c, h16, color_in, rgb, sigma, marched.deltas, rays, weights_sum=None,
+                  image_raw=None, bg=bg, march_ws=marched.ws)
     if not composite:
-        return (xyzs, offsets, enc, ws16, wc16, fb_s, fb_c, h16, color_in, rgb, sigma, deltas, rays, None, None, bg, ws)
+        return saved
     # ---- composite + epilogue ----
     weights_sum = torch.empty(N, **f32)
     depth_raw = torch.empty(N, **f32)
@@ -311,33 +297,30 @@ def _render_train_network(marched, emb16, ws16, wc16, bg, offsets, cfg, rcfg, co
     image = torch.empty(N, 3, **f32)
     depth = torch.empty(N, **f32)
     bg_mode = 2 if bg is not None else 1
-    _check(capi.lib.ngp_composite_rays_train_forward_ex(sigma.data_ptr(), rgb.data_ptr(), deltas.data_ptr(), rays.data_ptr(), M, N,
-                                                        float(T_thresh), weights_sum.data_ptr(), depth_raw.data_ptr(), image_raw.data_ptr(),
-                                                        bg_mode, float(bg_scalar), capi.ptr(bg), nears.data_ptr(), fars.data_ptr(),
-                                                        image.data_ptr(), depth.data_ptr(), st))
-    saved = (xyzs, offsets, enc, ws16, wc16, fb_s, fb_c, h16, color_in, rgb, sigma, deltas, rays, weights_sum, image_raw, bg, ws)
-    return image, depth, weights_sum, saved
+    capi.check(capi.lib.ngp_composite_rays_train_forward_ex(sigma.data_ptr(), rgb.data_ptr(), marched.deltas.data_ptr(), rays.data_ptr(), M, N,
+                                                             float(rcfg.T_thresh), weights_sum.data_ptr(), depth_raw.data_ptr(), image_raw.data_ptr(),
+                                                             bg_mode, float(rcfg.bg_scalar), capi.ptr(bg), marched.nears.data_ptr(),
+                                                             marched.fars.data_ptr(), image.data_ptr(), depth.data_ptr(), st))
+    return image, depth, weights_sum, saved._replace(weights_sum=weights_sum, image_raw=image_raw)
 
 
 def _render_train_backward(saved, cfg, rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc, found_inf=None, overwrite=False):
     """the backward launches: grad_image [N,3] fp32 (and optionally grad_ws [N]) -> gradients accumulated into g_emb (scatter-add, must
     hold the running sum / zeros) and written to g_ws / g_wc (fp16, flat)"""
-    (xyzs, offsets, enc, ws16, wc16, fb_s, fb_c, h16, color_in, rgb, sigma, deltas, rays, weights_sum, image_raw, bg, march_ws) = saved
-    (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, _) = cfg
-    (cascade, grid_size, min_near, capacity, perturb, dt_gamma, max_steps, T_thresh, density_scale, bg_scalar) = rcfg
-    M, N = xyzs.shape[0], rays.shape[0]
-    dev = xyzs.device
+    s = saved
+    M, N = s.xyzs.shape[0], s.rays.shape[0]
+    dev = s.xyzs.device
     st = capi.stream()
-    half = dict(device=dev, dtype=torch.half)
     g_sigma = torch.empty(M, device=dev)  # rows without a gradient are zeroed by the compositor (rows_used = first word of the march workspace)
     g_rgb = torch.empty(M, 3, device=dev)
-    bg_mode = 2 if bg is not None else 1
-    _check(capi.lib.ngp_composite_rays_train_backward_ex(capi.ptr(grad_ws), grad_image.data_ptr(), sigma.data_ptr(), rgb.data_ptr(),
-                                                         deltas.data_ptr(), rays.data_ptr(), weights_sum.data_ptr(), image_raw.data_ptr(),
-                                                         M, N, float(T_thresh), g_sigma.data_ptr(), g_rgb.data_ptr(), bg_mode,
-                                                         float(bg_scalar), capi.ptr(bg), march_ws.data_ptr(), st))
-    g_out16 = torch.empty(M, 16, **half)
-    _check(capi.lib.ngp_pipeline_rgb_backward(g_rgb.data_ptr(), rgb.data_ptr(), g_out16.data_ptr(), M, st))
+    bg_mode = 2 if s.bg is not None else 1
+    capi.check(capi.lib.ngp_composite_rays_train_backward_ex(capi.ptr(grad_ws), grad_image.data_ptr(), s.sigma.data_ptr(), s.rgb.data_ptr(),
+                                                              s.deltas.data_ptr(), s.rays.data_ptr(), s.weights_sum.data_ptr(),
+                                                              s.image_raw.data_ptr(), M, N, float(rcfg.T_thresh), g_sigma.data_ptr(),
+                                                              g_rgb.data_ptr(), bg_mode, float(rcfg.bg_scalar), capi.ptr(s.bg),
+                                                              s.march_ws.data_ptr(), st))
+    g_out16 = torch.empty(M, 16, device=dev, dtype=torch.half)
+    capi.check(capi.lib.ngp_pipeline_rgb_backward(g_rgb.data_ptr(), s.rgb.data_ptr(), g_out16.data_ptr(), M, st))
     _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf, None, overwrite)
 
 
@@ -345,38 +328,38 @@ def _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, fou
     """colour MLP -> exp / feature shuffle -> sigma MLP -> grid scatter, from g_sigma [M] fp32 and g_out16 [M,16] fp16 (CONSUMED: reused as
     the sigma net's output gradient).  loss_job = (ray_err [N], loss [1]): the loss sum the compositor left to a later launch -- only
     accepted where `_carries_reductions` holds (it rides with the slab reduction in the grid backward's last launch)"""
-    (xyzs, offsets, enc, ws16, wc16, fb_s, fb_c, h16, color_in, rgb, sigma, deltas, rays, weights_sum, image_raw, bg, march_ws) = saved
-    (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, _) = cfg
-    density_scale = rcfg[8]
-    M = xyzs.shape[0]
+    s = saved
+    nl_sigma, nl_color, density_scale = cfg.nl_sigma, cfg.nl_color, rcfg.density_scale
+    grid = (cfg.L, cfg.S, cfg.H, cfg.gridtype, cfg.align, cfg.interp, cfg.bound)
+    M = s.xyzs.shape[0]
     st = capi.stream()
-    half = dict(device=xyzs.device, dtype=torch.half)
-    g_enc = torch.empty(L, M, 2, **half)
+    half = dict(device=s.xyzs.device, dtype=torch.half)
+    g_enc = torch.empty(cfg.L, M, 2, **half)
     if USE_FUSED_MID and nl_color in (2, 3) and nl_sigma in (2, 3):
         # the colour head writes the sigma net's output gradient itself (exp backward + feature shuffle in its epilogue) and both
         # networks' weight-gradient slabs are summed by ONE launch at the end: 3 launches instead of 5
         scratch_c = torch.empty(nl_color, M, 64, **half)
         scratch_s = torch.empty(nl_sigma, M, 64, **half)
         g_h16 = torch.empty(M, 16, **half)
-        rc = capi.NGP_FF_RECOMPUTE if fb_c is None else 0
-        _check(capi.lib.ngp_network_backward_color(g_out16.data_ptr(), color_in.data_ptr(), wc16.data_ptr(), capi.ptr(fb_c), M, nl_color,
-                                                   scratch_c.data_ptr(), g_sigma.data_ptr(), h16.data_ptr(), float(density_scale),
-                                                   g_h16.data_ptr(), g_wc.data_ptr(), capi.NGP_FF_DEFER_REDUCE | rc, st))
-        _check(capi.lib.ngp_ffmlp_backward_ex(g_h16.data_ptr(), enc.data_ptr(), ws16.data_ptr(), capi.ptr(fb_s), M, 32, 16, 64, nl_sigma,
-                                              0, 6, 1, scratch_s.data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(),
-                                              _PLANAR_IN | _PLANAR_DX | capi.NGP_FF_DEFER_REDUCE | rc, st))
+        rc = capi.NGP_FF_RECOMPUTE if s.fb_c is None else 0
+        capi.check(capi.lib.ngp_network_backward_color(g_out16.data_ptr(), s.color_in.data_ptr(), s.wc16.data_ptr(), capi.ptr(s.fb_c), M, nl_color,
+                                                        scratch_c.data_ptr(), g_sigma.data_ptr(), s.h16.data_ptr(), float(density_scale),
+                                                        g_h16.data_ptr(), g_wc.data_ptr(), capi.NGP_FF_DEFER_REDUCE | rc, st))
+        capi.check(capi.lib.ngp_ffmlp_backward_ex(g_h16.data_ptr(), s.enc.data_ptr(), s.ws16.data_ptr(), capi.ptr(s.fb_s), M, 32, 16, 64, nl_sigma,
+                                                   0, 6, 1, scratch_s.data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(),
+                                                   _PLANAR_IN | _PLANAR_DX | capi.NGP_FF_DEFER_REDUCE | rc, st))
         n_c, n_s = capi.lib.ngp_ffmlp_backward_slab_count(M, 32, 64, nl_color), capi.lib.ngp_ffmlp_backward_slab_count(M, 32, 64, nl_sigma)
         if USE_SLABS_IN_ACCUMULATE:
             # the slab reduction of both MLPs (and the loss sum) ride in the grid backward's last launch (independent work, one launch less)
             err, loss = loss_job if loss_job is not None else (None, None)
             slabs = capi.SlabSets(scratch_c.data_ptr(), n_c, g_wc.numel(), g_wc.data_ptr(), scratch_s.data_ptr(), n_s, g_ws.numel(), g_ws.data_ptr(),
                                   capi.ptr(err), 0 if err is None else err.numel(), capi.ptr(loss))
-            _grid_backward(g_enc, xyzs, offsets, g_emb, M, L, S, H, gridtype, align, interp, bound, st, found_inf, slabs, overwrite, table_adam)
+            _grid_backward(g_enc, s.xyzs, s.offsets, g_emb, M, *grid, st, found_inf, slabs, overwrite, table_adam)
             return
         if loss_job is not None:
             raise RuntimeError('fused: a deferred loss sum needs the carried reductions (_carries_reductions)')
-        _check(capi.lib.ngp_ffmlp_reduce_slabs_pair(scratch_c.data_ptr(), n_c, g_wc.numel(), g_wc.data_ptr(), scratch_s.data_ptr(), n_s, g_ws.numel(),
-                                                    g_ws.data_ptr(), capi.ptr(found_inf), st))
+        capi.check(capi.lib.ngp_ffmlp_reduce_slabs_pair(scratch_c.data_ptr(), n_c, g_wc.numel(), g_wc.data_ptr(), scratch_s.data_ptr(), n_s, g_ws.numel(),
+                                                         g_ws.data_ptr(), capi.ptr(found_inf), st))
     else:
         if found_inf is not None:
             raise RuntimeError('fused: found_inf needs the fused colour-head / slab-reduction path (see iteration_checks_gradients)')
@@ -384,23 +367,23 @@ def _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, fou
             raise RuntimeError('fused: a deferred loss sum needs the carried reductions (_carries_reductions)')
         g_color_in = torch.empty(M, 32, **half)
         scratch = torch.empty(max(nl_color, nl_sigma), M, 64, **half)
-        _check(capi.lib.ngp_ffmlp_backward_ex(g_out16.data_ptr(), color_in.data_ptr(), wc16.data_ptr(), fb_c.data_ptr(), M, 32, 16, 64,
-                                              nl_color, 0, 6, 1, scratch.data_ptr(), g_color_in.data_ptr(), g_wc.data_ptr(), 0, st))
+        capi.check(capi.lib.ngp_ffmlp_backward_ex(g_out16.data_ptr(), s.color_in.data_ptr(), s.wc16.data_ptr(), s.fb_c.data_ptr(), M, 32, 16, 64,
+                                                   nl_color, 0, 6, 1, scratch.data_ptr(), g_color_in.data_ptr(), g_wc.data_ptr(), 0, st))
         g_h16 = g_out16
-        _check(capi.lib.ngp_pipeline_mid_backward(g_sigma.data_ptr(), h16.data_ptr(), g_color_in.data_ptr(), g_h16.data_ptr(), M,
-                                                  float(density_scale), st))
-        _check(capi.lib.ngp_ffmlp_backward_ex(g_h16.data_ptr(), enc.data_ptr(), ws16.data_ptr(), fb_s.data_ptr(), M, 32, 16, 64, nl_sigma,
-                                              0, 6, 1, scratch[:nl_sigma].data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(),
-                                              _PLANAR_IN | _PLANAR_DX, st))
-    _grid_backward(g_enc, xyzs, offsets, g_emb, M, L, S, H, gridtype, align, interp, bound, st, found_inf, None, overwrite, table_adam)
+        capi.check(capi.lib.ngp_pipeline_mid_backward(g_sigma.data_ptr(), s.h16.data_ptr(), g_color_in.data_ptr(), g_h16.data_ptr(), M,
+                                                       float(density_scale), st))
+        capi.check(capi.lib.ngp_ffmlp_backward_ex(g_h16.data_ptr(), s.enc.data_ptr(), s.ws16.data_ptr(), s.fb_s.data_ptr(), M, 32, 16, 64, nl_sigma,
+                                                   0, 6, 1, scratch[:nl_sigma].data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(),
+                                                   _PLANAR_IN | _PLANAR_DX, st))
+    _grid_backward(g_enc, s.xyzs, s.offsets, g_emb, M, *grid, st, found_inf, None, overwrite, table_adam)
 
 
 class _fused_render_train(Function):
     @staticmethod
     def forward(ctx, rays_o, rays_d, embeddings, w_sigma, w_color, bg, offsets, bitfield, aabb, counter, cfg, rcfg, bufs):
-        emb16, ws16, wc16 = _half_weights(embeddings, w_sigma, w_color, bufs)
-        image, depth, weights_sum, saved = _render_train_forward(rays_o, rays_d, emb16, ws16, wc16, bg, offsets, bitfield, aabb, counter,
-                                                                 cfg, rcfg)
+        # (the forward launches of the fused training render on the current stream)
+        marched = _render_train_march(rays_o, rays_d, bitfield, aabb, counter, cfg, rcfg)
+        image, depth, weights_sum, saved = _render_train_network(marched, bufs, bg, offsets, cfg, rcfg)
         ctx.save_for_backward(*saved)
         ctx.cfg, ctx.rcfg, ctx.n_emb, ctx.bufs = cfg, rcfg, embeddings.shape[0], bufs
         ctx.mark_non_differentiable(depth)
@@ -408,12 +391,12 @@ class _fused_render_train(Function):
 
     @staticmethod
     def backward(ctx, grad_image, grad_depth, grad_ws):
-        saved = ctx.saved_tensors
-        dev = saved[0].device
-        N = saved[12].shape[0]  # rays
+        saved = Saved(*ctx.saved_tensors)
+        dev = saved.xyzs.device
+        N = saved.rays.shape[0]
         grad_image = torch.zeros(N, 3, device=dev) if grad_image is None else grad_image.contiguous().float()
         grad_ws = None if grad_ws is None else grad_ws.contiguous().float()
-        g_emb, g_ws, g_wc, deposited = _grad_targets(ctx.bufs, ctx.n_emb, saved[3], saved[4], dev)
+        g_emb, g_ws, g_wc, deposited = _grad_targets(ctx.bufs, ctx.n_emb, dev)
         _render_train_backward(saved, ctx.cfg, ctx.rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc)
         if deposited:
             return (None,) * 13
@@ -421,24 +404,24 @@ class _fused_render_train(Function):
 
 
 def network_cfg(encoder, sigma_net, color_net, bound, training):
-    return (float(bound), int(encoder.num_levels), float(np.log2(encoder.per_level_scale)), int(encoder.base_resolution),
-            int(encoder.gridtype_id), int(bool(encoder.align_corners)), int(encoder.interp_id), int(sigma_net.num_layers),
-            int(color_net.num_layers), bool(training))
+    return NetCfg(float(bound), int(encoder.num_levels), float(np.log2(encoder.per_level_scale)), int(encoder.base_resolution),
+                  int(encoder.gridtype_id), int(bool(encoder.align_corners)), int(encoder.interp_id), int(sigma_net.num_layers),
+                  int(color_net.num_layers), bool(training))
 
 
 def fused_render_train(model, rays_o, rays_d, box, counter, capacity, bg_color, perturb, dt_gamma, max_steps, T_thresh):
     """-> image [N,3], depth [N], weights_sum [N]; `counter` [2] int32 receives (samples marched, rays)"""
     cfg = network_cfg(model.encoder, model.sigma_net, model.color_net, model.bound, True)
     bg_t, rcfg = _render_cfg(model, capacity, bg_color, perturb, dt_gamma, max_steps, T_thresh)
-    bufs = _optimizer_buffers((model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights))
-    return _fused_render_train.apply(rays_o, rays_d, model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights, bg_t,
-                                     model.encoder.offsets, model.density_bitfield, box, counter, cfg, rcfg, bufs)
+    params = (model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights)
+    return _fused_render_train.apply(rays_o, rays_d, *params, bg_t, model.encoder.offsets, model.density_bitfield, box, counter, cfg, rcfg,
+                                     _operands(params, deposit=True))
 
 
 def _render_cfg(model, capacity, bg_color, perturb, dt_gamma, max_steps, T_thresh):
     bg_t, bg_s = (bg_color.contiguous().float().view(-1, 3), 0.0) if torch.is_tensor(bg_color) else (None, float(bg_color))
-    rcfg = (int(model.cascade), int(model.grid_size), float(model.min_near), int(capacity), bool(perturb), float(dt_gamma), int(max_steps),
-            float(T_thresh), float(model.density_scale), bg_s)
+    rcfg = RenderCfg(int(model.cascade), int(model.grid_size), float(model.min_near), int(capacity), bool(perturb), float(dt_gamma),
+                     int(max_steps), float(T_thresh), float(model.density_scale), bg_s)
     return bg_t, rcfg
 
 
@@ -455,43 +438,27 @@ def fused_train_iteration(model, rays_o, rays_d, target, box, counter, capacity,
     overwrite_table: the table's deposit buffer RECEIVES this iteration's gradient (every entry written, nothing added, nothing read) and
     the next optimizer step keeps the buffer instead of zeroing it (optim.NGPAdam reads the flag this call leaves on the parameter) --
     for a loop that steps the optimizer after every iteration (graph.GraphedTrainStep); gradients do not accumulate across calls in
-    this mode, and producers that add (the autograd paths) find the buffer zeroed first (`_optimizer_buffers`).
+    this mode, and producers that add (the autograd paths) find the buffer zeroed first (`_operands`).
     table_adam: an optim.NGPAdam on which `enable_table_fusion(model.encoder.embeddings)` was called -- the grid backward's slice accumulate
     applies Adam to the table in its flush (speculative double buffer, include/ngp_hip.h ngp_table_adam_t) and the optimizer's next
     `step(gradients_checked=True)` is one small launch (Adam on the MLP weights, commit, parity flip).  Needs overwrite_table, found_inf
     and a batch of >= 16 384 samples (else the C entry refuses before launching anything).
     -> (loss [1] fp32, image [N,3], depth [N], weights_sum [N]); same arithmetic as model.render + mse_loss + scaled backward
     (tests/test_gpu_graph.py)."""
-    cfg = network_cfg(model.encoder, model.sigma_net, model.color_net, model.bound, True)
-    bg_t, rcfg = _render_cfg(model, capacity, bg_color, perturb, dt_gamma, max_steps, T_thresh)
-    bufs = _optimizer_buffers((model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights), overwrite_table)
-    if bufs is None:
-        raise RuntimeError('fused_train_iteration: the parameters are not managed by optim.NGPAdam(deposit=True)')
-    rays_o = rays_o.contiguous().view(-1, 3)
-    rays_d = rays_d.contiguous().view(-1, 3)
-    target = target.contiguous().view(-1, 3)
-    if target.shape[0] != rays_o.shape[0] or target.dtype != torch.float32:
-        raise RuntimeError('fused_train_iteration: target must be [N,3] float32')
-    marched = _render_train_march(rays_o, rays_d, model.density_bitfield, box, counter, cfg, rcfg, noise_seed)
-    ta = _table_adam_of(table_adam, model)
-    out = _train_iteration_rest(marched, bufs, bg_t, model.encoder.offsets, target, loss_scale, cfg, rcfg, found_inf, overwrite_table, ta)
-    if overwrite_table:
-        model.encoder.embeddings._ngp_deposit_overwritten = True   # read (and reset) by the optimizer's next step: it keeps the buffer
-    if ta is not None:
-        _mark_table_adam(model, cfg, capacity)                     # ... and does not sweep the table: this iteration's backward did
-    return out
+    march, rest = fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, capacity, loss_scale, bg_color, perturb, dt_gamma,
+                                              max_steps, T_thresh, noise_seed, found_inf, overwrite_table, table_adam)
+    march()
+    return rest()
 
 
-def _mark_table_adam(model, cfg, M):
-    """tell the optimizer's next step() that the grid backward swept the table -- except the dense-level prefix (entries), which it does"""
-    (bound, L, S, H, gridtype, align, interp, nl_sigma, nl_color, _) = cfg
-    emb = model.encoder.embeddings
+def _table_adam_prefix(model, cfg, M):
+    """the dense-level entries at the start of the table that the grid backward's Adam sweep leaves to the optimizer's next step()"""
     arr = capi.host_offsets(model.encoder.offsets)
-    prefix = int(capi.lib.ngp_grid_table_adam_prefix(ctypes.cast(arr, ctypes.c_void_p), int(M), 3, 2, L, S, H, gridtype, align, capi.NGP_F16))
+    prefix = int(capi.lib.ngp_grid_table_adam_prefix(ctypes.cast(arr, ctypes.c_void_p), int(M), 3, 2, cfg.L, cfg.S, cfg.H, cfg.gridtype, cfg.align,
+                                                     capi.NGP_F16))
     if prefix == 0xffffffff:
         raise RuntimeError('fused: table_adam: this batch / table shape cannot carry the sweep (ngp_grid_table_adam_prefix)')
-    emb._ngp_table_adam_prefix = prefix
-    emb._ngp_table_adam_done = True
+    return prefix
 
 
 def _table_adam_of(optimizer, model):
@@ -541,19 +508,17 @@ def iteration_checks_gradients(model):
 def _train_iteration_rest(marched, bufs, bg_t, offsets, target, loss_scale, cfg, rcfg, found_inf=None, overwrite=False, table_adam=None):
     if table_adam is not None and not (USE_FUSED_COMPOSITE and found_inf is not None and overwrite):
         raise RuntimeError('fused: table_adam needs the fused compositor, the in-kernel non-finite sweep (found_inf) and overwrite_table')
+    g_emb, g_ws, g_wc = bufs.g_emb, bufs.g_ws.view(-1), bufs.g_wc.view(-1)
     if not USE_FUSED_COMPOSITE:
-        image, depth, weights_sum, saved = _render_train_network(marched, bufs[0], bufs[1], bufs[2], bg_t, offsets, cfg, rcfg)
+        image, depth, weights_sum, saved = _render_train_network(marched, bufs, bg_t, offsets, cfg, rcfg)
         loss = torch.empty(1, device=image.device, dtype=torch.float32)
         grad_image = torch.empty_like(image)
-        _check(capi.lib.ngp_pipeline_mse_loss(image.data_ptr(), target.data_ptr(), image.numel(), capi.ptr(loss_scale), loss.data_ptr(),
-                                              grad_image.data_ptr(), capi.stream()))
-        _render_train_backward(saved, cfg, rcfg, grad_image, None, bufs[3], bufs[4].view(-1), bufs[5].view(-1), found_inf, overwrite)
+        capi.check(capi.lib.ngp_pipeline_mse_loss(image.data_ptr(), target.data_ptr(), image.numel(), capi.ptr(loss_scale), loss.data_ptr(),
+                                                   grad_image.data_ptr(), capi.stream()))
+        _render_train_backward(saved, cfg, rcfg, grad_image, None, g_emb, g_ws, g_wc, found_inf, overwrite)
         return loss, image, depth, weights_sum
-    saved = _render_train_network(marched, bufs[0], bufs[1], bufs[2], bg_t, offsets, cfg, rcfg, composite=False)
-    (xyzs, _, _, _, _, _, _, _, _, rgb, sigma, deltas, rays, _, _, bg, march_ws) = saved
-    (_, _, _, _, _, _, _, T_thresh, _, bg_scalar) = rcfg
-    nears, fars = marched[4], marched[5]
-    N, M, dev = rays.shape[0], xyzs.shape[0], xyzs.device
+    s = _render_train_network(marched, bufs, bg_t, offsets, cfg, rcfg, composite=False)
+    N, M, dev = s.rays.shape[0], s.xyzs.shape[0], s.xyzs.device
     f32 = dict(device=dev, dtype=torch.float32)
     weights_sum, image, depth = torch.empty(N, **f32), torch.empty(N, 3, **f32), torch.empty(N, **f32)
     loss, ray_err = torch.empty(1, **f32), torch.empty(N, **f32)
@@ -561,15 +526,16 @@ def _train_iteration_rest(marched, bufs, bg_t, offsets, target, loss_scale, cfg,
     g_out16 = torch.empty(M, 16, device=dev, dtype=torch.half)
     # the loss VALUE: summed by the compositor's last workgroup (a ticket round trip at the end of every workgroup), or left to the launch
     # that carries the slab reduction (same routine, same bits: the compositor then ends without tickets)
-    defer = _carries_reductions(cfg[7], cfg[8])
-    _check(capi.lib.ngp_composite_train_loss_backward(sigma.data_ptr(), rgb.data_ptr(), deltas.data_ptr(), rays.data_ptr(), M, N,
-                                                      float(T_thresh), 2 if bg is not None else 1, float(bg_scalar), capi.ptr(bg),
-                                                      nears.data_ptr(), fars.data_ptr(), target.data_ptr(), capi.ptr(loss_scale),
-                                                      weights_sum.data_ptr(), image.data_ptr(), depth.data_ptr(), None if defer else loss.data_ptr(),
-                                                      ray_err.data_ptr(), g_sigma.data_ptr(), g_out16.data_ptr(), march_ws.data_ptr(),
-                                                      march_ws.numel() * march_ws.element_size(), capi.stream()))
-    _network_backward(saved, cfg, rcfg, g_sigma, g_out16, bufs[3], bufs[4].view(-1), bufs[5].view(-1), found_inf,
-                      loss_job=(ray_err, loss) if defer else None, overwrite=overwrite, table_adam=table_adam)
+    defer = _carries_reductions(cfg.nl_sigma, cfg.nl_color)
+    capi.check(capi.lib.ngp_composite_train_loss_backward(s.sigma.data_ptr(), s.rgb.data_ptr(), s.deltas.data_ptr(), s.rays.data_ptr(), M, N,
+                                                           float(rcfg.T_thresh), 2 if s.bg is not None else 1, float(rcfg.bg_scalar), capi.ptr(s.bg),
+                                                           marched.nears.data_ptr(), marched.fars.data_ptr(), target.data_ptr(),
+                                                           capi.ptr(loss_scale), weights_sum.data_ptr(), image.data_ptr(), depth.data_ptr(),
+                                                           None if defer else loss.data_ptr(), ray_err.data_ptr(), g_sigma.data_ptr(),
+                                                           g_out16.data_ptr(), s.march_ws.data_ptr(),
+                                                           s.march_ws.numel() * s.march_ws.element_size(), capi.stream()))
+    _network_backward(s, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf, loss_job=(ray_err, loss) if defer else None,
+                      overwrite=overwrite, table_adam=table_adam)
     return loss, image, depth, weights_sum
 
 
@@ -579,15 +545,17 @@ def fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, cap
     """`fused_train_iteration` in two halves for data-parallel training: returns (march, rest) callables -- `march()` issues the
     parameter-independent launches (near/far, ray marching), `rest()` everything that reads the weights (encode, MLPs, composite, loss,
     backward).  graph.GraphedTrainStep captures them into separate HIP graphs so that the all-gather of the updated fp16 shadow weights
-    (optim.NGPAdam, sharded mode) runs underneath the marcher.  Same launches, same arithmetic as the unsplit call."""
+    (optim.NGPAdam, sharded mode) runs underneath the marcher.  The unsplit call is `march(); return rest()` of this one."""
     cfg = network_cfg(model.encoder, model.sigma_net, model.color_net, model.bound, True)
     bg_t, rcfg = _render_cfg(model, capacity, bg_color, perturb, dt_gamma, max_steps, T_thresh)
-    bufs = _optimizer_buffers((model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights), overwrite_table)
-    if bufs is None:
+    bufs = _operands((model.encoder.embeddings, model.sigma_net.weights, model.color_net.weights), True, overwrite_table)
+    if bufs.g_emb is None:
         raise RuntimeError('fused_train_iteration: the parameters are not managed by optim.NGPAdam(deposit=True)')
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)
     target = target.contiguous().view(-1, 3)
+    if target.shape[0] != rays_o.shape[0] or target.dtype != torch.float32:
+        raise RuntimeError('fused_train_iteration: target must be [N,3] float32')
     box_ = {}
 
     def march():   # (called again -- a second captured graph -- it marches into the SAME buffers, the ones rest() reads)
@@ -597,9 +565,9 @@ def fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, cap
         ta = _table_adam_of(table_adam, model)
         out = _train_iteration_rest(box_['m'], bufs, bg_t, model.encoder.offsets, target, loss_scale, cfg, rcfg, found_inf, overwrite_table, ta)
         if overwrite_table:
-            model.encoder.embeddings._ngp_deposit_overwritten = True
-        if ta is not None:
-            _mark_table_adam(model, cfg, capacity)
+            # read (and reset) by the optimizer's next step: it keeps the buffer -- and, where this iteration's backward swept the table with
+            # Adam, applies Adam to the dense-level prefix only
+            announce_overwrite(model.encoder.embeddings, None if ta is None else _table_adam_prefix(model, cfg, capacity))
         return out
     return march, rest
 
@@ -619,15 +587,7 @@ def fused_density(x, encoder, sigma_net, bound):
     M = x.shape[0]
     dev = x.device
     st = capi.stream()
-    emb = encoder.embeddings
-    w = sigma_net.weights
-    _resync_stale_shadows((emb, w))
-    emb16 = getattr(emb, '_ngp_fp16_pin', None)
-    emb16 = emb16 if emb16 is not None else getattr(emb, '_ngp_fp16', None)
-    emb16 = emb16 if emb16 is not None else emb.detach().to(torch.half)
-    w16 = getattr(w, '_ngp_fp16_pin', None)
-    w16 = w16 if w16 is not None else getattr(w, '_ngp_fp16', None)
-    w16 = w16 if w16 is not None else w.detach().to(torch.half)
+    emb16, w16 = _half_weights((encoder.embeddings, sigma_net.weights))
     L = int(encoder.num_levels)
     enc = torch.empty(L, M, 2, device=dev, dtype=torch.half)
     S, H = float(np.log2(encoder.per_level_scale)), int(encoder.base_resolution)
@@ -635,8 +595,8 @@ def fused_density(x, encoder, sigma_net, bound):
     _grid_forward(x.contiguous(), emb16, encoder.offsets, enc, M, L, S, H, int(encoder.gridtype_id), int(bool(encoder.align_corners)),
                   int(encoder.interp_id), bound, costs, st)
     h16 = torch.empty(M, 16, device=dev, dtype=torch.half)
-    _check(capi.lib.ngp_ffmlp_inference_ex(enc.data_ptr(), w16.data_ptr(), M, 32, 16, 64, int(sigma_net.num_layers), 0, 6, None, h16.data_ptr(),
-                                           _PLANAR_IN, st))
+    capi.check(capi.lib.ngp_ffmlp_inference_ex(enc.data_ptr(), w16.data_ptr(), M, 32, 16, 64, int(sigma_net.num_layers), 0, 6, None, h16.data_ptr(),
+                                                _PLANAR_IN, st))
     return torch.exp(h16[:, 0].float()), h16[:, 1:]
 
 
@@ -650,14 +610,10 @@ def inference_weights(model, x):
     probe = torch.empty(128, 3, device=x.device, dtype=torch.float32)
     if not getattr(model, '_fused_ok', lambda *_: False)(probe, probe):
         return None
-    params = (enc.embeddings, sn.weights, cn.weights)
-    sh = [getattr(p, '_ngp_fp16_pin', None) for p in params]
-    if any(t is None for t in sh):
-        _resync_stale_shadows(params)
-        sh = [getattr(p, '_ngp_fp16', None) for p in params]
-    if any(t is None for t in sh) or getattr(sh[0], '_ngp_sel', None) is not None:
+    emb16, ws16, wc16 = _half_weights((enc.embeddings, sn.weights, cn.weights), cast=False)
+    if emb16 is None or ws16 is None or wc16 is None or getattr(emb16, '_ngp_sel', None) is not None:
         return None
-    return sh[0], sh[1], sh[2], network_cfg(enc, sn, cn, model.bound, False)
+    return emb16, ws16, wc16, network_cfg(enc, sn, cn, model.bound, False)
 
 
 class pinned_half_weights:

@@ -251,10 +251,6 @@ class GraphedTrainStep:
         if fn is not None:
             fn()
 
-    def _table_adam(self):
-        """the optimizer to hand to the fused iteration as `table_adam` (None: the separate Adam sweep)"""
-        return self.optimizer if self.table_fused else None
-
     def _overwrites_table(self):
         """single-GPU direct iteration: the grid backward WRITES the table gradient and the optimizer keeps the buffer (no zeroing, no
         read of the old value: 49 MB per step).  Not with an averager / sharded exchange (they own the flat buffer's life cycle)."""
@@ -268,11 +264,9 @@ class GraphedTrainStep:
         """after a replay: what the captured optimizer step left in the table's deposit buffer (Python ran only at capture time)"""
         emb = getattr(getattr(self.model, 'encoder', None), 'embeddings', None)
         if emb is not None and self.used_direct and self._overwrites_table():
-            emb._ngp_grad16_stale = True
-            if self.averager is not None:   # sharded update without the memset: every deposit buffer is left as its producer wrote it
-                for p in getattr(self.optimizer, 'flat_params', []):
-                    if getattr(p, '_ngp_grad16', None) is not None:
-                        p._ngp_grad16_stale = True
+            from optim import replayed_kept_deposits
+            # (sharded update without the memset: every deposit buffer is left as its producer wrote it)
+            replayed_kept_deposits([emb] if self.averager is None else [emb] + list(getattr(self.optimizer, 'flat_params', [])))
 
     def _clean_deposits(self):
         """before replaying graphs whose producers ADD into the deposit buffers: zero what an overwriting producer left behind"""
@@ -291,24 +285,33 @@ class GraphedTrainStep:
             return m._fused_render_ok(self.rays_o.view(-1, 3), self.rays_d.view(-1, 3), 1 if bg is None else bg,
                                       kw.get('force_all_rays', False))
 
+    def _iteration_args(self, checked, p=None):
+        """(args, kwargs) of fused.fused_train_iteration / fused_train_iteration_split on the static buffers -- of buffer set `p` of the
+        lookahead (its own counter row and noise seed), else of the single set (seeded by the optimizer's step count).
+        checked: the producers flag non-finite gradients themselves -- and carry the table's Adam sweep when the graphs were captured for it
+        (table_fused; the optimizer is then handed over as `table_adam`, else its separate sweep runs)"""
+        m, kw, opt = self.model, self.render_kwargs, self.optimizer
+        bg = kw.get('bg_color', None)
+        if p is None:
+            batch, counter, seed = (self.rays_o, self.rays_d, self.target), self.counter[0], opt.scalars[3:4]
+        else:
+            batch, counter, seed = (self.la_rays_o[p], self.la_rays_d[p], self.la_target[p]), self.counter[p], self.la_seed[p:p + 1]
+        args = (m, *batch, m.aabb_train, counter, self.captured_capacity, opt.scalars[0:1], 1 if bg is None else bg, kw.get('perturb', False),
+                kw.get('dt_gamma', 0), kw.get('max_steps', 1024), kw.get('T_thresh', 1e-4))
+        return args, dict(noise_seed=seed, found_inf=opt.scalars[2:3] if checked else None, overwrite_table=self._overwrites_table(),
+                          table_adam=opt if checked and self.table_fused else None)
+
     def _iteration_front(self):
         """zero_grad -> render -> loss -> scaled backward, with the model's bookkeeping pinned for capture"""
         m = self.model
         if self._direct_ok():
             from fused import fused_train_iteration
-            kw = self.render_kwargs
-            bg = kw.get('bg_color', None)
             self.optimizer.zero_grad(set_to_none=True)
             # single rank (or local gradients before a sharded exchange): the producers flag non-finite gradients, no separate sweep.
             # After an all-reduce the sweep has to see the REDUCED values, so the replicated data-parallel path keeps it.
             self.producers_check = self._checked_ok and (self.averager is None)
-            loss, _, _, _ = fused_train_iteration(m, self.rays_o, self.rays_d, self.target, m.aabb_train, self.counter[0],
-                                                  self.captured_capacity, self.optimizer.scalars[0:1], 1 if bg is None else bg,
-                                                  kw.get('perturb', False), kw.get('dt_gamma', 0), kw.get('max_steps', 1024),
-                                                  kw.get('T_thresh', 1e-4), noise_seed=self.optimizer.scalars[3:4],
-                                                  found_inf=self.optimizer.scalars[2:3] if self.producers_check else None,
-                                                  overwrite_table=self._overwrites_table(),
-                                                  table_adam=self._table_adam() if self.producers_check else None)
+            args, kwargs = self._iteration_args(self.producers_check)
+            loss, _, _, _ = fused_train_iteration(*args, **kwargs)
             self.used_direct = True
             return loss[0]
         self.used_direct = False
@@ -381,13 +384,9 @@ class GraphedTrainStep:
             #   main stream altogether: _capture_lookahead.  (Folding the next batch's march behind the shard update -- two replays per step --
             #   was measured over a 1-rank RCCL group and dropped: 0.607 against 0.591 ms, EXPERIMENTS.md round 5.)
             from fused import fused_train_iteration_split
-            m, kw, opt = self.model, self.render_kwargs, self.optimizer
-            bg = kw.get('bg_color', None)
-            march, rest = fused_train_iteration_split(m, self.rays_o, self.rays_d, self.target, m.aabb_train, self.counter[0], self.captured_capacity,
-                                                      opt.scalars[0:1], 1 if bg is None else bg, kw.get('perturb', False), kw.get('dt_gamma', 0),
-                                                      kw.get('max_steps', 1024), kw.get('T_thresh', 1e-4), noise_seed=opt.scalars[3:4],
-                                                      found_inf=opt.scalars[2:3] if self._checked_ok else None,
-                                                      overwrite_table=self._overwrites_table())
+            opt = self.optimizer
+            args, kwargs = self._iteration_args(self._checked_ok)   # (no table fusion here: it needs averager=None)
+            march, rest = fused_train_iteration_split(*args, **kwargs)
             opt.wait_shadows()
             torch.cuda.synchronize()
             ga, gb, gc_ = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -420,8 +419,7 @@ class GraphedTrainStep:
         """two buffer sets, per set a march graph (static rays of the set -> its samples) and a rest graph (samples + target -> loss,
         gradients, optimizer step).  The march graphs allocate from their own pool: a march replays while the OTHER set's rest graph runs."""
         from fused import fused_train_iteration_split
-        m, kw, opt = self.model, self.render_kwargs, self.optimizer
-        bg = kw.get('bg_color', None)
+        opt = self.optimizer
         self.producers_check = self._checked_ok
         pool_march, pool_rest = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
         # data-parallel sharded update: the rest graph ends with the local non-finite sweep + poison; reduce-scatter -> [apply graph] ->
@@ -432,12 +430,8 @@ class GraphedTrainStep:
             torch.cuda.synchronize()
         la = []
         for p in range(2):
-            march, rest = fused_train_iteration_split(m, self.la_rays_o[p], self.la_rays_d[p], self.la_target[p], m.aabb_train, self.counter[p],
-                                                      self.captured_capacity, opt.scalars[0:1], 1 if bg is None else bg,
-                                                      kw.get('perturb', False), kw.get('dt_gamma', 0), kw.get('max_steps', 1024),
-                                                      kw.get('T_thresh', 1e-4), noise_seed=self.la_seed[p:p + 1],
-                                                      found_inf=opt.scalars[2:3] if self._checked_ok else None,
-                                                      overwrite_table=self._overwrites_table(), table_adam=None if sharded else self._table_adam())
+            args, kwargs = self._iteration_args(self._checked_ok, p)   # (a sharded update has no fused table: it needs averager=None)
+            march, rest = fused_train_iteration_split(*args, **kwargs)
             gm, gr = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with _capture_into(gm, pool=pool_march):
                 march()

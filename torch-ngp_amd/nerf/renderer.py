@@ -376,18 +376,17 @@ class NeRFRenderer(nn.Module):
             w = fused.inference_weights(self, s_o)
             if w is not None:
                 emb16, ws16, wc16, cfg = w
-                (bound_, L_, S_, H_, gridtype_, align_, interp_, nl_s, nl_c, _) = cfg
                 a = capi.RenderLoop()
                 a.state, a.alive[0], a.alive[1] = state.data_ptr(), alive[0].data_ptr(), alive[1].data_ptr()
                 a.rays_t, a.rays_o, a.rays_d, a.nears, a.fars, a.grid = (s_t.data_ptr(), s_o.data_ptr(), s_d.data_ptr(), s_near.data_ptr(), s_far.data_ptr(),
                                                                          bits.data_ptr())
                 a.embeddings, a.offsets, a.w_sigma, a.w_color = emb16.data_ptr(), self.encoder.offsets.data_ptr(), ws16.data_ptr(), wc16.data_ptr()
-                a.level_cost_host = capi.ray_level_costs(L_, S_, H_, 3.0 ** 0.5 / (1024.0 * max(float(bound_), 1e-6))) if fused.USE_BALANCED_FORWARD else None
+                a.level_cost_host = capi.ray_level_costs(cfg.L, cfg.S, cfg.H, 3.0 ** 0.5 / (1024.0 * max(float(cfg.bound), 1e-6))) if fused.USE_BALANCED_FORWARD else None
                 a.weights_sum, a.depth, a.image, a.compact_workspace = s_ws.data_ptr(), s_depth.data_ptr(), s_image.data_ptr(), ws.data_ptr()
                 a.max_steps, a.cascade, a.grid_size = int(max_steps), int(self.cascade), int(self.grid_size)
-                a.L, a.H, a.gridtype, a.interp, a.num_layers_sigma, a.num_layers_color = L_, H_, gridtype_, interp_, nl_s, nl_c
-                a.align_corners = align_
-                a.bound, a.dt_gamma, a.T_thresh, a.S, a.density_scale = float(self.bound), float(dt_gamma), float(T_thresh), float(S_), float(self.density_scale)
+                a.L, a.H, a.gridtype, a.interp, a.num_layers_sigma, a.num_layers_color = cfg.L, cfg.H, cfg.gridtype, cfg.interp, cfg.nl_sigma, cfg.nl_color
+                a.align_corners = cfg.align
+                a.bound, a.dt_gamma, a.T_thresh, a.S, a.density_scale = float(self.bound), float(dt_gamma), float(T_thresh), float(cfg.S), float(self.density_scale)
                 if getattr(self, 'loop_device_rows', True):
                     # the march publishes the rows that can carry a sample; the encoder and the network -- launched for the stale host-side
                     # bound -- stop there (ngp_march_rays_dev_rows / ngp_grid_encode_forward_sel / ngp_network_forward_rows): an oversized

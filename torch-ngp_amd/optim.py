@@ -34,6 +34,27 @@ Multi-GPU (one process per GPU, torch.distributed; 'nccl' is RCCL over xGMI), tw
     `shard='force'` runs this path on ONE rank as well (a 1-rank process group: every collective executes, the exchange is the identity) --
     bench.py's `ddp_overhead_1rank` and tests/test_gpu_ddp.py, the only way to execute RCCL on a one-GPU box.
     The fp32 parameters are re-pointed into one flat master buffer (`gather_master()` completes them on every rank for checkpoints).
+
+The deposit hand-off: who may write which mark when.  The gradient producers (fused.py; graph.py after a replay) and this optimizer agree
+on the state of a parameter's fp16 gradient buffer `p._ngp_grad16` through marks on the torch Parameter.  Producers set them only through
+the functions below (tests and tools that play producer assign them directly):
+
+| state of the buffer | marks on the Parameter | entered by |
+|---|---|---|
+| clean (all zero) | neither | the update kernel's zeroing (`step()`, `apply(zero=True)`); `clean_deposits()` on a stale buffer |
+| added-into | neither | an adding producer (the autograd Functions of fused.py), which asks for `clean_deposits()` first |
+| overwritten this step | `_ngp_deposit_overwritten` | `announce_overwrite()`: the producer wrote every element and read none (`overwrite_table`) |
+| stale (a consumed gradient) | `_ngp_grad16_stale` | `step()` / `apply(zero=False)` on an overwritten buffer: kept, not zeroed; `replayed_kept_deposits()` after a graph replay of the two |
+
+A stale buffer goes back to overwritten (the next overwriting producer) or to clean (`clean_deposits()`: asked for by an adding producer,
+and by `step()` itself for every buffer nobody announced).  A consumer that meets a stale buffer nobody refreshed refuses
+(`_refuse_stale_deposits`: it would apply the previous step's gradient a second time, or average it).  `announce_overwrite(p, prefix)`
+also carries the table sweep: `_ngp_table_adam_done` (the producer's grid backward applied Adam to the table, the next `step()` is the small
+closing launch and resets the mark) and `_ngp_table_adam_prefix` (the dense-level entries at the start of the table, which that launch
+sweeps).  The shadow half of the contract: `p._ngp_fp16` is current while `p._ngp_version == p._version` (`refresh_shadow`,
+`resync_stale_shadows`).  One host flag belongs to the same hand-off: `NGPAdam._maybe_flipped`, set by `table_adam()` ("a fused-table step
+was issued": buffer set B may be the current one) and cleared by `materialize()`.  Open finding: Python sets it
+at capture time only, so after the first `materialize()` later graph replays flip the parity word unseen and `materialize()` returns early.
 """
 import ctypes
 
@@ -43,6 +64,54 @@ import torch.distributed as dist
 import _ngp_capi as capi
 
 _MAX = 8
+
+
+def announce_overwrite(p, table_adam_prefix=None):
+    """a producer WROTE the whole deposit buffer of `p` this step: the next step()/apply keeps the buffer instead of zeroing it.
+    table_adam_prefix: the producer's grid backward also applied Adam to the table `p`, except its first `table_adam_prefix` entries (the
+    dense levels: ngp_grid_table_adam_prefix) -- the next step() sweeps those in its closing launch and leaves the rest alone"""
+    p._ngp_deposit_overwritten = True
+    if table_adam_prefix is not None:
+        p._ngp_table_adam_prefix = int(table_adam_prefix)
+        p._ngp_table_adam_done = True
+
+
+def _consumed(p, kept):
+    """step() / apply() handed the deposit buffer of `p` to the update kernel, which zeroed it (clean) or kept it (stale from here on)"""
+    p._ngp_deposit_overwritten = False
+    p._ngp_grad16_stale = kept
+
+
+def replayed_kept_deposits(params):
+    """after the replay of a captured step() / apply(zero=False) behind overwriting producers: Python ran at capture time only, so the
+    overwritten -> stale transition of every replay is stated here"""
+    for p in params:
+        if getattr(p, '_ngp_grad16', None) is not None:
+            p._ngp_grad16_stale = True
+
+
+def clean_deposits(params):
+    """zero the fp16 deposit buffers that an overwriting producer left stale, before a producer that ADDS into them or a step without a
+    fresh deposit; a no-op otherwise (one Python attribute check per parameter)"""
+    for p in params:
+        if getattr(p, '_ngp_grad16_stale', False):
+            p._ngp_grad16.zero_()
+            p._ngp_grad16_stale = False
+
+
+def refresh_shadow(p):
+    """the fp16 shadow of `p` from its fp32 value, and the version it was taken at"""
+    p._ngp_fp16.copy_(p.detach())
+    p._ngp_version = p._version
+
+
+def resync_stale_shadows(params):
+    """NGPAdam updates parameters and fp16 shadows together through raw pointers (no autograd version bump); any OTHER in-place write
+    to a parameter (load_state_dict, manual init) bumps `p._version` -- refresh the shadow then, instead of silently using stale weights"""
+    for p in params:
+        if getattr(p, '_ngp_fp16', None) is not None and getattr(p, '_ngp_version', None) != p._version:
+            with torch.no_grad():
+                refresh_shadow(p)
 
 
 class NGPAdam:
@@ -152,9 +221,14 @@ class NGPAdam:
 
     def table_adam(self):
         """ctypes ngp_table_adam_t for the grid backward of this step's iteration (None when no table is fused); marks the step as fused"""
-        p = self.fused_table
-        if p is None:
+        if self.fused_table is None:
             return None
+        self._maybe_flipped = True
+        return self._table_adam_struct()
+
+    def _table_adam_struct(self):
+        """the struct alone, nothing marked (the closing launch of a fused step takes it too, for the table's dense-level prefix)"""
+        p = self.fused_table
         st, alt = self.state[p], self._table_alt
         lr = [g['lr'] for g in self.param_groups if any(q is p for q in g['params'])][0]
         ta = capi.TableAdam()
@@ -164,14 +238,6 @@ class NGPAdam:
         ta.param_fp16[0], ta.param_fp16[1] = st['fp16'].data_ptr(), alt['p16'].data_ptr()
         ta.state = self.scalars.data_ptr()
         ta.lr, ta.beta1, ta.beta2, ta.eps = float(lr), self.betas[0], self.betas[1], self.eps
-        self._maybe_flipped = True
-        return ta
-
-    def _table_struct(self):
-        """the same struct without marking a step (the closing launch of a fused step needs it for the table's dense-level prefix)"""
-        flag = self._maybe_flipped
-        ta = self.table_adam()
-        self._maybe_flipped = flag
         return ta
 
     @torch.no_grad()
@@ -245,8 +311,7 @@ class NGPAdam:
             self.gather_master()
         for p, st in self.state.items():
             if 'fp16' in st:
-                st['fp16'].copy_(p.detach())
-                p._ngp_version = p._version
+                refresh_shadow(p)
 
     # -- gradient exchange ---------------------------------------------------------------------------
     def _avg_native(self):
@@ -270,7 +335,7 @@ class NGPAdam:
 
     def _refuse_stale_deposits(self, what):
         """the overwrite-table protocol (fused.USE_OVERWRITE_TABLE) leaves a deposit buffer STALE after the step that kept it; every producer
-        of the repository either overwrites it again (and says so: _ngp_deposit_overwritten) or zeroes it first.  A consumer that meets a
+        of the repository either overwrites it again (and says so: announce_overwrite) or zeroes it first.  A consumer that meets a
         stale buffer nobody has refreshed would average / apply the PREVIOUS step's gradient: refuse loudly"""
         for p in self.flat_params:
             if getattr(p, '_ngp_grad16_stale', False) and not getattr(p, '_ngp_deposit_overwritten', False):
@@ -347,8 +412,8 @@ class NGPAdam:
         """Adam on my shard (skipped everywhere when any rank saw a non-finite gradient), loss-scale / step-count commit, and the flat
         deposit buffer zeroed for the next backward; capturable.  zero=False: the producers of the NEXT step overwrite every element they own
         (the captured fused iteration with overwrite_table: the grid backward writes the whole table gradient, the slab reduction writes the
-        MLP gradients), so the 24.5 MB memset is skipped -- the buffers are stale from here on, which the caller has to announce
-        (graph.GraphedTrainStep._mark_deposits) so that a producer that ADDS cleans them first."""
+        MLP gradients), so the 24.5 MB memset is skipped -- the buffers are stale from here on, which a caller that REPLAYS this call has
+        to state itself (replayed_kept_deposits) so that a producer that ADDS cleans them first."""
         if len(self._keep) > 64:   # used standalone in a loop without pre_reduce_check()/step(): do not grow without bound
             del self._keep[:-8]
         if self.verdict == 'poison':
@@ -362,8 +427,7 @@ class NGPAdam:
         if not (self.flat_grad16.is_cuda and torch.cuda.is_current_stream_capturing()):
             self._poisoned = getattr(self, '_poison_captured', False)   # an eager step consumed its poison launch; a captured one replays it
         for p in self.flat_params:   # zeroed: clean, whatever an overwriting producer announced; kept: stale until overwritten / cleaned
-            p._ngp_deposit_overwritten = False
-            p._ngp_grad16_stale = not zero
+            _consumed(p, kept=not zero)
 
     @torch.no_grad()
     def gather_shadows(self, async_op=True):
@@ -426,21 +490,13 @@ class NGPAdam:
                         # this step's producer WROTE the whole buffer (fused iteration with overwrite_table): the update kernel leaves it
                         # alone instead of zeroing it -- it is stale from here on, until the next overwriting producer or a clean_deposits()
                         is_half = 3
-                        p._ngp_deposit_overwritten = False
-                        p._ngp_grad16_stale = True
+                        _consumed(p, kept=True)
                 else:
                     continue
                 entries.append((p, st, grad, is_half, g['lr']))
         return entries
 
-    @staticmethod
-    def clean_deposits(params):
-        """zero the fp16 deposit buffers that an overwriting producer left stale (see `_entries`), before a producer that ADDS into them
-        or a step without a fresh deposit; a no-op otherwise (one Python attribute check per parameter)"""
-        for p in params:
-            if getattr(p, '_ngp_grad16_stale', False):
-                p._ngp_grad16.zero_()
-                p._ngp_grad16_stale = False
+    clean_deposits = staticmethod(clean_deposits)   # (`optimizer.clean_deposits(params)`: the spelling of graph.py and the tests)
 
     def _deposit_used(self, st):
         # only checked on the eager path (never while capturing a graph: it reads the device)
@@ -448,41 +504,32 @@ class NGPAdam:
             return False
         return bool(st['grad16'].ne(0).any().item())
 
-    def _launch(self, entries, phases, omd):
-        """one ngp_optim_adam_step_ex call.  entries: up to 8 tuples (n, param, exp_avg, exp_avg_sq, grad, fp16 shadow or None, grad_is_half,
-        lr, ema shadow or None) of flat tensors (param / moments may be None for a CHECK-only call)"""
+    def _entry_arrays(self, entries, ema):
+        """the per-entry arguments of a launch as nine void* (ctypes arrays, kept alive until the next step): n, param, exp_avg, exp_avg_sq,
+        grad, fp16 shadow, grad_is_half, lr and -- `ema` -- the EMA shadow (else None); all None for a launch without entries.
+        entries: up to 8 tuples in that order, of flat tensors (param / moments / shadows may be None)"""
         k = len(entries)
+        if not k:
+            return [None] * 9
         vp = ctypes.c_void_p
 
         def ptrs(i):
             return (vp * k)(*[(e[i].data_ptr() if e[i] is not None else None) for e in entries])
-        if k:
-            n = (ctypes.c_uint64 * k)(*[int(e[0]) for e in entries])
-            arrs = (n, ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5), (ctypes.c_int * k)(*[int(e[6]) for e in entries]),
-                    (ctypes.c_float * k)(*[float(e[7]) for e in entries]), ptrs(8) if omd > 0.0 else None)
-            self._keep.append((arrs, entries))
-            cast = [ctypes.cast(a, vp) if a is not None else None for a in arrs]
-        else:
-            cast = [None] * 9
-        capi.check(capi.lib.ngp_optim_adam_step_ex(k, cast[0], cast[1], cast[2], cast[3], cast[4], cast[5], cast[6], cast[7], self.betas[0],
+        arrs = ((ctypes.c_uint64 * k)(*[int(e[0]) for e in entries]), ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5),
+                (ctypes.c_int * k)(*[int(e[6]) for e in entries]), (ctypes.c_float * k)(*[float(e[7]) for e in entries]), ptrs(8) if ema else None)
+        self._keep.append((arrs, entries))
+        return [ctypes.cast(a, vp) if a is not None else None for a in arrs]
+
+    def _launch(self, entries, phases, omd):
+        """one ngp_optim_adam_step_ex call over up to 8 entries (`_entry_arrays`; param / moments may be None for a CHECK-only call)"""
+        cast = self._entry_arrays(entries, ema=omd > 0.0)
+        capi.check(capi.lib.ngp_optim_adam_step_ex(len(entries), cast[0], cast[1], cast[2], cast[3], cast[4], cast[5], cast[6], cast[7], self.betas[0],
                                                    self.betas[1], self.eps, 1.0, self.growth_factor, self.backoff_factor, self.growth_interval,
                                                    self.scalars.data_ptr(), cast[8], float(omd), phases, capi.stream()))
 
     def _launch_small_commit(self, entries, flip, table_prefix=0):
-        k = len(entries)
-        vp = ctypes.c_void_p
-
-        def ptrs(i):
-            return (vp * k)(*[(e[i].data_ptr() if e[i] is not None else None) for e in entries])
-        if k:
-            n = (ctypes.c_uint64 * k)(*[int(e[0]) for e in entries])
-            arrs = (n, ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5), (ctypes.c_int * k)(*[int(e[6]) for e in entries]),
-                    (ctypes.c_float * k)(*[float(e[7]) for e in entries]))
-            self._keep.append((arrs, entries))
-            cast = [ctypes.cast(a, vp) for a in arrs]
-        else:
-            cast = [None] * 8
-        ta = self._table_struct() if table_prefix else None   # (copied by the C entry before it returns)
+        k, cast = len(entries), self._entry_arrays(entries, ema=False)
+        ta = self._table_adam_struct() if table_prefix else None   # (copied by the C entry before it returns)
         capi.check(capi.lib.ngp_optim_adam_small_commit(k, cast[0], cast[1], cast[2], cast[3], cast[4], cast[5], cast[6], cast[7], self.betas[0],
                                                         self.betas[1], self.eps, 1.0, self.growth_factor, self.backoff_factor, self.growth_interval,
                                                         self.scalars.data_ptr(), 1 if flip else 0,
@@ -703,7 +750,7 @@ class NGPEma:
         if self.optimizer is not None and hasattr(self.optimizer, 'materialize'):
             self.optimizer.materialize()   # BEFORE the parameters are written (else the sync below would copy set B over them)
         for s_, p in zip(self.shadow_params, self.params):
-            p.copy_(s_)  # bumps the version counter: stale fp16 shadows are detected by fused._resync_stale_shadows
+            p.copy_(s_)  # bumps the version counter: stale fp16 shadows are detected by resync_stale_shadows
         if self.optimizer is not None:
             self.optimizer._sync_shadows(assume_complete=True)   # every rank just wrote the complete parameter set
 
