@@ -534,3 +534,190 @@ def test_double_buffered_table_bookkeeping_on_the_host():
     sharded = Double([{'params': [torch.nn.Parameter(torch.zeros(8, 2))], 'lr': 1e-2}], world_size=2, shard=False)
     with pytest.raises(RuntimeError, match='data-parallel'):
         sharded.enable_table_fusion(sharded.flat_params[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# What Python decides at capture time and a replay has to state again.  graph.GraphedTrainStep runs here on the CPU over stub
+# graphs for its plain replay, its lookahead replay (stub stream / events) and a switch between captured capacities; what the replays do
+# to the TABLE at odd and even counts, the re-capture and the real capacity ladder need the device: tests/test_gpu_table_adam.py.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _fused_double():
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "torch-ngp_amd"))
+    Double = _make_double()
+    torch.manual_seed(0)
+    table, mlp = torch.nn.Parameter(torch.randn(64, 2) * 0.1), torch.nn.Parameter(torch.randn(128) * 0.1)
+    opt = Double([{'params': [table], 'lr': 1e-2}, {'params': [mlp], 'lr': 3e-3}], betas=(0.9, 0.99), eps=1e-15)
+    return opt, table, mlp
+
+
+def test_a_stated_replay_makes_the_next_materialize_read_the_parity_word():
+    from optim import replayed_fused_table_step
+    opt, table, mlp = _fused_double()
+    replayed_fused_table_step(opt)                       # no fused table: nothing to state
+    assert not opt._maybe_flipped
+    opt.enable_table_fusion(table)
+    alt, st = opt._table_alt, opt.state[table]
+    opt._maybe_flipped = True                            # capture time: table_adam() took the struct
+    opt.materialize()                                    # the first reader after the capture: parity 0, flag cleared
+    assert not opt._maybe_flipped and float(opt.scalars[5]) == 0.0
+    before = table.detach().clone()
+    alt['p'].fill_(3.0); alt['m'].fill_(0.5); alt['v'].fill_(0.25); alt['p16'].fill_(3.0)
+    opt.scalars[5] = 1.0                                 # a replay flipped the word on the device ...
+    opt.materialize()                                    # ... and nobody said so: the word is not read (the gate of the drop-in forward)
+    assert torch.equal(table.detach(), before) and float(opt.scalars[5]) == 1.0
+    replayed_fused_table_step(opt)
+    assert opt._maybe_flipped
+    opt.materialize()
+    assert float(opt.scalars[5]) == 0.0 and not opt._maybe_flipped
+    assert float(table.detach().min()) == 3.0 and float(st['exp_avg'].min()) == 0.5 and float(st['exp_avg_sq'].min()) == 0.25
+    assert float(st['fp16'].float().min()) == 3.0
+    # stated after a replay that did not flip (a skipped step): one read, nothing copied
+    alt['p'].fill_(7.0)
+    replayed_fused_table_step(opt)
+    opt.materialize()
+    assert float(table.detach().min()) == 3.0 and not opt._maybe_flipped
+
+
+class _StubGraph:
+    def __init__(self, log, name):
+        self.log, self.name = log, name
+
+    def replay(self):
+        self.log.append(self.name)
+
+
+class _StubStream:
+    def wait_event(self, e):
+        pass
+
+    def wait_stream(self, s):
+        pass
+
+
+class _StubEvent:
+    def record(self, s=None):
+        pass
+
+
+def _stub_stepper(opt, table):
+    from graph import GraphedTrainStep
+
+    class Model(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.encoder = torch.nn.Module()
+            self.encoder.embeddings = table
+            self.mean_count = 20000
+            self.local_step = 1
+            self.register_buffer('step_counter', torch.zeros(16, 2, dtype=torch.int32))
+
+    st = GraphedTrainStep(Model(), opt, None, 8, {}, fused_table_adam=True, capacity_ladder=())
+    st.global_step = 1                                   # (no occupancy refresh in the steps below)
+    return st
+
+
+def test_graphed_train_step_states_the_replay_at_every_replay_site(monkeypatch):
+    opt, table, mlp = _fused_double()
+    opt.enable_table_fusion(table)
+    st = _stub_stepper(opt, table)
+    log = []
+    cap = st._capacity()
+    o, d, t = torch.zeros(1, 8, 3), torch.zeros(1, 8, 3), torch.zeros(8, 3)
+    # the plain graph of step()
+    st.graphs, st.captured_capacity, st.loss = (_StubGraph(log, 'plain'),), cap, torch.zeros(())
+    st.table_fused = False
+    st.step(o, d, t)
+    assert log == ['plain'] and not opt._maybe_flipped   # graphs with the separate sweep: nothing flips
+    st.table_fused = True
+    st.step(o, d, t)
+    assert log == ['plain', 'plain'] and opt._maybe_flipped
+    # a switch to another captured capacity (_activate: no Python iteration runs), then its replay
+    opt._maybe_flipped = False
+    st._captured = {cap: st._snapshot()}
+    other = dict(st._snapshot(), graphs=(_StubGraph(log, 'other'),))
+    st._captured[cap + 4 * st.quantum] = other
+    st.model.mean_count = cap + 3 * st.quantum
+    st.step(o, d, t)
+    assert log[-1] == 'other' and st.n_switches == 1 and st.captured_capacity == cap + 4 * st.quantum and opt._maybe_flipped
+    # the lookahead's rest graph (the march of a batch nobody announced runs in line)
+    opt._maybe_flipped = False
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda *a, **k: _StubStream())
+    st.la_rays_o, st.la_rays_d = [torch.zeros(8, 3) for _ in range(2)], [torch.zeros(8, 3) for _ in range(2)]
+    st.la_target, st.la_seed = [torch.zeros(8, 3) for _ in range(2)], torch.zeros(2, dtype=torch.int32)
+    st.la_event, st.la_slot_event = [_StubEvent(), _StubEvent()], _StubEvent()
+    st.la = [(_StubGraph(log, f'march{p}'), _StubGraph(log, f'rest{p}'), torch.zeros(())) for p in range(2)]
+    st._captured = {st.captured_capacity: st._snapshot()}
+    st.step(o, d, t)
+    assert log[-2:] == ['march0', 'rest0'] and st.la_cur == 1 and opt._maybe_flipped
+    opt.materialize()
+    assert not opt._maybe_flipped
+
+
+def test_table_fusion_fit_is_decided_against_the_small_commit_cap():
+    import ctypes
+    import re
+    import numpy as np
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "torch-ngp_amd"))
+    import _ngp_capi as capi
+    import optim
+    from gridencoder.grid import level_offsets
+    # the cap is the one the C entry enforces
+    src = open(os.path.join(root, 'torch-ngp_amd', 'csrc', 'optim.hip')).read()
+    m = re.search(r'NGP_REQUIRE\(total <= \(1u << (\d+)\)', src)
+    assert m is not None and optim.SMALL_COMMIT_MAX_PARAMS == 1 << int(m.group(1)) == 1 << 22
+    cap = optim.SMALL_COMMIT_MAX_PARAMS
+    rest = 18432
+    assert optim.table_fusion_fits((cap - rest) // 2, 2, rest)               # exactly the cap
+    assert optim.table_fusion_fits((cap - rest) // 2 - 1, 2, rest)
+    assert not optim.table_fusion_fits((cap - rest) // 2 + 1, 2, rest)
+    assert not optim.table_fusion_fits((cap - rest) // 2, 2, rest + 1)
+    assert optim.table_fusion_fits(0, 2, cap) and not optim.table_fusion_fits(0, 2, cap + 1)
+    # the real prefix (ngp_grid_table_adam_prefix of the built library) of 16 levels x 2 features at a batch the sorted backward serves.
+    # A dense level rides in the prefix while it has <= 128 x 4096 entries (the round-robin bins of plan_backward), so it is the grid's
+    # GEOMETRY that fills the prefix, not the hash-table size:
+    def prefix(base, desired, log2_T):
+        scale = float(np.exp2(np.log2(desired / base) / 15))                  # GridEncoder: per_level_scale
+        off = np.ascontiguousarray(level_offsets(3, 16, scale, base, log2_T, False), dtype=np.int32)
+        p = int(capi.lib.ngp_grid_table_adam_prefix(off.ctypes.data_as(ctypes.c_void_p), 24576, 3, 2, 16, float(np.log2(scale)), base, 0, 0, capi.NGP_F16))
+        assert p == 0xffffffff or p in [int(x) for x in off]                  # a whole number of levels
+        return p
+    # the flagship geometry (16 -> 2048): levels 0-4 are dense, 352 696 entries, for every table size that carries the sweep at all ...
+    assert [prefix(16, 2048, T) for T in (17, 18, 19)] == [136696, 352696, 352696]
+    assert optim.table_fusion_fits(352696, 2, rest)
+    # ... and from log2_hashmap_size = 20 on level 5 (83^3 = 551 368 entries, still dense) is too large for the round-robin bins: the grid
+    # backward cannot carry the sweep, whatever the cap says (graph.GraphedTrainStep._table_fusion_fits keeps the separate sweep then)
+    assert [prefix(16, 2048, T) for T in (20, 21, 22)] == [0xffffffff] * 3
+    # a slowly growing grid has many dense levels: 32 -> 128 still fits (10 levels), 32 -> 96 does not (13 levels, 4.7 M parameters)
+    assert prefix(32, 128, 19) == 1672624 and optim.table_fusion_fits(1672624, 2, rest)
+    assert prefix(32, 96, 19) == 2357584 and not optim.table_fusion_fits(2357584, 2, rest)
+    assert 2357584 * 2 + rest == 4733600 > cap
+
+
+def test_poison_guard_returns_when_the_captured_poison_launch_is_discarded():
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "torch-ngp_amd"))
+    Double = _make_double()
+    torch.manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn(64, 2) * 0.1), torch.nn.Parameter(torch.randn(128) * 0.1)]
+    opt = Double([{'params': params, 'lr': 1e-2}], betas=(0.9, 0.99), eps=1e-15, init_scale=1.0, world_size=1, shard='force', rank=0)
+    assert opt.shard and opt.verdict == 'poison'
+    with pytest.raises(RuntimeError, match=r"verdict='poison' needs poison_shards\(\)"):
+        opt.reduce_gradients()
+    # capture time: poison_shards() inside a stream capture records that every replay issues the launch
+    opt.poison_shards()
+    opt._poison_captured = True
+    opt.apply()                                          # (eager: consumes an eager poison launch, keeps a captured one)
+    assert opt._poisoned
+    # the graphs are dropped / recorded anew: GraphedTrainStep tells the optimizer (in _capture() and where a capture fails)
+    st = _stub_stepper(opt, params[0])
+    st._captures_discarded()
+    assert not opt._poison_captured and not opt._poisoned
+    with pytest.raises(RuntimeError, match=r"verdict='poison' needs poison_shards\(\)"):
+        opt.reduce_gradients()
+    opt.apply()
+    assert not opt._poisoned                              # and it stays that way
+    with pytest.raises(RuntimeError, match=r"verdict='poison' needs poison_shards\(\)"):
+        opt.reduce_gradients()

@@ -221,6 +221,7 @@ class GraphedTrainStep:
             except Exception as e:  # noqa: BLE001
                 self.capture_error = repr(e)
                 self.graphs = None
+                self._captures_discarded()
                 torch.cuda.synchronize()
         if cap is not None and self.graphs is not None and self.capture_error is None and self.capacity_ladder:
             # the ladder: graphs for the capacities the estimate may move to (each rung owns its buffers: ~2 KB per sample and buffer set)
@@ -229,11 +230,15 @@ class GraphedTrainStep:
                 rung = ((int(base * f) + self.quantum - 1) // self.quantum) * self.quantum
                 if rung in self._captured or rung < 16384:
                     continue
+                # (what the optimizer recorded about the graphs that stay, should this rung fail half-way: NGPAdam.captures_discarded)
+                kept = {k: getattr(self.optimizer, k) for k in ('_poison_captured', '_poisoned') if hasattr(self.optimizer, k)}
                 try:
                     self.captured_capacity = rung
                     self._capture()
                 except Exception as e:  # noqa: BLE001 -- the ladder is an optimisation: keep what was captured
                     self.ladder_error = repr(e)
+                    for k, v in kept.items():
+                        setattr(self.optimizer, k, v)
                     torch.cuda.synchronize()
                     break
             self._activate(base)
@@ -267,6 +272,39 @@ class GraphedTrainStep:
             from optim import replayed_kept_deposits
             # (sharded update without the memset: every deposit buffer is left as its producer wrote it)
             replayed_kept_deposits([emb] if self.averager is None else [emb] + list(getattr(self.optimizer, 'flat_params', [])))
+
+    def _after_replay(self):
+        """what Python would have stated had it issued the step that was just replayed: the deposit buffers the captured optimizer step kept
+        (`_mark_deposits`) and, for graphs that carry the table's Adam sweep, that the parity word may have flipped
+        (optim.replayed_fused_table_step: `materialize()` reads the word again).  Attribute writes only."""
+        self._mark_deposits()
+        if self.table_fused:
+            from optim import replayed_fused_table_step
+            replayed_fused_table_step(self.optimizer)
+
+    def _captures_discarded(self):
+        """the graphs are dropped (a failed capture) or about to be recorded anew: the optimizer forgets what it recorded at capture time"""
+        fn = getattr(self.optimizer, 'captures_discarded', None)
+        if fn is not None:
+            fn()
+
+    def _table_fusion_fits(self, emb):
+        """does the closing launch of a fused-table step serve THIS table (optim.table_fusion_fits: its dense-level prefix at the captured
+        capacity + the other tensors against the cap of ngp_optim_adam_small_commit)?  False as well where the grid backward cannot carry
+        the sweep at all: the graphs then keep the separate sweep"""
+        import ctypes
+        import _ngp_capi as capi
+        from fused import network_cfg
+        from optim import table_fusion_fits
+        m = self.model
+        arr = capi.host_offsets(m.encoder.offsets)
+        if arr is None:
+            return False
+        cfg = network_cfg(m.encoder, m.sigma_net, m.color_net, m.bound, True)
+        prefix = int(capi.lib.ngp_grid_table_adam_prefix(ctypes.cast(arr, ctypes.c_void_p), int(self.captured_capacity), 3, int(emb.shape[1]), cfg.L,
+                                                         cfg.S, cfg.H, cfg.gridtype, cfg.align, capi.NGP_F16))
+        rest = sum(p.numel() for p in getattr(self.optimizer, 'flat_params', []) if p is not emb)
+        return prefix != 0xffffffff and table_fusion_fits(prefix, emb.shape[1], rest)
 
     def _clean_deposits(self):
         """before replaying graphs whose producers ADD into the deposit buffers: zero what an overwriting producer left behind"""
@@ -360,10 +398,11 @@ class GraphedTrainStep:
             from fused import iteration_checks_gradients
             self._checked_ok = iteration_checks_gradients(self.model)
         self.sync_params()   # (outside the capture: a re-capture starts from buffer set A)
+        self._captures_discarded()   # (a capture that contains poison_shards() records it again)
         self.table_fused = False
         if self.fused_table_adam and self._checked_ok and self._overwrites_table() and self.captured_capacity >= 16384:
             emb = getattr(getattr(self.model, 'encoder', None), 'embeddings', None)
-            if emb is not None and getattr(emb, '_ngp_fp16', None) is not None:
+            if emb is not None and getattr(emb, '_ngp_fp16', None) is not None and self._table_fusion_fits(emb):
                 self.optimizer.enable_table_fusion(emb)
                 self.table_fused = True
         self.la = None
@@ -668,6 +707,7 @@ class GraphedTrainStep:
             except Exception as e:  # noqa: BLE001 -- keep training eagerly; the caller can inspect .capture_error
                 self.capture_error = repr(e)
                 self.graphs = None
+                self._captures_discarded()
                 torch.cuda.synchronize()
                 loss = self._eager(rays_o, rays_d, target)
                 self.global_step += 1
@@ -676,7 +716,7 @@ class GraphedTrainStep:
         self._clean_deposits()
         if self.la is not None:
             loss = self._step_lookahead(rays_o, rays_d, target, next_rays)
-            self._mark_deposits()
+            self._after_replay()
             m.local_step += 1
             self.global_step += 1
             return loss
@@ -705,7 +745,7 @@ class GraphedTrainStep:
                 self._precopied = (no, nd, nt, (no._version, nd._version, nt._version))
             self.graphs[2].replay()            # verdict + Adam on my shard, scale / step commit, deposit buffer zeroed
             opt.gather_shadows()               # all-gather of the fp16 shadows on the side stream
-            self._mark_deposits()
+            self._after_replay()
             m.local_step += 1
             self.global_step += 1
             return self.loss
@@ -716,7 +756,7 @@ class GraphedTrainStep:
         if len(self.graphs) == 2:
             self.averager.all_reduce()
             self.graphs[1].replay()
-        self._mark_deposits()
+        self._after_replay()
         # hand the sample count to the model's 16-slot ring exactly where the eager renderer would have put it
         m.step_counter[m.local_step % 16].copy_(self.counter[0], non_blocking=True)
         m.local_step += 1

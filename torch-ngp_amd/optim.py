@@ -53,8 +53,9 @@ also carries the table sweep: `_ngp_table_adam_done` (the producer's grid backwa
 closing launch and resets the mark) and `_ngp_table_adam_prefix` (the dense-level entries at the start of the table, which that launch
 sweeps).  The shadow half of the contract: `p._ngp_fp16` is current while `p._ngp_version == p._version` (`refresh_shadow`,
 `resync_stale_shadows`).  One host flag belongs to the same hand-off: `NGPAdam._maybe_flipped`, set by `table_adam()` ("a fused-table step
-was issued": buffer set B may be the current one) and cleared by `materialize()`.  Open finding: Python sets it
-at capture time only, so after the first `materialize()` later graph replays flip the parity word unseen and `materialize()` returns early.
+was issued": buffer set B may be the current one) and cleared by `materialize()`.  Python runs `table_adam()` at capture time only, so
+whoever REPLAYS a captured fused-table step states it after every replay (`replayed_fused_table_step()`): `materialize()` then reads the
+parity word again (tests/test_gpu_table_adam.py: every reader and writer outside the graphs at odd and even replay counts).
 """
 import ctypes
 
@@ -88,6 +89,27 @@ def replayed_kept_deposits(params):
     for p in params:
         if getattr(p, '_ngp_grad16', None) is not None:
             p._ngp_grad16_stale = True
+
+
+def replayed_fused_table_step(optimizer):
+    """after the replay of a captured fused-table iteration (`table_adam()` handed to the grid backward + the closing launch): the device
+    may have flipped the parity word, buffer set B may be the current one -- what `table_adam()` recorded when Python issued the step.
+    One attribute write, no device work; `materialize()` reads the word the next time somebody outside the graphs asks for the table"""
+    if getattr(optimizer, 'fused_table', None) is not None:
+        optimizer._maybe_flipped = True
+
+
+# ngp_optim_adam_small_commit (csrc/optim.hip: NGP_REQUIRE(total <= (1u << 22))) serves the closing launch of a fused-table step up to this
+# many parameters: the table's dense-level prefix plus the remaining tensors
+SMALL_COMMIT_MAX_PARAMS = 1 << 22
+
+
+def table_fusion_fits(prefix_entries, level_dim, rest_params):
+    """can the closing launch of a fused-table step carry what the grid backward leaves to it?  prefix_entries: the dense-level entries
+    at the start of the table (ngp_grid_table_adam_prefix), level_dim: features per entry, rest_params: elements of the optimizer's
+    other tensors.  Asked BEFORE `enable_table_fusion` (graph.GraphedTrainStep._capture): a table that does not fit keeps the separate
+    sweep instead of failing in step()"""
+    return int(prefix_entries) * int(level_dim) + int(rest_params) <= SMALL_COMMIT_MAX_PARAMS
 
 
 def clean_deposits(params):
@@ -366,6 +388,13 @@ class NGPAdam:
             if self.flat_grad16.is_cuda and torch.cuda.is_current_stream_capturing():
                 self._poison_captured = True   # part of a graph: every replay issues it
             self._poisoned = True   # (host-side: reduce_gradients() refuses to run without it -- at capture time for a captured step)
+
+    def captures_discarded(self):
+        """the graphs that replayed this optimizer's building blocks were dropped or are about to be captured anew (graph.GraphedTrainStep:
+        `_capture()`, a failed capture): what capture time recorded about them no longer holds.  A poison launch that was part of a graph
+        is not issued any more, so `reduce_gradients()` asks for `poison_shards()` again (a new capture that contains it says so itself)"""
+        self._poison_captured = False
+        self._poisoned = False
 
     def _poison_launch(self):
         capi.check(capi.lib.ngp_optim_poison_shards(self.flat_grad16.data_ptr(), self.world_size, self.payload, self.scalars.data_ptr(), capi.stream()))
