@@ -216,6 +216,10 @@ int ngp_compact_rays(const int32_t* rays_alive, uint32_t n_alive, int32_t* out_a
  * (one matmul's weights in LDS at a time).  The only shapes refused (NGP_ERR_INVALID) are those whose single largest
  * layer exceeds the LDS: hidden_dim * max(input_dim, hidden_dim) * 2 bytes > 152 KiB, i.e. input_dim > 304 with 256-wide layers.
  * activation ids: 0 ReLU, 1 Exp, 2 Sine, 3 Sigmoid, 4 Squareplus, 5 Softplus, 6 None (utils.h:29-37).
+ * `activation` is the hidden layers' one, `output_activation` is applied to the output matmul and is FORWARD-ONLY: the backward ignores it
+ * (grad is taken as the gradient of what the output matmul produced, as in the reference, ffmlp.cu:780).  The backward takes the derivative
+ * from the STORED post-activations y (ReLU y > 0, Exp y, Sigmoid y(1-y), Squareplus s^2/(s^2+1) with s = 10y, Softplus 1 - exp(-10y),
+ * None 1: utils.h:532-582); Sine back-propagates as the identity -- cos(x) cannot be recovered from sin(x), the reference passes it through too.
  * --------------------------------------------------------------------------------------------- */
 
 /* replaces ffmlp_forward (ffmlp.cu:635-671): forward_buffer [num_layers,B,hidden] receives the hidden

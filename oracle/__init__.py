@@ -333,28 +333,59 @@ def ffmlp_forward(inputs, weights, input_dim, output_dim, hidden_dim, num_layers
     return out, np.stack(acts, 0)
 
 
+def _act_backward_factor(y, act):
+    """act'(pre-activation) written in terms of the STORED post-activation y (utils.h:532-582, warp_activation_backward)."""
+    if act == 1:
+        return y
+    if act == 3:
+        return y * (1.0 - y)
+    if act == 4:
+        s = y * 10.0
+        return s * s / (s * s + 1.0)
+    if act == 5:
+        return 1.0 - np.exp(-y * 10.0)
+    if act in (2, _ACT_NONE):
+        return np.ones_like(y)
+    raise ValueError(act)
+
+
 def ffmlp_backward(grad, inputs, weights, forward_buffer, input_dim, output_dim, hidden_dim, num_layers,
-                   round_hidden=True, dtype=np.float64):
-    """Backward of the ReLU/none MLP (ffmlp.cu:749-895 semantics: ReLU mask from stored post-activation > 0).
-    returns grad_inputs [B,in], grad_weights flat.  With round_hidden the back-propagated hidden
-    gradients are rounded to fp16 between layers (backward_buffer is fp16, ffmlp.py:72)."""
+                   round_hidden=True, dtype=np.float64, activation=0, return_hidden=False):
+    """Backward of the MLP (ffmlp.cu:749-895 semantics).  The derivative of the hidden activation is taken from the STORED
+    post-activation y (forward_buffer, i.e. after the fp16 rounding of ffmlp_forward(round_hidden=True)), as the reference's
+    warp_activation_backward does: ReLU y > 0, Exp y, Sigmoid y(1-y), Squareplus s^2/(s^2+1) with s = 10y, Softplus
+    1 - exp(-10y), None 1.  Sine (2) back-propagates as the identity: its derivative cannot be recovered from sin(x) alone and
+    the reference passes the gradient through unchanged as well.  The output activation plays no part (ffmlp.cu:780).
+    returns grad_inputs [B,in], grad_weights flat (and, with return_hidden, the list of hidden gradients dZ, last layer first).
+    With round_hidden the back-propagated hidden gradients are rounded to fp16 between layers (backward_buffer is fp16,
+    ffmlp.py:72)."""
     g = np.asarray(grad, dtype=dtype)
     x = np.asarray(inputs, dtype=dtype)
     fb = np.asarray(forward_buffer, dtype=dtype)
     mats = [np.asarray(m, dtype=dtype) for m in ffmlp_split_weights(weights, input_dim, output_dim, hidden_dim, num_layers)]
+
+    def transfer(gh, y):
+        if activation == _ACT_RELU:
+            return gh * (y > 0)
+        return gh * _act_backward_factor(y, activation)
+
     gws = [None] * (num_layers + 1)
+    hidden = []
     gws[num_layers] = g.T @ fb[num_layers - 1]
-    gh = (g @ mats[num_layers]) * (fb[num_layers - 1] > 0)
+    gh = transfer(g @ mats[num_layers], fb[num_layers - 1])
     if round_hidden:
         gh = gh.astype(np.float16).astype(dtype)
+    hidden.append(gh)
     for li in range(num_layers - 1, 0, -1):
         gws[li] = gh.T @ fb[li - 1]
-        gh = (gh @ mats[li]) * (fb[li - 1] > 0)
+        gh = transfer(gh @ mats[li], fb[li - 1])
         if round_hidden:
             gh = gh.astype(np.float16).astype(dtype)
+        hidden.append(gh)
     gws[0] = gh.T @ x
     gx = gh @ mats[0]
-    return gx, np.concatenate([m.reshape(-1) for m in gws])
+    gw = np.concatenate([m.reshape(-1) for m in gws])
+    return (gx, gw, hidden) if return_hidden else (gx, gw)
 
 
 def trunc_exp_forward(x):

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 
 def cu16(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda().half()
+    return torch.tensor(np.ascontiguousarray(a, dtype=np.float32)).cuda().half()   # (a copy: the shared reference arrays are read-only)
 
 
 def _be():
@@ -293,3 +293,259 @@ def test_empty_batch_backward_returns_zero_weight_gradient():
     with torch.autocast('cuda', dtype=torch.float16):
         rgb = m.color(torch.zeros(8, 3, device='cuda'), d, mask=torch.zeros(8, dtype=torch.bool, device='cuda'), geo_feat=geo)
     assert float(rgb.abs().max()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Every activation (0 ReLU, 1 Exp, 2 Sine, 3 Sigmoid, 4 Squareplus, 5 Softplus, 6 None) through forward, inference and backward.
+# Cases, data and reference values: tests/ffmlp_act_cases.py (the same table tests/test_ffmlp_activations.py checks on the CPU).
+#
+# Which test launches which kernel with activation != 0, each at B = 128 (4 tiles, one workgroup, direct weight-gradient store) and
+# B = 4224 (132 tiles, 33 workgroups, fp32 slabs + k_ffmlp_reduce_slabs; several chunks in the layered path with a workspace):
+#   test_activation_backward_register_resident   k_ffmlp_backward_paired<W, J, 1|2, false> and k_ffmlp_backward<W, J, 3, false>,
+#                                                W in {32, 64}, J in {1, 2} (the comment column of FAST_SHAPES names each)
+#   test_activation_backward_single_wave         k_ffmlp_backward<64,1,1,*>, <64,2,2,*>, <32,1,2,*>, <32,2,1,*> (NGP_FF_SINGLE_WAVE)
+#   test_activation_backward_layered             k_ffmlp_dgrad_layered<16|32|64|128|256, false>, k_ffmlp_wgrad, k_ffmlp_reduce_slabs
+#   test_activation_forward_and_inference        k_ffmlp_forward<16|32|64, *, false>, k_ffmlp_forward_wide<128, *, false>,
+#                                                k_ffmlp_forward_layered<256|64, *> (256-wide, 6 layers, 96 inputs, NGP_FF_LAYERED)
+#
+# Bars.  There are no ReLU mask flips for activations 1-6, so EVERY element is held to the bar:
+#   dL/dx          |got - ref| <= 4e-3 (|ref| + max |ref|)
+#   dL/dW          per matrix: relative L2 < 2e-3 and max error < 3e-3 of the maximum
+#   forward        rtol = atol / max |ref| = 3e-3 (__expf / __sinf / __logf), 1e-3 with ReLU hidden layers and no output activation
+# The reference's own noise is measured per case (ffmlp_act_cases.backward_case: the float32 oracle against the float64 one at the
+# same rounding points, 1e-4 .. 5e-4 of max |dx| -- one flipped fp16 rounding); a case whose 4 x floor exceeds a bar is held to
+# 4 x its floor instead.  On the table as it stands no case needs that (EXPERIMENTS.md, "FFMLP activations parity").
+# ------------------------------------------------------------------------------------------------------------------------------
+import ffmlp_act_cases as C
+
+
+def _capi():
+    import _ngp_capi as capi
+    return capi
+
+
+def _forward_capi(xt, wt, B, din, hid, nl, act, out_act, flags, train=True):
+    capi = _capi()
+    out = torch.empty(B, 16, device='cuda', dtype=torch.half)
+    if train:
+        fb = torch.empty(nl, B, hid, device='cuda', dtype=torch.half)
+        capi.check(capi.lib.ngp_ffmlp_forward_ex(xt.data_ptr(), wt.data_ptr(), B, din, 16, hid, nl, act, out_act, fb.data_ptr(), out.data_ptr(), flags,
+                                                 capi.stream()))
+        return out, fb
+    scratch = torch.empty(B, hid, device='cuda', dtype=torch.half)
+    capi.check(capi.lib.ngp_ffmlp_inference_ex(xt.data_ptr(), wt.data_ptr(), B, din, 16, hid, nl, act, out_act, scratch.data_ptr(), out.data_ptr(), flags,
+                                               capi.stream()))
+    return out, None
+
+
+def _backward_capi(gt, xt, wt, fb, B, din, hid, nl, act, out_act=6, flags=0, workspace=False, with_dx=True):
+    """-> (grad_inputs fp16 tensor, grad_weights fp16 tensor); the outputs start as NaN so that anything left unwritten shows"""
+    capi = _capi()
+    gi = torch.full((B, din), float('nan'), device='cuda', dtype=torch.half)
+    gw = torch.full((C.n_params(din, hid, nl),), float('nan'), device='cuda', dtype=torch.half)
+    bb = torch.zeros(nl, B, hid, device='cuda', dtype=torch.half)
+    ws, nbytes = None, 0
+    if workspace:
+        nbytes = capi.lib.ngp_ffmlp_backward_workspace_bytes(B, din, hid, nl)
+        assert nbytes > 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
+    capi.check(capi.lib.ngp_ffmlp_backward_ws(gt.data_ptr(), xt.data_ptr(), wt.data_ptr(), fb.data_ptr(), B, din, 16, hid, nl, act, out_act,
+                                              1 if with_dx else 0, bb.data_ptr(), gi.data_ptr(), gw.data_ptr(), flags,
+                                              ws.data_ptr() if ws is not None else None, nbytes, capi.stream()))
+    torch.cuda.synchronize()
+    return gi, gw
+
+
+def _forward_bar(act, out_act):
+    return 1e-3 if act == 0 and out_act == 6 else 3e-3
+
+
+def _check_forward(out, ref, act, out_act, label):
+    got = out.float().cpu().numpy()
+    tol = _forward_bar(act, out_act)
+    scale = np.abs(ref).max()
+    err = np.abs(got - ref) / (np.abs(ref) + scale)
+    print(f'PARITY fwd {label}: max |err| / (|ref| + max) {err.max():.2e} (bar {tol:.0e})')
+    np.testing.assert_allclose(got, ref, rtol=tol, atol=tol * scale)
+
+
+def _check_backward(gi, gw, c, din, hid, nl, act, label):
+    """dL/dx and every weight-gradient matrix against the oracle values of case c, every element (activations 1-6), or with the ReLU
+    mask-flip allowance of test_forward_inference_backward (activation 0)"""
+    gx, gwn = gi.float().cpu().numpy(), gw.float().cpu().numpy()
+    assert np.isfinite(gx).all() and np.isfinite(gwn).all(), label
+    rgx, rgw = c['rgx'], c['rgw']
+    e_el, e_max = C.dx_errors(gx, rgx)
+    werr = C.w_errors(gwn, rgw, din, hid, nl)
+    print(f'PARITY bwd {label}: dx elem {e_el:.2e} max {e_max:.2e} floor {c["floor_dx"]:.1e} | dW L2 {max(w[0] for w in werr):.2e} '
+          f'max {max(w[1] for w in werr):.2e} floor {max(c["floor_w"]):.1e}')
+    if act == 0:
+        _close_except_relu_flips(gx, rgx, C.DX_TOL)
+        flips = max(1, nl - 1)
+        for l2, mx in werr:
+            assert mx < C.W_MAX * flips and l2 < C.W_L2 * flips, (label, werr)
+        return
+    amax = np.abs(rgx).max()
+    # a case may exceed the project bar only where 4 x the oracle's own float32-vs-float64 noise explains it
+    bound = np.maximum(C.DX_TOL * (np.abs(rgx) + amax), 4 * c['floor_dx'] * amax)
+    bad = np.abs(gx - rgx) > bound
+    assert not bad.any(), (label, int(bad.sum()), e_el, e_max)
+    for (l2, mx), fl in zip(werr, c['floor_w']):
+        assert l2 < max(C.W_L2, 4 * fl) and mx < max(C.W_MAX, 4 * fl), (label, werr)
+
+
+def _id(v):
+    return '-'.join(str(x) for x in v)
+
+
+@pytest.mark.parametrize('case', C.FAST_CASES, ids=_id)
+@pytest.mark.parametrize('B', C.BATCHES)
+def test_activation_backward_register_resident(case, B):
+    din, hid, nl, act = case
+    c = C.backward_case(din, hid, nl, act, B)
+    C.check_conditions(c, din, hid, nl)
+    label = f'fast {din}->{hid}x{nl} {C.ACT_NAMES[act]} B={B}'
+    out, fb, xt, wt = _run_forward(c['x'], c['w'], din, hid, nl, act=act)
+    _check_forward(out, c['ref'], act, 6, label)
+    gt = cu16(c['g'])
+    n_params = C.n_params(din, hid, nl)
+    gi = torch.full((B, din), float('nan'), device='cuda', dtype=torch.half)
+    gw = torch.full((n_params,), float('nan'), device='cuda', dtype=torch.half)
+    bb = torch.zeros(nl, B, hid, device='cuda', dtype=torch.half)
+    _be().ffmlp_backward(gt, xt, wt, fb, B, din, 16, hid, nl, act, 6, True, bb, gi, gw)
+    _check_backward(gi, gw, c, din, hid, nl, act, label)
+    # without dL/dx the weight gradients are unchanged and grad_inputs is not touched
+    gw2 = torch.full_like(gw, float('nan'))
+    dummy = torch.zeros(1, device='cuda', dtype=torch.half)
+    bb.zero_()
+    _be().ffmlp_backward(gt, xt, wt, fb, B, din, 16, hid, nl, act, 6, False, bb, dummy, gw2)
+    assert torch.equal(gw2, gw) and dummy.item() == 0
+
+
+@pytest.mark.parametrize('case', C.SINGLE_WAVE_CASES, ids=_id)
+@pytest.mark.parametrize('B', C.BATCHES)
+def test_activation_backward_single_wave(case, B):
+    """NGP_FF_SINGLE_WAVE runs k_ffmlp_backward<W, J, 1|2, *> where the paired kernel would: role 1 of the paired kernel walks the same dgrad
+    chain with the same MFMA sequence per output, so dL/dx is bit-identical; the weight gradients differ in fp32 summation order only."""
+    din, hid, nl, act = case
+    capi = _capi()
+    c = C.backward_case(din, hid, nl, act, B)
+    C.check_conditions(c, din, hid, nl)
+    label = f'single-wave {din}->{hid}x{nl} {C.ACT_NAMES[act]} B={B}'
+    xt, wt, gt = cu16(c['x']), cu16(c['w']), cu16(c['g'])
+    out, fb = _forward_capi(xt, wt, B, din, hid, nl, act, 6, 0)
+    gi_p, gw_p = _backward_capi(gt, xt, wt, fb, B, din, hid, nl, act)
+    gi_s, gw_s = _backward_capi(gt, xt, wt, fb, B, din, hid, nl, act, flags=capi.NGP_FF_SINGLE_WAVE)
+    _check_backward(gi_s, gw_s, c, din, hid, nl, act, label)
+    assert torch.equal(gi_s, gi_p)
+    a, b = gw_s.float().cpu().numpy(), gw_p.float().cpu().numpy()
+    assert np.abs(a - b).max() <= 2e-3 * np.abs(b).max()
+
+
+@pytest.mark.parametrize('case', C.LAYERED_CASES, ids=_id)
+@pytest.mark.parametrize('B', C.BATCHES)
+def test_activation_backward_layered(case, B):
+    """once with the workspace ngp_ffmlp_backward_workspace_bytes asks for (sample chunks + k_ffmlp_reduce_slabs where B allows more than
+    one chunk) and once with NULL (one chunk, direct store): both against the oracle, and against each other to fp32 summation order"""
+    din, hid, nl, act, forced = case
+    capi = _capi()
+    flags = capi.NGP_FF_LAYERED if forced else 0
+    c = C.backward_case(din, hid, nl, act, B)
+    C.check_conditions(c, din, hid, nl)
+    label = f'layered{"(forced)" if forced else ""} {din}->{hid}x{nl} {C.ACT_NAMES[act]} B={B}'
+    xt, wt, gt = cu16(c['x']), cu16(c['w']), cu16(c['g'])
+    out, fb = _forward_capi(xt, wt, B, din, hid, nl, act, 6, flags)
+    _check_forward(out, c['ref'], act, 6, label)
+    n_params = C.n_params(din, hid, nl)
+    res = []
+    for with_ws in (True, False):
+        if forced:   # (the workspace query answers 0 for a shape the register-resident kernels serve: size it as the layered path does)
+            gi = torch.full((B, din), float('nan'), device='cuda', dtype=torch.half)
+            gw = torch.full((n_params,), float('nan'), device='cuda', dtype=torch.half)
+            bb = torch.zeros(nl, B, hid, device='cuda', dtype=torch.half)
+            nbytes = 64 * n_params * 4 if with_ws else 0
+            ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda') if with_ws else None
+            capi.check(capi.lib.ngp_ffmlp_backward_ws(gt.data_ptr(), xt.data_ptr(), wt.data_ptr(), fb.data_ptr(), B, din, 16, hid, nl, act, 6, 1,
+                                                      bb.data_ptr(), gi.data_ptr(), gw.data_ptr(), flags, ws.data_ptr() if with_ws else None, nbytes,
+                                                      capi.stream()))
+            torch.cuda.synchronize()
+        else:
+            gi, gw = _backward_capi(gt, xt, wt, fb, B, din, hid, nl, act, flags=flags, workspace=with_ws)
+        _check_backward(gi, gw, c, din, hid, nl, act, label + (' ws' if with_ws else ' no-ws'))
+        res.append((gi, gw.float().cpu().numpy()))
+    assert torch.equal(res[0][0], res[1][0])
+    assert np.abs(res[0][1] - res[1][1]).max() <= 2e-3 * np.abs(res[1][1]).max()
+    if forced:   # the register-resident kernels run the same MFMA sequence per output: dL/dx bit for bit, dW to fp32 summation order
+        out_r, fb_r = _forward_capi(xt, wt, B, din, hid, nl, act, 6, 0)
+        assert torch.equal(out_r, out) and torch.equal(fb_r, fb)
+        gi_r, gw_r = _backward_capi(gt, xt, wt, fb_r, B, din, hid, nl, act)
+        assert torch.equal(gi_r, res[0][0])
+        assert np.abs(gw_r.float().cpu().numpy() - res[1][1]).max() <= 2e-3 * np.abs(res[1][1]).max()
+
+
+@pytest.mark.parametrize('case', C.OUT_ACT_IGNORED_CASES, ids=_id)
+def test_backward_ignores_output_activation(case):
+    """the backward takes grad as dL/d(what the output layer's matmul produced): output_activation is a forward-only argument, as in the
+    reference (ffmlp.cu:780)"""
+    din, hid, nl, act, _ = case
+    B = 128
+    c = C.backward_case(din, hid, nl, act, B)
+    C.check_conditions(c, din, hid, nl)
+    xt, wt, gt = cu16(c['x']), cu16(c['w']), cu16(c['g'])
+    out, fb = _forward_capi(xt, wt, B, din, hid, nl, act, 6, 0)
+    res = [_backward_capi(gt, xt, wt, fb, B, din, hid, nl, act, out_act=oa) for oa in (0, 3, 6)]
+    _check_backward(res[2][0], res[2][1], c, din, hid, nl, act, f'out_act {din}->{hid}x{nl} {C.ACT_NAMES[act]}')
+    for gi, gw in res[:2]:
+        assert torch.equal(gi, res[2][0]) and torch.equal(gw, res[2][1])
+
+
+@pytest.mark.parametrize('case', C.FORWARD_CASES, ids=_id)
+@pytest.mark.parametrize('B', C.BATCHES)
+def test_activation_forward_and_inference(case, B):
+    """training forward against the oracle, inference bit-identical with it, and -- where the register-resident kernel serves the shape --
+    the layered kernel (NGP_FF_LAYERED) bit-identical with the register-resident one"""
+    din, hid, nl, act, out_act, forced = case
+    capi = _capi()
+    c = C.forward_case(din, hid, nl, act, out_act, B)
+    C.check_forward_conditions(c)
+    label = f'{din}->{hid}x{nl} {C.ACT_NAMES[act]}/{C.ACT_NAMES[out_act]}{" layered(forced)" if forced else ""} B={B}'
+    xt, wt = cu16(c['x']), cu16(c['w'])
+    flags = capi.NGP_FF_LAYERED if forced else 0
+    out, _ = _forward_capi(xt, wt, B, din, hid, nl, act, out_act, flags)
+    _check_forward(out, c['ref'], act, out_act, label)
+    out_i, _ = _forward_capi(xt, wt, B, din, hid, nl, act, out_act, flags, train=False)
+    assert torch.equal(out_i, out)
+    if forced:
+        out_r, _ = _forward_capi(xt, wt, B, din, hid, nl, act, out_act, 0)
+        out_ri, _ = _forward_capi(xt, wt, B, din, hid, nl, act, out_act, 0, train=False)
+        assert torch.equal(out_r, out) and torch.equal(out_ri, out)
+    # the pybind entry points take the same route
+    out_p, _, _, _ = _run_forward(c['x'], c['w'], din, hid, nl, act=act, out_act=out_act)
+    if not forced:
+        assert torch.equal(out_p, out)
+
+
+def test_module_with_sigmoid_activation():
+    """FFMLP(32, 3, 64, 3, activation='sigmoid') under autocast: y, x.grad and weights.grad against the oracle; eval() takes the inference
+    kernel and must agree bit for bit"""
+    from ffmlp import FFMLP
+    din, hid, nl, act = C.MODULE_CASE
+    B, dout = C.MODULE_B, C.MODULE_OUT
+    c = C.backward_case(din, hid, nl, act, B, dout)
+    C.check_conditions(c, din, hid, nl)
+    net = FFMLP(din, dout, hid, nl, activation='sigmoid').cuda()
+    assert net.activation == 3 and net.weights.numel() == c['w'].size
+    with torch.no_grad():
+        net.weights.copy_(torch.tensor(c['w']))
+    x = torch.tensor(c['x']).cuda().requires_grad_(True)
+    with torch.autocast('cuda', dtype=torch.float16):
+        y = net(x)
+    assert y.dtype == torch.float16 and y.shape == (B, dout)
+    _check_forward(y.detach(), c['ref'][:, :dout], act, 6, 'module sigmoid')
+    # the kernels see the padded 16-column output gradient: columns dout..15 of the case's g are zero
+    y.backward(cu16(c['g'][:, :dout]))
+    _check_backward(x.grad, net.weights.grad, c, din, hid, nl, act, 'module sigmoid')
+    net.eval()
+    with torch.no_grad(), torch.autocast('cuda', dtype=torch.float16):
+        y2 = net(x)
+    assert torch.equal(y2, y.detach())
