@@ -532,6 +532,22 @@ __device__ __forceinline__ void atomic_add_half1(half_t* p, float a) {
     } while (old != assumed);
 }
 
+// Two adjacent fp16 values with ONE rounding per add (the packed atomic takes an fp16 addend: the addend is rounded, then the sum -- two
+// roundings): a 32-bit CAS on the pair's word, each half added in fp32 and rounded once.  p is 4-byte aligned (an even channel of an even-C row).
+__device__ __forceinline__ void atomic_add_pair_once(half_t* p, float a, float b) {
+    uint32_t* word = reinterpret_cast<uint32_t*>(p);
+    uint32_t old = *word, assumed;
+    do {
+        assumed = old;
+        half_t lo = __builtin_bit_cast(half_t, (uint16_t)(assumed & 0xFFFFu));
+        half_t hi = __builtin_bit_cast(half_t, (uint16_t)(assumed >> 16));
+        lo = (half_t)((float)lo + a);
+        hi = (half_t)((float)hi + b);
+        const uint32_t nw = (uint32_t)__builtin_bit_cast(uint16_t, lo) | ((uint32_t)__builtin_bit_cast(uint16_t, hi) << 16);
+        old = atomicCAS(word, assumed, nw);
+    } while (old != assumed);
+}
+
 template <typename T, int C>
 __device__ __forceinline__ void scatter_add(T* dst, const float (&g)[C], float w) {
     if constexpr (sizeof(T) == 2) {
@@ -1716,7 +1732,13 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grad_tv(const T* __restrict__ i
         float upd[C];
 #pragma unroll
         for (int c = 0; c < C; c++) upd[c] = w * res[c] * rsqrtf(idelta[c] + 1e-9f);
-        scatter_add<T, C>(gtable + idx, upd, 1.0f);
+        // (the update is some 1e-3 of the weight and the gradient it joins is small too: on an fp16 table every add rounds ONCE, also with even C)
+        if constexpr (sizeof(T) == 2 && C % 2 == 0) {
+#pragma unroll
+            for (int c = 0; c < C; c += 2) atomic_add_pair_once(reinterpret_cast<half_t*>(gtable + idx) + c, upd[c], upd[c + 1]);
+        } else {
+            scatter_add<T, C>(gtable + idx, upd, 1.0f);
+        }
     }
 }
 
