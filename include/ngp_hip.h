@@ -403,6 +403,25 @@ int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const void* weig
                           uint32_t output_activation, int calc_grad_inputs, void* backward_buffer, void* grad_inputs, void* grad_weights,
                           uint32_t flags, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
 
+/* Second order (no reference counterpart): the backward of ngp_ffmlp_backward's outputs with respect to the upstream gradient `u`
+ * [B,input_dim] of grad_inputs -- what torch.autograd.grad(..., create_graph=True) on a loss of d y / d x (eikonal, normals) needs;
+ * DESIGN.md 3.7 has the formulas.  grad [B,16], inputs [B,input_dim], weights, u: fp16 row-major; forward_buffer as ngp_ffmlp_forward*
+ * left it (private layout).  Outputs, all fp16, all written (not accumulated), each nullable -- a NULL output skips the terms that
+ * feed only it:
+ *   grad_grad     [B,16]        d loss / d grad
+ *   grad_weights2 [n_params]    d loss / d weights, the layout of `weights`; bit-reproducible (fp32 slabs, one fixed-order reduction)
+ *   grad_inputs2  [B,input_dim] d loss / d inputs; exactly zero for ReLU, Sine and None (written as zeros)
+ * The terms with respect to the upstream gradient of grad_weights are not provided.  Every width runs the layered kernels; the
+ * workspace (ngp_ffmlp_backward_backward_workspace_bytes(...) bytes, 256-byte aligned) holds the recomputed hidden gradients, the
+ * tangents and the weight-gradient slabs.  B a multiple of 128 (0: no-op), output_dim 16.  A bad shape, a NULL grad / inputs /
+ * weights / forward_buffer / u or a short workspace: NGP_ERR_INVALID before anything is launched. */
+size_t ngp_ffmlp_backward_backward_workspace_bytes(uint32_t B, uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers,
+                                                   uint32_t activation);
+int ngp_ffmlp_backward_backward(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, const void* u,
+                                uint32_t B, uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers,
+                                uint32_t activation, void* grad_grad, void* grad_weights2, void* grad_inputs2, void* workspace,
+                                size_t workspace_bytes, ngp_stream_t stream);
+
 /* The whole network of nerf/network_ff.py:51-74 behind the encoder in ONE launch (64-wide ReLU networks with 32 inputs, the instant-ngp
  * configuration): sigma FFMLP -> trunc_exp / SH(4) / feature shuffle -> colour FFMLP -> sigmoid.  enc: the encoder output, [M,32] fp16
  * row-major or (flags & NGP_FF_INPUT_PLANAR) the encoder's own [16][M][2] layout; dirs [M_valid,3] fp32 (rows >= M_valid use dir = 0);

@@ -90,6 +90,7 @@ _SIGNATURES = {
     'ngp_ffmlp_inference_ex': [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp],
     'ngp_ffmlp_backward_ex': [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _u32, _vp],
     'ngp_ffmlp_backward_ws': [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _i32, _vp, _vp, _vp, _u32, _vp, _sz, _vp],
+    'ngp_ffmlp_backward_backward': [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _sz, _vp],
     'ngp_network_forward': [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     'ngp_network_forward_rows': [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp],
     'ngp_march_rays_dev_rows': [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp],
@@ -135,6 +136,8 @@ lib.ngp_march_rays_train_workspace_bytes.restype = _sz
 lib.ngp_compact_rays_workspace_bytes.argtypes = [_u32]
 lib.ngp_ffmlp_backward_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32]
 lib.ngp_ffmlp_backward_workspace_bytes.restype = _sz
+lib.ngp_ffmlp_backward_backward_workspace_bytes.argtypes = [_u32, _u32, _u32, _u32, _u32]
+lib.ngp_ffmlp_backward_backward_workspace_bytes.restype = _sz
 lib.ngp_grid_backward_workspace_bytes.argtypes = [_vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _i32]
 lib.ngp_grid_backward_workspace_bytes.restype = _sz
 lib.ngp_grid_backward_backward_workspace_bytes.argtypes = [_vp, _u32, _u32, _u32, _u32, _i32]
@@ -159,7 +162,7 @@ EXPORTED = sorted(list(_SIGNATURES) + ['ngp_last_error', 'ngp_target_arch', 'ngp
                                        'ngp_grid_backward_workspace_bytes', 'ngp_ffmlp_backward_workspace_bytes',
                                        'ngp_ffmlp_backward_slab_count', 'ngp_density_grid_update_workspace_bytes', 'ngp_grid_forward_work_lists', 'ngp_coarse_occupancy_bytes',
                                        'ngp_grid_table_adam_prefix', 'ngp_linear_stack_flat_size',
-                                       'ngp_grid_backward_backward_workspace_bytes'])
+                                       'ngp_grid_backward_backward_workspace_bytes', 'ngp_ffmlp_backward_backward_workspace_bytes'])
 
 
 def check(rc):

@@ -2336,3 +2336,5 @@ extern "C" int ngp_free_splitk(void) {
     g_splitk_request = 0;
     return NGP_OK;
 }
+
+#include "ffmlp_second.inc"  // second order: ngp_ffmlp_backward_backward
