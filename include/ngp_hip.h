@@ -10,9 +10,9 @@
  *   - at::optional<at::Tensor> becomes a pointer that may be NULL;
  *   - the element type that the reference dispatches on (AT_DISPATCH_FLOATING_TYPES_AND_HALF) is an
  *     explicit `dtype` code.  NGP_F64 is accepted by the grid encoder (forward, backward -- with a workspace --,
- *     total variation) and the SH encoder; the raymarching entries take float* and have *_f64 twins for the
- *     compositors, near_far_from_aabb, sph_from_ray and packbits.  Every other entry refuses fp64 with
- *     NGP_ERR_INVALID (the marchers, ffmlp, freq encoder, fused / graph / optimizer entries);
+ *     total variation) and the SH encoder; the raymarching entries and the frequency encoder take float* and have
+ *     *_f64 twins (the compositors, near_far_from_aabb, sph_from_ray, packbits; freq_encode forward / backward).
+ *     Every other entry refuses fp64 with NGP_ERR_INVALID (the marchers, ffmlp, fused / graph / optimizer entries);
  *   - a trailing `stream` (a hipStream_t passed as void*; NULL = the legacy default stream the
  *     reference launches on);
  *   - every function returns 0 on success and a non-zero NGP_ERR_* code on failure, with a
@@ -129,6 +129,14 @@ int ngp_sh_encode_forward(const void* inputs, void* outputs, uint32_t B, uint32_
 /* replaces sh_encode_backward (shencoder.cu:419-439): grad_inputs[b,d] += sum_ch grad[b,ch]*dy_dx[b,d,ch] */
 int ngp_sh_encode_backward(const void* grad, const void* inputs, uint32_t B, uint32_t D, uint32_t C,
                            const void* dy_dx, void* grad_inputs, int dtype, ngp_stream_t stream);
+/* EXTENSION, the backward of sh_encode_backward (shencoder.cu:419-439) for a loss on grad_inputs (torch.autograd.grad(..., create_graph=True)):
+ * u [B,3] = d loss / d grad_inputs; grad [B,C*C], inputs [B,3] and dy_dx [B,3*C*C] as the first backward saw them.
+ *   grad_grad    [B,C*C]  sum_d u_d dy_dx[b,d,i]                                   (NULL: not computed)
+ *   grad_inputs2 [B,3]    sum_i grad_i sum_d u_d d2Y_i/dx_d dx_e                   (NULL: not computed; zeros for C <= 2)
+ * Both are overwritten, deterministic, no atomics.  dtype F32 or F64 (F16: NGP_ERR_INVALID, "second order is provided for float32 and
+ * float64").  D must be 3, C in 1..8; NULL grad / inputs / dy_dx / u: NGP_ERR_INVALID (B == 0 is a no-op). */
+int ngp_sh_encode_backward_backward(const void* grad, const void* inputs, const void* dy_dx, const void* u, uint32_t B, uint32_t D,
+                                    uint32_t C, void* grad_grad, void* grad_inputs2, int dtype, ngp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * raymarching      (reference: raymarching/src/raymarching.h:7-18, bindings.cpp:5-19)
@@ -630,7 +638,7 @@ int ngp_composite_train_loss_backward(const float* sigmas, const float* rgbs, co
                                       void* grad_out16, void* march_workspace, size_t march_workspace_bytes, ngp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * freqencoder       (reference: freqencoder/src/freqencoder.h:6-10, bindings.cpp:5-8) -- SURVEY.md 8(f).3, fp32 only.
+ * freqencoder       (reference: freqencoder/src/freqencoder.h:6-10, bindings.cpp:5-8) -- SURVEY.md 8(f).3; fp32, *_f64 twins.
  * outputs [B,C], C = D + 2*D*deg: x | per frequency f: sin(2^f x_d) for all d, then cos(2^f x_d) for all d.
  * --------------------------------------------------------------------------------------------- */
 /* replaces freq_encode_forward (freqencoder.cu:97-111) */
@@ -639,6 +647,20 @@ int ngp_freq_encode_forward(const float* inputs, uint32_t B, uint32_t D, uint32_
 /* replaces freq_encode_backward (freqencoder.cu:114-131): grad [B,C], outputs [B,C] (saved), grad_inputs [B,D] overwritten */
 int ngp_freq_encode_backward(const float* grad, const float* outputs, uint32_t B, uint32_t D, uint32_t deg, uint32_t C,
                              float* grad_inputs, ngp_stream_t stream);
+/* EXTENSION of freq_encode_forward (freqencoder.cu:97-111) to float64: the same kernel on double, cos as sin(. + pi/2) in double */
+int ngp_freq_encode_forward_f64(const double* inputs, uint32_t B, uint32_t D, uint32_t deg, uint32_t C, double* outputs,
+                                ngp_stream_t stream);
+/* EXTENSION of freq_encode_backward (freqencoder.cu:114-131) to float64 */
+int ngp_freq_encode_backward_f64(const double* grad, const double* outputs, uint32_t B, uint32_t D, uint32_t deg, uint32_t C,
+                                 double* grad_inputs, ngp_stream_t stream);
+/* EXTENSION, the backward of freq_encode_backward (freqencoder.cu:114-131) for a loss on grad_inputs (torch.autograd.grad(...,
+ * create_graph=True)): u [B,D] = d loss / d grad_inputs; grad [B,C] and outputs [B,C] as the first backward saw them.
+ *   grad_grad    [B,C]  identity block u_d; sin slot 2^f u_d cos[f,d]; cos slot -2^f u_d sin[f,d]      (NULL: not computed)
+ *   grad_inputs2 [B,D]  -u_d sum_f 4^f (g_sin[f,d] sin[f,d] + g_cos[f,d] cos[f,d])                       (NULL: not computed)
+ * Both are overwritten, deterministic, no atomics.  dtype F32 or F64 (all five tensors).  A wrong C, a dtype other than F32 / F64, a
+ * NULL grad / outputs / u: NGP_ERR_INVALID (B == 0 is a no-op). */
+int ngp_freq_encode_backward_backward(const void* grad, const void* outputs, const void* u, uint32_t B, uint32_t D, uint32_t deg,
+                                      uint32_t C, void* grad_grad, void* grad_inputs2, int dtype, ngp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused optimizer + loss-scaling step -- EXTENSION: replaces torch.optim.Adam + GradScaler.step/update

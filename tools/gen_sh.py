@@ -3,6 +3,8 @@
  (a) oracle/sh_table.inc          -- double precision, un-optimised, one expression per line
  (b) torch-ngp_amd/csrc/sh_poly.inc -- fp32 device code, common sub-expressions shared
  (c) torch-ngp_amd/csrc/sh_poly64.inc -- the same device tables in double precision (fp64.hip)
+ (d) torch-ngp_amd/csrc/sh_hess.inc / sh_hess64.inc -- the second partial derivatives (fp32 / fp64 literals) for the second-order
+     backward (csrc/encoder_second.hip), by symbolic differentiation through the same c_expr / expand_pows path
 
 The 64 basis polynomials (bands 0..7) are the Cartesian forms the reference evaluates
 (reference: shencoder/src/shencoder.cu:50-120, closed forms given in its trailing comments);
@@ -15,8 +17,9 @@ The value polynomials are pinned independently in tests/test_oracle_sh.py agains
 scipy.special.sph_harm (all 64, unit vectors) and against golden vectors produced by the
 reference's own pure-torch SHEncoder_torch (testing/test_shencoder.py:8-89, bands 0..4).
 
-Run:  python tools/gen_sh.py       (rewrites the three .inc files in place; needs sympy)
+Run:  python tools/gen_sh.py       (rewrites the five .inc files in place; needs sympy)
 """
+import functools
 import os
 import sympy as sp
 
@@ -108,14 +111,20 @@ def basis():
     return Y
 
 
-def c_expr(e, suffix):
-    """C expression for a sympy polynomial with all numeric factors evaluated to 17 digits."""
+@functools.lru_cache(maxsize=None)
+def _double_code(e):
+    """(the float and the double table of one polynomial share this step)"""
     e = sp.nsimplify(e)
     e = sp.expand(e)
     # Horner in z then y then x keeps the operation count and rounding modest
     e = sp.horner(e, z, y, x) if e.free_symbols else e
     e = e.evalf(17)
-    code = sp.ccode(e)
+    return sp.ccode(e)
+
+
+def c_expr(e, suffix):
+    """C expression for a sympy polynomial with all numeric factors evaluated to 17 digits."""
+    code = _double_code(sp.sympify(e))
     if suffix:
         # turn every floating literal into a float literal
         import re
@@ -137,9 +146,29 @@ def expand_pows(code):
     return pat.sub(rep, code)
 
 
-def main():
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
+HESSIAN = (('XX', 0, 0), ('XY', 0, 1), ('XZ', 0, 2), ('YY', 1, 1), ('YZ', 1, 2), ('ZZ', 2, 2))
+
+
+def hessian_lines(Y, prefix, suffix):
+    """per-band macros <prefix>_BAND_k_HESS: the six distinct second partial derivatives of every basis polynomial, component by component
+    in the order XX, XY, XZ, YY, YZ, ZZ; an entry that is identically zero is not emitted (the includer adds nothing for it)."""
+    v = (x, y, z)
+    dl = []
+    for band in range(8):
+        dl.append('#define %s_BAND_%d_HESS \\' % (prefix, band))
+        for i in range(band * band, (band + 1) * (band + 1)):
+            for name, a, b in HESSIAN:
+                h = sp.expand(sp.diff(Y[i], v[a], v[b]))
+                if h != 0:
+                    dl.append('    SH_H%s(%d, %s); \\' % (name, i, expand_pows(c_expr(h, suffix))))
+        dl.append('    ((void)0)')
+    return dl
+
+
+def main(root=None):
+    """root: the tree to write into (default: the repository this file lies in); oracle/ and torch-ngp_amd/csrc/ must exist there."""
+    if root is None:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     Y = basis()
     dY = [[sp.diff(Yi, v) for Yi in Y] for v in (x, y, z)]
 
@@ -196,7 +225,15 @@ def main():
         dl.append('    ((void)0)')
     with open(os.path.join(root, 'torch-ngp_amd', 'csrc', 'sh_poly64.inc'), 'w') as f:
         f.write('\n'.join(dl) + '\n')
-    print('wrote oracle/sh_table.inc, torch-ngp_amd/csrc/sh_poly.inc and torch-ngp_amd/csrc/sh_poly64.inc')
+    # ---------------- device: second partial derivatives (csrc/encoder_second.hip), float and double ----------------
+    for name, prefix, suffix, kind in (('sh_hess.inc', 'SH', True, 'fp32'), ('sh_hess64.inc', 'SH64', False, 'fp64')):
+        dl = ['// GENERATED by tools/gen_sh.py -- do not edit.  %s second partial derivatives of the real SH basis, band by band,' % kind,
+              '// by symbolic differentiation of the value polynomials.  SH_HXX(i, v) / SH_HXY / SH_HXZ / SH_HYY / SH_HYZ / SH_HZZ are',
+              '// supplied by the includer (x, y, z %s); entries that are identically zero are left out.' % ('float' if suffix else 'double')]
+        dl += hessian_lines(Y, prefix, suffix)
+        with open(os.path.join(root, 'torch-ngp_amd', 'csrc', name), 'w') as f:
+            f.write('\n'.join(dl) + '\n')
+    print('wrote oracle/sh_table.inc, torch-ngp_amd/csrc/sh_poly.inc, sh_poly64.inc, sh_hess.inc and sh_hess64.inc')
 
 
 if __name__ == '__main__':

@@ -46,6 +46,10 @@ _SIGNATURES = {
     'ngp_sh_encode_backward': [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp],
     'ngp_freq_encode_forward': [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     'ngp_freq_encode_backward': [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
+    'ngp_freq_encode_forward_f64': [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
+    'ngp_freq_encode_backward_f64': [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
+    'ngp_freq_encode_backward_backward': [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _i32, _vp],
+    'ngp_sh_encode_backward_backward': [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp],
     'ngp_near_far_from_aabb': [_vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp],
     'ngp_sph_from_ray': [_vp, _vp, _f32, _u32, _vp, _vp],
     'ngp_morton3D': [_vp, _u32, _vp, _vp],
@@ -194,6 +198,16 @@ class TableAdam(ctypes.Structure):
     """ngp_table_adam_t (include/ngp_hip.h): the two buffer sets of a table whose Adam sweep rides in the grid backward's accumulate launch"""
     _fields_ = [('param', ctypes.c_void_p * 2), ('exp_avg', ctypes.c_void_p * 2), ('exp_avg_sq', ctypes.c_void_p * 2), ('param_fp16', ctypes.c_void_p * 2),
                 ('state', ctypes.c_void_p), ('lr', ctypes.c_float), ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float)]
+
+
+class CallerTensor:
+    """The tensor an encoder was called with, in a wrapper that custom_fwd's cast_inputs leaves alone (the cast replaces an autocast caller's
+    tensor by an fp32 copy that is not part of the graph): the second-order gradient with respect to the points goes there (DESIGN.md
+    3.8)."""
+    __slots__ = ('tensor',)
+
+    def __init__(self, tensor):
+        self.tensor = tensor
 
 
 def ptr(t):
