@@ -617,6 +617,34 @@ int ngp_composite_rays_train_backward_ex(const float* grad_weights_sum, const fl
                                          float T_thresh, float* grad_sigmas, float* grad_rgbs, int bg_mode, float bg_scalar,
                                          const float* bg, const uint32_t* rows_used, ngp_stream_t stream);
 
+/* EXTENSION of composite_rays_train_forward / _backward (raymarching.cu:501-577, 602-682) for geometry losses: the same compositing
+ * (weights_sum, depth and image are the bits of ngp_composite_rays_train_forward) plus, per ray, the distortion of
+ * loss.py::EffDistLoss on the compositor's own weights and distances,
+ *   distortion = sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 deltas[i,0],   t_i = sum_{j<=i} deltas[j,1],
+ * and a backward that propagates the gradients of ALL four outputs -- depth included, which ngp_composite_rays_train_backward drops as
+ * the reference does -- to sigmas and rgbs in one sweep.  distortion [N], written at row rays[n,0] like the others (0 for an empty ray
+ * and for one whose samples do not fit M).  Backward: each of grad_weights_sum [N], grad_depth [N], grad_image [N,3], grad_distortion
+ * [N] may be NULL (= zero); weights_sum, depth, image, distortion are the forward's outputs; grad_sigmas [M] / grad_rgbs [M,3] are
+ * written for composited rows only, the caller pre-zeroes them.  deltas and rays get no gradient. */
+int ngp_composite_rays_train_geo_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                         uint32_t N, float T_thresh, float* weights_sum, float* depth, float* image,
+                                         float* distortion, ngp_stream_t stream);
+int ngp_composite_rays_train_geo_backward(const float* grad_weights_sum, const float* grad_depth, const float* grad_image,
+                                          const float* grad_distortion, const float* sigmas, const float* rgbs, const float* deltas,
+                                          const int32_t* rays, const float* weights_sum, const float* depth, const float* image,
+                                          const float* distortion, uint32_t M, uint32_t N, float T_thresh, float* grad_sigmas,
+                                          float* grad_rgbs, ngp_stream_t stream);
+/* fp64 twins of the two entries above (raymarching.cu:501-577, 602-682, loss.py::EffDistLoss in double, one lane per ray): the same
+ * arguments with every floating tensor double, for torch.autograd.gradcheck */
+int ngp_composite_rays_train_geo_forward_f64(const double* sigmas, const double* rgbs, const double* deltas, const int32_t* rays,
+                                             uint32_t M, uint32_t N, float T_thresh, double* weights_sum, double* depth, double* image,
+                                             double* distortion, ngp_stream_t stream);
+int ngp_composite_rays_train_geo_backward_f64(const double* grad_weights_sum, const double* grad_depth, const double* grad_image,
+                                              const double* grad_distortion, const double* sigmas, const double* rgbs,
+                                              const double* deltas, const int32_t* rays, const double* weights_sum, const double* depth,
+                                              const double* image, const double* distortion, uint32_t M, uint32_t N, float T_thresh,
+                                              double* grad_sigmas, double* grad_rgbs, ngp_stream_t stream);
+
 /* The image-space middle of one TRAINING iteration in one launch (optional extension; what the four calls
  * ngp_composite_rays_train_forward_ex -> ngp_pipeline_mse_loss -> ngp_composite_rays_train_backward_ex -> ngp_pipeline_rgb_backward
  * compute, expression for expression: raymarching.cu:501-577 forward, renderer.py:316-318 finish, nerf/utils.py:516,557 loss,

@@ -1022,6 +1022,157 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_bwd(const flo
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// compositing for geometry losses (extension: raymarching.cu:501-577, 602-682 + loss.py::EffDistLoss): differentiable depth and the
+// mip-NeRF-360 distortion  L = sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 d0_i  in the same wave-per-ray scan
+// ---------------------------------------------------------------------------------------------
+// t is non-decreasing, so L = sum_i 2 w_i A_i + 1/3 sum_i w_i^2 d0_i with A_i = sum_{j<i} w_j (t_i - t_j) = t_i W_<i - D_<i (W_<i, D_<i: the
+// exclusive prefixes of w and w t).  A_i is scanned in the form that has no cancellation, A_i = sum_{k<=i} W_<k d1_k (each step of t
+// moves every weight in front of it): a sum of non-negative terms, where t_i W_<i - D_<i loses t_i / (t_i - t_j) in relative accuracy on
+// a long ray.
+// The distortion does not take its weights from the transmittance product.  alpha = 1 - __expf(-x) at a small optical depth x = sigma d0
+// carries the exponential's absolute error into a number 1 / x times smaller, and T = prod (1 - alpha_j) multiplies one rounded
+// exponential per sample: on a 300-sample ray weights_sum ends 4.5 ulp from its float64 value (measured), and L, of degree two in the
+// weights, 6 ulp.  weights_sum, depth and image keep those weights -- their expressions are k_composite_train_fwd's term for term, the
+// same bits -- but L is summed over weights from the log domain: T'_i = exp(-X_<i) with X the scanned optical depth (ONE exponential
+// per sample instead of a product of i), alpha'_i = -expm1(-x_i) (series below 1/4), w'_i = alpha'_i T'_i, W'_<k = 1 - T'_k (the weights
+// telescope; k_composite_train_bwd uses the same identity for its weights_sum term).  The live set is the shared one (T_thresh is
+// compared against the product).  Two scans more than k_composite_train_fwd (X, A).
+// 1 - exp(-x) = x - x^2/2 + x^3/6 - ... : the eighth term is below 2^-29 of the sum for |x| < 1/4
+__device__ __forceinline__ float one_minus_exp_neg(float x, float e) {  // e = exp(-x), used where the subtraction is harmless
+    float p = __builtin_fmaf(x, 1.0f / 5040.0f, -1.0f / 720.0f);
+    p = __builtin_fmaf(x, p, 1.0f / 120.0f);
+    p = __builtin_fmaf(x, p, -1.0f / 24.0f);
+    p = __builtin_fmaf(x, p, 1.0f / 6.0f);
+    p = __builtin_fmaf(x, p, -0.5f);
+    p = __builtin_fmaf(x, p, 1.0f);
+    return fabsf(x) < 0.25f ? x * p : 1.0f - e;
+}
+__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                                           const float* __restrict__ deltas, const int32_t* __restrict__ rays,
+                                                                           uint32_t M, uint32_t N, float T_thresh,
+                                                                           float* __restrict__ weights_sum, float* __restrict__ depth,
+                                                                           float* __restrict__ image, float* __restrict__ distortion) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    float r = 0, g = 0, b = 0, ws = 0, d = 0, dist = 0;
+    if (num != 0 && offset + num <= M) {
+        float T = 1.0f, tcarry = 0.0f, xcarry = 0.0f, acarry = 0.0f;  // transmittance / accumulated real-delta / optical depth / A before this row
+        for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+            const uint32_t s = s0 + lane;
+            const bool valid = s < num;
+            float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+            if (valid) {
+                sg = sigmas[offset + s];
+                const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
+                d0 = dl.x; d1 = dl.y;
+                cr = rgbs[(size_t)(offset + s) * 3];
+                cg = rgbs[(size_t)(offset + s) * 3 + 1];
+                cb = rgbs[(size_t)(offset + s) * 3 + 2];
+            }
+            const float e = __expf(-sg * d0);
+            const float alpha = valid ? 1.0f - e : 0.0f;
+            const float om = 1.0f - alpha;
+            const float pin = wave_incl_prod(om, lane);
+            const float T_before = T * prev_lane(1.0f, pin);
+            const float tt = tcarry + wave_incl_sum(d1, lane);
+            const bool live = valid && !(T_before < T_thresh);
+            const float w = live ? alpha * T_before : 0.0f;
+            r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
+            // the distortion's own weights (invalid lanes: sg = d0 = d1 = 0)
+            const float x = sg * d0;
+            const float xa = xcarry + wave_incl_sum(x, lane);         // X_<=i
+            const float Tq = __expf(-prev_lane(xcarry, xa));          // T'_i = exp(-X_<i)
+            const float wq = live ? one_minus_exp_neg(x, e) * Tq : 0.0f;
+            const float a = acarry + wave_incl_sum((1.0f - Tq) * d1, lane);  // A_i (lanes behind the stop: w' = 0)
+            dist += 2.0f * wq * a + (1.0f / 3.0f) * (wq * wq * d0);
+            T = T * lane63(pin);
+            tcarry = lane63(tt);
+            xcarry = lane63(xa);
+            acarry = lane63(a);
+            if (T < T_thresh) break;  // wave-uniform
+        }
+        r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d); dist = wave_total(dist);
+    }
+    if (lane == 0) {
+        weights_sum[index] = ws;
+        depth[index] = d;
+        image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+        distortion[index] = dist;
+    }
+}
+
+// Backward of the four outputs in ONE sweep.  With g_i = dL/dw_i = 2 (t_i W_<i - D_<i) + 2 ((D - D_<=i) - t_i (W - W_<=i)) + 2/3 w_i d0_i:
+//   dD/dsigma_i = d0_i (T_{i+1} t_i - (D - D_<=i))                 (the colour term of k_composite_train_bwd with t as the colour)
+//   dL/dsigma_i = d0_i (g_i T_{i+1} - (G - G_<=i)),  G = sum_j g_j w_j = 2 L   (L is homogeneous of degree 2 in w)
+// so every ray total is a saved forward output and nothing is swept twice.  Three scans more than k_composite_train_bwd (t, D, G); its
+// grad_sigmas sum is kept term for term and the two new terms are added to it: with zero grad_depth / grad_distortion the same bits.
+// A NULL gradient pointer is a zero gradient.  Writes live rows only (the caller pre-zeroes, as for ngp_composite_rays_train_backward).
+__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_bwd(const float* __restrict__ grad_ws, const float* __restrict__ grad_depth,
+                                                                           const float* __restrict__ grad_image, const float* __restrict__ grad_dist,
+                                                                           const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                                           const float* __restrict__ deltas, const int32_t* __restrict__ rays,
+                                                                           const float* __restrict__ weights_sum, const float* __restrict__ depth,
+                                                                           const float* __restrict__ image, const float* __restrict__ distortion,
+                                                                           uint32_t M, uint32_t N, float T_thresh, float* __restrict__ grad_sigmas,
+                                                                           float* __restrict__ grad_rgbs) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    if (num == 0 || offset + num > M) return;
+    const float gi0 = grad_image ? grad_image[index * 3] : 0.0f, gi1 = grad_image ? grad_image[index * 3 + 1] : 0.0f,
+                gi2 = grad_image ? grad_image[index * 3 + 2] : 0.0f;
+    const float gw = grad_ws ? grad_ws[index] : 0.0f, gd = grad_depth ? grad_depth[index] : 0.0f, gl = grad_dist ? grad_dist[index] : 0.0f;
+    const float rf = image[index * 3], gf = image[index * 3 + 1], bf = image[index * 3 + 2], wsf = weights_sum[index];
+    const float df = depth[index], gtot = 2.0f * distortion[index];
+    float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f, tcarry = 0.0f, dcarry = 0.0f, gcarry = 0.0f;  // carries from previous rows
+    for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        const bool valid = s < num;
+        float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+        if (valid) {
+            sg = sigmas[offset + s];
+            const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
+            d0 = dl.x; d1 = dl.y;
+            cr = rgbs[(size_t)(offset + s) * 3];
+            cg = rgbs[(size_t)(offset + s) * 3 + 1];
+            cb = rgbs[(size_t)(offset + s) * 3 + 2];
+        }
+        const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
+        const float pin = wave_incl_prod(1.0f - alpha, lane);
+        const float T_before = T * prev_lane(1.0f, pin);
+        const float T_after = T * pin;
+        const float tt = tcarry + wave_incl_sum(d1, lane);
+        const bool live = valid && !(T_before < T_thresh);
+        const float w = live ? alpha * T_before : 0.0f;
+        const float ra = rc + wave_incl_sum(w * cr, lane);
+        const float ga = gc + wave_incl_sum(w * cg, lane);
+        const float ba = bc + wave_incl_sum(w * cb, lane);
+        const float da = dcarry + wave_incl_sum(w * tt, lane);  // D_<=i
+        const float d_before = prev_lane(dcarry, da);           // D_<i
+        const float d_rest = df - da;                            // D - D_<=i
+        const float w_rest = wsf - (1.0f - T_after);             // W - W_<=i
+        const float gwi = 2.0f * (tt * (1.0f - T_before) - d_before) + 2.0f * (d_rest - tt * w_rest) + (2.0f / 3.0f) * (w * d0);
+        const float gga = gcarry + wave_incl_sum(gwi * w, lane);  // G_<=i
+        if (live) {
+            const uint32_t o = offset + s;
+            grad_rgbs[(size_t)o * 3] = gi0 * w;
+            grad_rgbs[(size_t)o * 3 + 1] = gi1 * w;
+            grad_rgbs[(size_t)o * 3 + 2] = gi2 * w;
+            const float plain = gi0 * (T_after * cr - (rf - ra)) + gi1 * (T_after * cg - (gf - ga)) + gi2 * (T_after * cb - (bf - ba)) +
+                                gw * (1.0f - wsf);
+            grad_sigmas[o] = d0 * (plain + gd * (T_after * tt - d_rest) + gl * (gwi * T_after - (gtot - gga)));
+        }
+        T = T * lane63(pin);
+        tcarry = lane63(tt);
+        rc = lane63(ra); gc = lane63(ga); bc = lane63(ba); dcarry = lane63(da); gcarry = lane63(gga);
+        if (T < T_thresh) break;
+    }
+}
+
 // The image-space middle of a training iteration in ONE launch, one wavefront per ray:
 //   k_composite_train_fwd (+ finish)  ->  the Trainer's MSE loss and its scaled gradient (k_mse_loss)  ->  k_composite_train_bwd  ->
 //   the colour head's sigmoid backward (k_rgb_backward),
@@ -1567,6 +1718,31 @@ extern "C" int ngp_composite_rays_train_backward_ex(const float* grad_weights_su
                        grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, fin, rows_used,
                        ray_blocks);
     return check_launch("composite_rays_train_backward");
+}
+
+extern "C" int ngp_composite_rays_train_geo_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                                    uint32_t N, float T_thresh, float* weights_sum, float* depth, float* image,
+                                                    float* distortion, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && distortion, NGP_ERR_INVALID,
+                "composite_rays_train_geo_forward: NULL tensor");
+    hipLaunchKernelGGL(k_composite_train_geo_fwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs, deltas,
+                       rays, M, N, T_thresh, weights_sum, depth, image, distortion);
+    return check_launch("composite_rays_train_geo_forward");
+}
+
+extern "C" int ngp_composite_rays_train_geo_backward(const float* grad_weights_sum, const float* grad_depth, const float* grad_image,
+                                                     const float* grad_distortion, const float* sigmas, const float* rgbs,
+                                                     const float* deltas, const int32_t* rays, const float* weights_sum, const float* depth,
+                                                     const float* image, const float* distortion, uint32_t M, uint32_t N, float T_thresh,
+                                                     float* grad_sigmas, float* grad_rgbs, ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && distortion && grad_sigmas && grad_rgbs, NGP_ERR_INVALID,
+                "composite_rays_train_geo_backward: NULL tensor");
+    hipLaunchKernelGGL(k_composite_train_geo_bwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), grad_weights_sum,
+                       grad_depth, grad_image, grad_distortion, sigmas, rgbs, deltas, rays, weights_sum, depth, image, distortion, M, N,
+                       T_thresh, grad_sigmas, grad_rgbs);
+    return check_launch("composite_rays_train_geo_backward");
 }
 
 extern "C" int ngp_composite_train_loss_backward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,

@@ -316,7 +316,7 @@ class GraphedTrainStep:
         m, kw = self.model, self.render_kwargs
         if not (self.direct and m.training and getattr(m, 'bg_radius', 0) <= 0 and hasattr(m, '_fused_render_ok')):
             return False
-        if kw.get('staged', False):
+        if kw.get('staged', False) or kw.get('geo', False):  # geo: the fused iteration has no depth_raw / distortion outputs
             return False
         bg = kw.get('bg_color', None)
         with torch.autocast('cuda', dtype=self.autocast_dtype):  # the fused path IS the fp16-autocast arithmetic; it checks for it

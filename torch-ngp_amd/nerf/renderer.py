@@ -160,10 +160,10 @@ class NeRFRenderer(nn.Module):
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)
         return image.view(*lead, 3), depth.view(*lead)
 
-    def _fused_render_ok(self, rays_o, rays_d, bg_color, force_all_rays):
+    def _fused_render_ok(self, rays_o, rays_d, bg_color, force_all_rays, geo=False):
         """the fused training render needs the estimate-sized sample buffer (no host read-back), a plain colour background and a
-        network the fused sample pipeline accepts (network_ff.NeRFNetwork._fused_ok)"""
-        if not getattr(self, 'fused', False) or force_all_rays or self.mean_count <= 0 or self.bg_radius > 0:
+        network the fused sample pipeline accepts (network_ff.NeRFNetwork._fused_ok); it has no geometry outputs (geo)"""
+        if geo or not getattr(self, 'fused', False) or force_all_rays or self.mean_count <= 0 or self.bg_radius > 0:
             return False
         if not (rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32):
             return False
@@ -178,8 +178,10 @@ class NeRFRenderer(nn.Module):
         return bool(probe(dummy, dummy)) and torch.is_grad_enabled()
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
-                 T_thresh=1e-4, **kwargs):
+                 T_thresh=1e-4, geo=False, **kwargs):
         # rays_o, rays_d [B, N, 3] (B == 1) -> {'image' [B,N,3], 'depth' [B,N], ('weights_sum' when training)}
+        # geo (extension, training only): composite with raymarching.composite_rays_train_geo -- 'depth' becomes differentiable
+        # and the results gain 'depth_raw' [N] (the compositor's un-normalised depth) and 'distortion' [N] (EffDistLoss per ray / (far - near))
         lead = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -188,7 +190,7 @@ class NeRFRenderer(nn.Module):
         box = self.aabb_train if self.training else self.aabb_infer
         results = {}
 
-        if self.training and self.bg_radius <= 0 and self._fused_render_ok(rays_o, rays_d, 1 if bg_color is None else bg_color, force_all_rays):
+        if self.training and self.bg_radius <= 0 and self._fused_render_ok(rays_o, rays_d, 1 if bg_color is None else bg_color, force_all_rays, geo):
             bg_color = 1 if bg_color is None else bg_color
             # extension (fused.py): the whole training branch below as one autograd Function, identical arithmetic
             from fused import fused_render_train
@@ -213,18 +215,30 @@ class NeRFRenderer(nn.Module):
                 self.mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps)
             sigmas, rgbs = self(xyzs, dirs)
             sigmas = self.density_scale * sigmas
+            if geo:
+                composite = raymarching.composite_rays_train_geo
+            else:
+                composite = lambda *a: raymarching.composite_rays_train(*a) + (None,)
             if sigmas.dim() == 2:  # stacked residual models (CCNeRF): composite each
-                images, depths = [], []
+                images, depths, raws, dists = [], [], [], []
                 for k in range(sigmas.shape[0]):
-                    weights_sum, depth, image = raymarching.composite_rays_train(sigmas[k], rgbs[k], deltas, rays, T_thresh)
-                    image, depth = self._finish(image, depth, weights_sum, bg_color, nears, fars, lead)
+                    weights_sum, depth_raw, image, distortion = composite(sigmas[k], rgbs[k], deltas, rays, T_thresh)
+                    image, depth = self._finish(image, depth_raw, weights_sum, bg_color, nears, fars, lead)
                     images.append(image)
                     depths.append(depth)
+                    raws.append(depth_raw)
+                    dists.append(distortion)
                 image, depth = torch.stack(images, 0), torch.stack(depths, 0)
+                if geo:
+                    depth_raw, distortion = torch.stack(raws, 0), torch.stack(dists, 0)
             else:
-                weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
-                image, depth = self._finish(image, depth, weights_sum, bg_color, nears, fars, lead)
+                weights_sum, depth_raw, image, distortion = composite(sigmas, rgbs, deltas, rays, T_thresh)
+                image, depth = self._finish(image, depth_raw, weights_sum, bg_color, nears, fars, lead)
             results['weights_sum'] = weights_sum
+            if geo:
+                results['depth_raw'] = depth_raw
+                # (a ray that misses the box has near = far and no samples: its distortion stays 0 instead of 0 / 0)
+                results['distortion'] = distortion / (fars - nears).clamp_min(torch.finfo(torch.float32).tiny)
         else:
             weights_sum = torch.zeros(n_rays, dtype=torch.float32, device=dev)
             depth = torch.zeros(n_rays, dtype=torch.float32, device=dev)

@@ -121,6 +121,32 @@ def composite_rays_train_backward(grad_weights_sum, grad_image, sigmas, rgbs, de
         capi.ptr(weights_sum), capi.ptr(image), M, N, float(T_thresh), capi.ptr(grad_sigmas), capi.ptr(grad_rgbs), capi.stream()))
 
 
+def composite_rays_train_geo_forward(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image, distortion):
+    """extension (include/ngp_hip.h, ngp_composite_rays_train_geo_forward): composite_rays_train_forward + the per-ray distortion.  Not in
+    the compiled `_raymarching` module (its table is the reference's): raymarching.py calls this helper whichever backend it imported."""
+    floats = ((sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (depth, 'depth'), (image, 'image'),
+              (distortion, 'distortion'))
+    fn = capi.lib.ngp_composite_rays_train_geo_forward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_composite_rays_train_geo_forward)
+    _i32(rays, 'rays')
+    capi.check(fn(capi.ptr(sigmas), capi.ptr(rgbs), capi.ptr(deltas), capi.ptr(rays), M, N, float(T_thresh), capi.ptr(weights_sum), capi.ptr(depth),
+                  capi.ptr(image), capi.ptr(distortion), capi.stream()))
+
+
+def composite_rays_train_geo_backward(grad_weights_sum, grad_depth, grad_image, grad_distortion, sigmas, rgbs, deltas, rays, weights_sum, depth,
+                                      image, distortion, M, N, T_thresh, grad_sigmas, grad_rgbs):
+    """extension (ngp_composite_rays_train_geo_backward): the gradients of all four outputs in one sweep; a None gradient is a zero one"""
+    floats = tuple((t, n) for t, n in (
+        (grad_weights_sum, 'grad_weights_sum'), (grad_depth, 'grad_depth'), (grad_image, 'grad_image'), (grad_distortion, 'grad_distortion'),
+        (sigmas, 'sigmas'), (rgbs, 'rgbs'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (depth, 'depth'), (image, 'image'),
+        (distortion, 'distortion'), (grad_sigmas, 'grad_sigmas'), (grad_rgbs, 'grad_rgbs')) if t is not None)
+    fn = capi.lib.ngp_composite_rays_train_geo_backward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_composite_rays_train_geo_backward)
+    _i32(rays, 'rays')
+    capi.check(fn(
+        capi.ptr(grad_weights_sum), capi.ptr(grad_depth), capi.ptr(grad_image), capi.ptr(grad_distortion), capi.ptr(sigmas), capi.ptr(rgbs),
+        capi.ptr(deltas), capi.ptr(rays), capi.ptr(weights_sum), capi.ptr(depth), capi.ptr(image), capi.ptr(distortion), M, N, float(T_thresh),
+        capi.ptr(grad_sigmas), capi.ptr(grad_rgbs), capi.stream()))
+
+
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, xyzs, dirs,
                deltas, noises):
     for t, n in ((rays_t, 'rays_t'), (rays_o, 'rays_o'), (rays_d, 'rays_d'), (nears, 'nears'), (fars, 'fars'), (xyzs, 'xyzs'),

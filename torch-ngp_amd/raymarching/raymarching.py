@@ -19,9 +19,10 @@ try:  # the compiled binding first, as the reference does (raymarching/raymarchi
     import _raymarching as _backend
 except ImportError:
     from .backend import _backend
+from . import backend as _geo  # the geometry compositor's entries are ctypes-only: the compiled module's table is the reference's
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'packbits_capped', 'march_rays_train',
-           'composite_rays_train', 'march_rays', 'composite_rays', 'compact_rays', 'update_density_grid', 'density_grid_state']
+           'composite_rays_train', 'composite_rays_train_geo', 'march_rays', 'composite_rays', 'compact_rays', 'update_density_grid', 'density_grid_state']
 
 _f32_fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 
@@ -224,6 +225,47 @@ class _composite_rays_train(Function):
 
 
 composite_rays_train = _composite_rays_train.apply
+
+
+class _composite_rays_train_geo(Function):
+    """Extension (not in the reference): composite_rays_train for geometry losses.  The same weights_sum, depth and image
+    (the same bits) plus the per-ray distortion of loss.py::EffDistLoss on the compositor's own weights, and a backward that propagates
+    the gradients of all four outputs -- depth included -- to sigmas and rgbs.  First order only."""
+
+    @staticmethod
+    @_f32_fwd
+    def forward(ctx, sigmas, rgbs, deltas, rays, T_thresh=1e-4):
+        """sigmas [M], rgbs [M,3], deltas [M,2], rays [N,3] -> weights_sum [N], depth [N], image [N,3], distortion [N]"""
+        sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous()
+        n_samples, n_rays = sigmas.shape[0], rays.shape[0]
+        weights_sum = torch.empty(n_rays, dtype=sigmas.dtype, device=sigmas.device)
+        depth = torch.empty_like(weights_sum)
+        distortion = torch.empty_like(weights_sum)
+        image = torch.empty(n_rays, 3, dtype=sigmas.dtype, device=sigmas.device)
+        _geo.composite_rays_train_geo_forward(sigmas, rgbs, deltas, rays, n_samples, n_rays, T_thresh, weights_sum, depth, image, distortion)
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image, distortion)
+        ctx.sizes = (n_samples, n_rays, T_thresh)
+        ctx.set_materialize_grads(False)  # an output the loss does not use arrives as None and goes to the kernel as a NULL pointer
+        return weights_sum, depth, image, distortion
+
+    @staticmethod
+    @custom_bwd(device_type='cuda')
+    def backward(ctx, grad_weights_sum, grad_depth, grad_image, grad_distortion):
+        if torch.is_grad_enabled() and any(g is not None and g.requires_grad for g in (grad_weights_sum, grad_depth, grad_image, grad_distortion)):
+            raise RuntimeError("composite_rays_train_geo: second-order gradients are not provided (the compositor's backward is not "
+                               "differentiable; raymarching stays first-order)")
+        sigmas, rgbs, deltas, rays, weights_sum, depth, image, distortion = ctx.saved_tensors
+        n_samples, n_rays, T_thresh = ctx.sizes
+        grad_sigmas = torch.zeros_like(sigmas)
+        grad_rgbs = torch.zeros_like(rgbs)
+        dense = lambda g: None if g is None else g.contiguous()
+        _geo.composite_rays_train_geo_backward(dense(grad_weights_sum), dense(grad_depth), dense(grad_image), dense(grad_distortion), sigmas, rgbs,
+                                               deltas, rays, weights_sum, depth, image, distortion, n_samples, n_rays, T_thresh, grad_sigmas,
+                                               grad_rgbs)
+        return grad_sigmas, grad_rgbs, None, None, None
+
+
+composite_rays_train_geo = _composite_rays_train_geo.apply
 
 
 # ----------------------------------------------------------------------------------------------
