@@ -664,6 +664,24 @@ int ngp_composite_train_loss_backward(const float* sigmas, const float* rgbs, co
                                       const float* fars, const float* target, const float* loss_scale, float* weights_sum,
                                       float* image_out, float* depth_out, float* loss, float* ray_err, float* grad_sigmas,
                                       void* grad_out16, void* march_workspace, size_t march_workspace_bytes, ngp_stream_t stream);
+/* ngp_composite_train_loss_backward with the geometry terms of ngp_composite_rays_train_geo_forward / _backward in the loss (optional
+ * extension, one launch, the same contract for grad_sigmas / grad_out16 / ray_err / loss / the tickets / march_workspace_bytes), N rays:
+ *   L = mean((image_out - target)^2) + lambda_distortion * mean_n(dist_n / span_n) + lambda_depth * mean_n(m_n * (d_n - z_n)^2),
+ *   span_n = max(fars_n - nears_n, FLT_MIN);  dist_n, d_n: the raw distortion and depth of ngp_composite_rays_train_geo_forward
+ *   in : ... as above, then after target: lambda_distortion, lambda_depth (finite, >= 0), target_depth z [N] (may be NULL only when
+ *        lambda_depth == 0), depth_weight m [N] (NULL = 1), both read at row rays[n,0] like target
+ *   out: ... as above, then after depth_out: depth_raw [N] (= d) and distortion [N] (= dist / span, the value the renderer returns)
+ * The gradients are those of the chain geo_forward -> ngp_pipeline_mse_loss + the per-ray gradients of the two terms -> geo_backward ->
+ * ngp_pipeline_rgb_backward, bit for bit; with both lambdas 0 every output of ngp_composite_train_loss_backward has the same bits.  ray_err
+ * [N] holds the per-ray squared error + 3 x the ray's two terms, so that sum / (3 N) -- here or in the carrying launch -- is L.  A ray
+ * without rows contributes its terms to L (depth 0, distortion 0) and no gradient.  N == 0: no-op. */
+int ngp_composite_train_geo_loss_backward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                          uint32_t N, float T_thresh, int bg_mode, float bg_scalar, const float* bg, const float* nears,
+                                          const float* fars, const float* target, float lambda_distortion, float lambda_depth,
+                                          const float* target_depth, const float* depth_weight, const float* loss_scale,
+                                          float* weights_sum, float* image_out, float* depth_out, float* depth_raw, float* distortion,
+                                          float* loss, float* ray_err, float* grad_sigmas, void* grad_out16, void* march_workspace,
+                                          size_t march_workspace_bytes, ngp_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * freqencoder       (reference: freqencoder/src/freqencoder.h:6-10, bindings.cpp:5-8) -- SURVEY.md 8(f).3; fp32, *_f64 twins.

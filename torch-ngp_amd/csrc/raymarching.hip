@@ -1336,6 +1336,207 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_loss_bwd(
     if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// k_composite_train_loss_bwd with the geometry terms in the loss, N rays:
+//   L = mean((image_out - target)^2) + lambda_distortion mean_n(dist_n / span_n) + lambda_depth mean_n(m_n (d_n - z_n)^2),
+//   span_n = max(fars_n - nears_n, FLT_MIN)   (dist_n, d_n: the raw distortion and depth of k_composite_train_geo_fwd; m: depth_weight, z: target_depth)
+// The same launch contract (tail workgroups, every row of grad_sigmas / grad_out16 written, tickets, loss == NULL).  Compositing, finish, MSE
+// and sigmoid backward are k_composite_train_loss_bwd's expressions, the distortion scans (X, A) k_composite_train_geo_fwd's, the backward
+// scans (t, D, G) k_composite_train_geo_bwd's, term for term; the ray totals the backward needs (depth, 2 dist) stay in registers.  With
+// both lambdas 0 the two new terms of grad_sigmas are zeros: the plain kernel's bits.  A ray without rows (empty, or not fitting M) adds
+// its terms to the loss VALUE (depth 0, distortion 0) and has no gradient, as in autograd.  ray_err carries 3 x the new terms: the
+// unchanged loss_sum_block (sum / 3N) then returns L.
+__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_loss_bwd(
+    const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas, const int32_t* __restrict__ rays,
+    uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum, Finish fin, const float* __restrict__ target,
+    float lambda_distortion, float lambda_depth, const float* __restrict__ target_depth, const float* __restrict__ depth_weight,
+    const float* __restrict__ loss_scale, float* __restrict__ depth_raw, float* __restrict__ distortion, float* __restrict__ ray_err,
+    uint32_t* __restrict__ ticket, float* __restrict__ loss, float* __restrict__ grad_sigmas, half_t* __restrict__ grad_out16,
+    const uint32_t* __restrict__ rows_used, uint32_t ray_blocks, uint32_t* __restrict__ group_tickets) {
+    const int lane = threadIdx.x & 63;
+    auto zero_row = [&](uint32_t o) {
+        half8_t z;
+#pragma unroll
+        for (int i = 0; i < 8; i++) z[i] = (half_t)0.0f;
+        half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
+        dst[0] = z; dst[1] = z;
+        grad_sigmas[o] = 0.0f;
+    };
+    if (blockIdx.x >= ray_blocks) {  // rows >= *rows_used that no ray owns
+        const uint32_t first = min(rows_used[0], M);
+        const uint32_t stride = (gridDim.x - ray_blocks) * CT_WAVES * 64;
+        for (uint32_t o = first + (blockIdx.x - ray_blocks) * CT_WAVES * 64 + threadIdx.x; o < M; o += stride) zero_row(o);
+        return;
+    }
+    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
+    if (n < N) {
+        const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+        const bool has_rows = num != 0 && offset + num <= M;
+        // ---- forward sweep (k_composite_train_geo_fwd) ----
+        float r = 0, g = 0, b = 0, ws = 0, d = 0, dist = 0;
+        if (has_rows) {
+            float T = 1.0f, tcarry = 0.0f, xcarry = 0.0f, acarry = 0.0f;
+            for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+                const uint32_t s = s0 + lane;
+                const bool valid = s < num;
+                float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+                if (valid) {
+                    sg = sigmas[offset + s];
+                    const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
+                    d0 = dl.x; d1 = dl.y;
+                    cr = rgbs[(size_t)(offset + s) * 3];
+                    cg = rgbs[(size_t)(offset + s) * 3 + 1];
+                    cb = rgbs[(size_t)(offset + s) * 3 + 2];
+                }
+                const float e = __expf(-sg * d0);
+                const float alpha = valid ? 1.0f - e : 0.0f;
+                const float om = 1.0f - alpha;
+                const float pin = wave_incl_prod(om, lane);
+                const float T_before = T * prev_lane(1.0f, pin);
+                const float tt = tcarry + wave_incl_sum(d1, lane);
+                const bool live = valid && !(T_before < T_thresh);
+                const float w = live ? alpha * T_before : 0.0f;
+                r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
+                // the distortion's own weights (invalid lanes: sg = d0 = d1 = 0)
+                const float x = sg * d0;
+                const float xa = xcarry + wave_incl_sum(x, lane);         // X_<=i
+                const float Tq = __expf(-prev_lane(xcarry, xa));          // T'_i = exp(-X_<i)
+                const float wq = live ? one_minus_exp_neg(x, e) * Tq : 0.0f;
+                const float a = acarry + wave_incl_sum((1.0f - Tq) * d1, lane);  // A_i (lanes behind the stop: w' = 0)
+                dist += 2.0f * wq * a + (1.0f / 3.0f) * (wq * wq * d0);
+                T = T * lane63(pin);
+                tcarry = lane63(tt);
+                xcarry = lane63(xa);
+                acarry = lane63(a);
+                if (T < T_thresh) break;  // wave-uniform
+            }
+            r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d); dist = wave_total(dist);
+        }
+        // ---- finish + loss (k_composite_train_loss_bwd) and the two geometry terms, every lane the same values ----
+        const float b0 = fin.mode == 2 ? fin.bg[index * 3] : fin.bg_scalar, b1 = fin.mode == 2 ? fin.bg[index * 3 + 1] : fin.bg_scalar,
+                    b2 = fin.mode == 2 ? fin.bg[index * 3 + 2] : fin.bg_scalar;
+        const float t1 = 1.0f - ws;
+        const float i0 = r + t1 * b0, i1 = g + t1 * b1, i2 = b + t1 * b2;
+        const float scale = loss_scale ? loss_scale[0] : 1.0f;
+        const float norm = 2.0f / (float)(3u * N);
+        const float e0 = i0 - target[index * 3], e1 = i1 - target[index * 3 + 1], e2 = i2 - target[index * 3 + 2];
+        const float gi0 = (norm * e0) * scale, gi1 = (norm * e1) * scale, gi2 = (norm * e2) * scale;
+        const float nr = fin.nears[index], fr = fin.fars[index];
+        const float span = fmaxf(fr - nr, FLT_MIN);   // the renderer's clamp_min(tiny): a ray that misses the box has near = far
+        const float dn = dist / span;
+        const float gl = ((lambda_distortion / (float)N) / span) * scale;          // dL/d dist_n, scaled
+        const float m = depth_weight ? depth_weight[index] : 1.0f;
+        const float dz = d - (target_depth ? target_depth[index] : 0.0f);          // (NULL only with lambda_depth == 0)
+        const float gd = (((2.0f * lambda_depth) / (float)N) * m * dz) * scale;    // dL/d d_n, scaled
+        if (lane == 0) {
+            weights_sum[index] = ws;
+            fin.image_out[index * 3] = i0; fin.image_out[index * 3 + 1] = i1; fin.image_out[index * 3 + 2] = i2;
+            fin.depth_out[index] = fmaxf(d - nr, 0.0f) / (fr - nr);
+            depth_raw[index] = d;
+            distortion[index] = dn;
+            // write-through store (agent scope), as in k_composite_train_loss_bwd
+            __hip_atomic_store(&ray_err[n], __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, e0 * e0)) +
+                                                3.0f * (lambda_distortion * dn + lambda_depth * (m * (dz * dz))),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        // ---- backward sweep (k_composite_train_geo_bwd with grad_weights_sum = gw, then k_rgb_backward) ----
+        if (has_rows) {
+            const float gw = 0.0f - (gi0 * b0 + gi1 * b1 + gi2 * b2);
+            const float rf = r, gf = g, bf = b, wsf = ws, df = d, gtot = 2.0f * dist;
+            float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f, tcarry = 0.0f, dcarry = 0.0f, gcarry = 0.0f;
+            for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+                const uint32_t s = s0 + lane;
+                const bool valid = s < num;
+                float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+                if (valid) {
+                    sg = sigmas[offset + s];
+                    const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
+                    d0 = dl.x; d1 = dl.y;
+                    cr = rgbs[(size_t)(offset + s) * 3];
+                    cg = rgbs[(size_t)(offset + s) * 3 + 1];
+                    cb = rgbs[(size_t)(offset + s) * 3 + 2];
+                }
+                const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
+                const float pin = wave_incl_prod(1.0f - alpha, lane);
+                const float T_before = T * prev_lane(1.0f, pin);
+                const float T_after = T * pin;
+                const float tt = tcarry + wave_incl_sum(d1, lane);
+                const bool live = valid && !(T_before < T_thresh);
+                const float w = live ? alpha * T_before : 0.0f;
+                const float ra = rc + wave_incl_sum(w * cr, lane);
+                const float ga = gc + wave_incl_sum(w * cg, lane);
+                const float ba = bc + wave_incl_sum(w * cb, lane);
+                const float da = dcarry + wave_incl_sum(w * tt, lane);  // D_<=i
+                const float d_before = prev_lane(dcarry, da);           // D_<i
+                const float d_rest = df - da;                            // D - D_<=i
+                const float w_rest = wsf - (1.0f - T_after);             // W - W_<=i
+                const float gwi = 2.0f * (tt * (1.0f - T_before) - d_before) + 2.0f * (d_rest - tt * w_rest) + (2.0f / 3.0f) * (w * d0);
+                const float gga = gcarry + wave_incl_sum(gwi * w, lane);  // G_<=i
+                if (live) {
+                    const uint32_t o = offset + s;
+                    half8_t lo, hi;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) { lo[i] = (half_t)0.0f; hi[i] = (half_t)0.0f; }
+                    lo[0] = to_half_rne((gi0 * w) * (cr * (1.0f - cr)));
+                    lo[1] = to_half_rne((gi1 * w) * (cg * (1.0f - cg)));
+                    lo[2] = to_half_rne((gi2 * w) * (cb * (1.0f - cb)));
+                    half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
+                    dst[0] = lo; dst[1] = hi;
+                    const float plain = gi0 * (T_after * cr - (rf - ra)) + gi1 * (T_after * cg - (gf - ga)) + gi2 * (T_after * cb - (bf - ba)) +
+                                        gw * (1.0f - wsf);
+                    grad_sigmas[o] = d0 * (plain + gd * (T_after * tt - d_rest) + gl * (gwi * T_after - (gtot - gga)));
+                } else if (valid) {
+                    zero_row(offset + s);
+                }
+                T = T * lane63(pin);
+                tcarry = lane63(tt);
+                rc = lane63(ra); gc = lane63(ga); bc = lane63(ba); dcarry = lane63(da); gcarry = lane63(gga);
+                if (T < T_thresh) {
+                    for (uint32_t z = s0 + 64 + lane; z < num; z += 64) zero_row(offset + z);
+                    break;
+                }
+            }
+        }
+    }
+    // ---- the loss value: k_composite_train_loss_bwd's tail, statement for statement (see the notes there; a separate body so that the
+    // plain kernel keeps its code) ----
+    if (loss == nullptr) return;
+    __shared__ float part[CT_WAVES];
+    __shared__ bool last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every lane: its own stores (the write-through ray_err store among them) have completed
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t groups = ray_blocks < CT_GROUPS ? ray_blocks : CT_GROUPS;
+        const uint32_t group = blockIdx.x % groups, members = (ray_blocks - group + groups - 1u) / groups;
+        uint32_t* gt = group_tickets + group * CT_GROUP_STRIDE;
+        bool l = false;
+        if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1u) {
+            __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            l = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1u;
+        }
+        last = l;
+    }
+    __syncthreads();
+    if (!last) return;
+    // common.h loss_sum_block, statement for statement (the same order of additions: the same bits).  Not a call: with a second call site in
+    // this file the compiler stops specialising that routine for its single caller and k_composite_train_loss_bwd gets another register
+    // allocation (read off the disassembly, EXPERIMENTS.md)
+    static_assert(CT_WAVES == 4, "four wave sums");
+    const uint32_t t = threadIdx.x;
+    float acc = 0.0f;
+    for (uint32_t i = t; i < N; i += 256u) acc += __hip_atomic_load(&ray_err[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    acc = wave_total(acc);
+    if ((t & 63u) == 0u) part[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0u) {
+        float v = 0.0f;
+#pragma unroll
+        for (int w = 0; w < 4; w++) v += part[w];
+        loss[0] = v / (float)(3u * N);
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // raymarching.cu:819-905 -- at most 8 samples per ray and call: one lane per alive ray
 __global__ __launch_bounds__(RM_THREADS) void k_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* __restrict__ rays_alive,
                                                                float* __restrict__ rays_t, const float* __restrict__ sigmas,
@@ -1768,6 +1969,39 @@ extern "C" int ngp_composite_train_loss_backward(const float* sigmas, const floa
                        deltas, rays, M, N, T_thresh, weights_sum, fin, target, loss_scale, ray_err, ws + 1, loss, grad_sigmas,
                        (half_t*)grad_out16, (const uint32_t*)ws, ray_blocks, ws + march_ws_ticket_word(N));
     return check_launch("composite_train_loss_backward");
+}
+
+extern "C" int ngp_composite_train_geo_loss_backward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
+                                                     uint32_t N, float T_thresh, int bg_mode, float bg_scalar, const float* bg,
+                                                     const float* nears, const float* fars, const float* target, float lambda_distortion,
+                                                     float lambda_depth, const float* target_depth, const float* depth_weight,
+                                                     const float* loss_scale, float* weights_sum, float* image_out, float* depth_out,
+                                                     float* depth_raw, float* distortion, float* loss, float* ray_err, float* grad_sigmas,
+                                                     void* grad_out16, void* march_workspace, size_t march_workspace_bytes,
+                                                     ngp_stream_t stream) {
+    if (N == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && rgbs && deltas && rays && target && weights_sum && depth_raw && distortion && ray_err && grad_sigmas && grad_out16 &&
+                    march_workspace,
+                NGP_ERR_INVALID, "composite_train_geo_loss_backward: NULL tensor");
+    NGP_REQUIRE(lambda_distortion >= 0.0f && lambda_distortion <= FLT_MAX && lambda_depth >= 0.0f && lambda_depth <= FLT_MAX, NGP_ERR_INVALID,
+                "composite_train_geo_loss_backward: lambda_distortion = %g, lambda_depth = %g must be finite and >= 0", (double)lambda_distortion,
+                (double)lambda_depth);
+    NGP_REQUIRE(target_depth || lambda_depth == 0.0f, NGP_ERR_INVALID, "composite_train_geo_loss_backward: lambda_depth > 0 needs target_depth");
+    NGP_REQUIRE(march_workspace_bytes >= ngp_march_rays_train_workspace_bytes(N), NGP_ERR_INVALID,
+                "composite_train_geo_loss_backward: march_workspace of %zu bytes, needs ngp_march_rays_train_workspace_bytes(%u) = %zu (the group tickets sit at its end)",
+                march_workspace_bytes, N, ngp_march_rays_train_workspace_bytes(N));
+    NGP_REQUIRE(bg_mode == 1 || bg_mode == 2, NGP_ERR_INVALID, "composite_train_geo_loss_backward: bg_mode must be 1 (scalar) or 2 (per ray)");
+    NGP_REQUIRE((uint64_t)N * 3u <= 0xffffffffull, NGP_ERR_INVALID, "composite_train_geo_loss_backward: too many rays");
+    Finish fin;
+    int rc = make_finish("composite_train_geo_loss_backward", bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, true, &fin);
+    if (rc) return rc;
+    uint32_t* ws = reinterpret_cast<uint32_t*>(march_workspace);
+    const uint32_t ray_blocks = cdiv(N, CT_WAVES), tail_blocks = 32u;
+    hipLaunchKernelGGL(k_composite_train_geo_loss_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs,
+                       deltas, rays, M, N, T_thresh, weights_sum, fin, target, lambda_distortion, lambda_depth, target_depth, depth_weight,
+                       loss_scale, depth_raw, distortion, ray_err, ws + 1, loss, grad_sigmas, (half_t*)grad_out16, (const uint32_t*)ws,
+                       ray_blocks, ws + march_ws_ticket_word(N));
+    return check_launch("composite_train_geo_loss_backward");
 }
 
 extern "C" int ngp_composite_rays_train_backward(const float* grad_weights_sum, const float* grad_image, const float* sigmas,

@@ -41,6 +41,31 @@ Saved = namedtuple('Saved', 'xyzs offsets enc ws16 wc16 fb_s fb_c h16 color_in r
 Bufs = namedtuple('Bufs', 'emb16 ws16 wc16 g_emb g_ws g_wc')
 
 
+class GeoLoss(namedtuple('GeoLoss', 'lambda_distortion lambda_depth target_depth depth_weight', defaults=(0.0, 0.0, None, None))):
+    """the geometry terms `fused_train_iteration(..., geo_loss=)` adds to the Trainer's MSE loss, N rays:
+         lambda_distortion * mean_n(distortion_n)                    distortion: what model.render(geo=True) returns (per ray / (far - near))
+       + lambda_depth * mean_n(depth_weight_n * (depth_raw_n - target_depth_n)^2)
+    lambdas: finite host floats >= 0 (they are launch arguments: baked into a captured graph); target_depth [N] fp32 on the device (needed
+    when lambda_depth > 0), depth_weight [N] fp32 or None (= 1)."""
+    __slots__ = ()
+
+    def __new__(cls, lambda_distortion=0.0, lambda_depth=0.0, target_depth=None, depth_weight=None):
+        lams = []
+        for name, v in (('lambda_distortion', lambda_distortion), ('lambda_depth', lambda_depth)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f'GeoLoss: {name} must be a host float, got {type(v).__name__}')
+            v = float(v)
+            if not (0.0 <= v < float('inf')):
+                raise ValueError(f'GeoLoss: {name} must be finite and >= 0, got {v}')
+            lams.append(v)
+        if lams[1] > 0 and target_depth is None:
+            raise ValueError('GeoLoss: lambda_depth > 0 needs target_depth')
+        for name, t in (('target_depth', target_depth), ('depth_weight', depth_weight)):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError(f'GeoLoss: {name} must be a contiguous [N] float32 tensor')
+        return super().__new__(cls, lams[0], lams[1], target_depth, depth_weight)
+
+
 def _grid_forward(x, emb16, offsets, enc, M, L, S, H, gridtype, align, interp, bound, costs, st):
     """the encoder launch of the fused paths.  A table that optim.NGPAdam keeps in two buffer sets (enable_table_fusion: the Adam sweep rides
     in the grid backward and writes the set that is NOT current) carries its second fp16 copy and the device-side parity word on the
@@ -427,7 +452,7 @@ def _render_cfg(model, capacity, bg_color, perturb, dt_gamma, max_steps, T_thres
 
 @torch.no_grad()
 def fused_train_iteration(model, rays_o, rays_d, target, box, counter, capacity, loss_scale, bg_color=1, perturb=False, dt_gamma=0,
-                          max_steps=1024, T_thresh=1e-4, noise_seed=None, found_inf=None, overwrite_table=False, table_adam=None):
+                          max_steps=1024, T_thresh=1e-4, noise_seed=None, found_inf=None, overwrite_table=False, table_adam=None, geo_loss=None):
     """One training iteration's forward + MSE loss + backward WITHOUT autograd: the launches of `_fused_render_train` forward, the
     Trainer's loss (nerf/utils.py:516,557) and its scaled gradient in one kernel, then the backward launches, depositing the gradients
     into the optimizer's fp16 buffers (optim.NGPAdam with deposit=True must manage the three parameter tensors).  28 launches instead
@@ -443,10 +468,13 @@ def fused_train_iteration(model, rays_o, rays_d, target, box, counter, capacity,
     applies Adam to the table in its flush (speculative double buffer, include/ngp_hip.h ngp_table_adam_t) and the optimizer's next
     `step(gradients_checked=True)` is one small launch (Adam on the MLP weights, commit, parity flip).  Needs overwrite_table, found_inf
     and a batch of >= 16 384 samples (else the C entry refuses before launching anything).
-    -> (loss [1] fp32, image [N,3], depth [N], weights_sum [N]); same arithmetic as model.render + mse_loss + scaled backward
-    (tests/test_gpu_graph.py)."""
+    geo_loss: a GeoLoss -- the distortion and depth terms join the loss inside the compositor's one launch (k_composite_train_geo_loss_bwd,
+    DESIGN.md 3.10; needs USE_FUSED_COMPOSITE) and the result gains depth_raw [N] and distortion [N], the values model.render(geo=True)
+    returns.  Every other mode above works unchanged.  None: the launches and the 4-tuple of the MSE-only iteration.
+    -> (loss [1] fp32, image [N,3], depth [N], weights_sum [N]) (+ depth_raw [N], distortion [N] with a geo_loss); same arithmetic as
+    model.render + mse_loss + scaled backward (tests/test_gpu_graph.py, tests/test_gpu_fused_geo_loss.py)."""
     march, rest = fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, capacity, loss_scale, bg_color, perturb, dt_gamma,
-                                              max_steps, T_thresh, noise_seed, found_inf, overwrite_table, table_adam)
+                                              max_steps, T_thresh, noise_seed, found_inf, overwrite_table, table_adam, geo_loss)
     march()
     return rest()
 
@@ -505,9 +533,12 @@ def iteration_checks_gradients(model):
     return bool(USE_FUSED_CHECK and USE_FUSED_MID and all(n in (2, 3) for n in nl) and capi.host_offsets(model.encoder.offsets) is not None)
 
 
-def _train_iteration_rest(marched, bufs, bg_t, offsets, target, loss_scale, cfg, rcfg, found_inf=None, overwrite=False, table_adam=None):
+def _train_iteration_rest(marched, bufs, bg_t, offsets, target, loss_scale, cfg, rcfg, found_inf=None, overwrite=False, table_adam=None,
+                          geo_loss=None):
     if table_adam is not None and not (USE_FUSED_COMPOSITE and found_inf is not None and overwrite):
         raise RuntimeError('fused: table_adam needs the fused compositor, the in-kernel non-finite sweep (found_inf) and overwrite_table')
+    if geo_loss is not None and not USE_FUSED_COMPOSITE:
+        raise RuntimeError('fused: geo_loss needs the fused compositor (USE_FUSED_COMPOSITE)')
     g_emb, g_ws, g_wc = bufs.g_emb, bufs.g_ws.view(-1), bufs.g_wc.view(-1)
     if not USE_FUSED_COMPOSITE:
         image, depth, weights_sum, saved = _render_train_network(marched, bufs, bg_t, offsets, cfg, rcfg)
@@ -527,6 +558,27 @@ def _train_iteration_rest(marched, bufs, bg_t, offsets, target, loss_scale, cfg,
     # the loss VALUE: summed by the compositor's last workgroup (a ticket round trip at the end of every workgroup), or left to the launch
     # that carries the slab reduction (same routine, same bits: the compositor then ends without tickets)
     defer = _carries_reductions(cfg.nl_sigma, cfg.nl_color)
+    if geo_loss is not None:
+        # the same launch with the distortion / depth terms in the loss: grad_sigmas / grad_out16 / ray_err keep their contract, so everything
+        # behind it (deferred loss sum, non-finite sweep, overwritten table, table Adam) is the MSE-only iteration's
+        for name in ('target_depth', 'depth_weight'):
+            t = getattr(geo_loss, name)
+            if t is not None and (t.shape[0] != N or t.device != dev):
+                raise RuntimeError(f'fused: geo_loss.{name} must be [{N}] float32 on {dev}')
+        depth_raw, distortion = torch.empty(N, **f32), torch.empty(N, **f32)
+        capi.check(capi.lib.ngp_composite_train_geo_loss_backward(s.sigma.data_ptr(), s.rgb.data_ptr(), s.deltas.data_ptr(), s.rays.data_ptr(), M, N,
+                                                                   float(rcfg.T_thresh), 2 if s.bg is not None else 1, float(rcfg.bg_scalar),
+                                                                   capi.ptr(s.bg), marched.nears.data_ptr(), marched.fars.data_ptr(),
+                                                                   target.data_ptr(), geo_loss.lambda_distortion, geo_loss.lambda_depth,
+                                                                   capi.ptr(geo_loss.target_depth), capi.ptr(geo_loss.depth_weight),
+                                                                   capi.ptr(loss_scale), weights_sum.data_ptr(), image.data_ptr(), depth.data_ptr(),
+                                                                   depth_raw.data_ptr(), distortion.data_ptr(),
+                                                                   None if defer else loss.data_ptr(), ray_err.data_ptr(), g_sigma.data_ptr(),
+                                                                   g_out16.data_ptr(), s.march_ws.data_ptr(),
+                                                                   s.march_ws.numel() * s.march_ws.element_size(), capi.stream()))
+        _network_backward(s, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf, loss_job=(ray_err, loss) if defer else None,
+                          overwrite=overwrite, table_adam=table_adam)
+        return loss, image, depth, weights_sum, depth_raw, distortion
     capi.check(capi.lib.ngp_composite_train_loss_backward(s.sigma.data_ptr(), s.rgb.data_ptr(), s.deltas.data_ptr(), s.rays.data_ptr(), M, N,
                                                            float(rcfg.T_thresh), 2 if s.bg is not None else 1, float(rcfg.bg_scalar), capi.ptr(s.bg),
                                                            marched.nears.data_ptr(), marched.fars.data_ptr(), target.data_ptr(),
@@ -541,7 +593,8 @@ def _train_iteration_rest(marched, bufs, bg_t, offsets, target, loss_scale, cfg,
 
 @torch.no_grad()
 def fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, capacity, loss_scale, bg_color=1, perturb=False, dt_gamma=0,
-                                max_steps=1024, T_thresh=1e-4, noise_seed=None, found_inf=None, overwrite_table=False, table_adam=None):
+                                max_steps=1024, T_thresh=1e-4, noise_seed=None, found_inf=None, overwrite_table=False, table_adam=None,
+                                geo_loss=None):
     """`fused_train_iteration` in two halves for data-parallel training: returns (march, rest) callables -- `march()` issues the
     parameter-independent launches (near/far, ray marching), `rest()` everything that reads the weights (encode, MLPs, composite, loss,
     backward).  graph.GraphedTrainStep captures them into separate HIP graphs so that the all-gather of the updated fp16 shadow weights
@@ -556,6 +609,8 @@ def fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, cap
     target = target.contiguous().view(-1, 3)
     if target.shape[0] != rays_o.shape[0] or target.dtype != torch.float32:
         raise RuntimeError('fused_train_iteration: target must be [N,3] float32')
+    if geo_loss is not None and not isinstance(geo_loss, GeoLoss):
+        raise TypeError('fused_train_iteration: geo_loss must be a fused.GeoLoss')
     box_ = {}
 
     def march():   # (called again -- a second captured graph -- it marches into the SAME buffers, the ones rest() reads)
@@ -563,7 +618,8 @@ def fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, cap
 
     def rest():
         ta = _table_adam_of(table_adam, model)
-        out = _train_iteration_rest(box_['m'], bufs, bg_t, model.encoder.offsets, target, loss_scale, cfg, rcfg, found_inf, overwrite_table, ta)
+        out = _train_iteration_rest(box_['m'], bufs, bg_t, model.encoder.offsets, target, loss_scale, cfg, rcfg, found_inf, overwrite_table, ta,
+                                    geo_loss)
         if overwrite_table:
             # read (and reset) by the optimizer's next step: it keeps the buffer -- and, where this iteration's backward swept the table with
             # Adam, applies Adam to the dense-level prefix only

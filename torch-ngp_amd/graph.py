@@ -67,7 +67,14 @@ def mse_loss(out, target):
 class GraphedTrainStep:
     def __init__(self, model, optimizer, scaler, n_rays, render_kwargs, loss_fn=mse_loss, averager=None, capacity_quantum=8192,
                  update_interval=16, after_update=None, autocast_dtype=torch.float16, direct=True, capacity_slack=2, lookahead=False,
-                 fused_table_adam=False, capacity_ladder=(0.8, 1.25, 1.5625, 1.953125, 2.44140625)):
+                 fused_table_adam=False, capacity_ladder=(0.8, 1.25, 1.5625, 1.953125, 2.44140625), geo_loss=None):
+        """geo_loss: a fused.GeoLoss(lambda_distortion=...) -- the autograd-free iteration adds the distortion term to the MSE loss inside its
+        compositor launch (fused.fused_train_iteration(geo_loss=)), in the single buffer set and the lookahead sets, captured
+        or not; the eager steps before the first capture render with geo=True and add the same term through autograd.  Needs the direct
+        iteration: a configuration or a model that is not eligible for it raises instead of training without the term (an arbitrary loss_fn
+        cannot be asked to add it).  The lambda is a host float baked into the captured launches: another value needs a new GraphedTrainStep.
+        lambda_depth > 0 is refused (ValueError): depth targets are per-batch tensors the static and lookahead buffer sets do not hold yet --
+        use the eager fused.fused_train_iteration for depth supervision."""
         self.model, self.optimizer, self.scaler = model, optimizer, scaler
         self.loss_fn, self.averager = loss_fn, averager
         if averager is not None and averager is not optimizer and getattr(optimizer, 'flat_grad16', None) is not None:
@@ -112,6 +119,17 @@ class GraphedTrainStep:
         # deposits gradients (optim.NGPAdam), and a model/render configuration the fused training render accepts
         self.direct = bool(direct) and loss_fn is mse_loss and scaler is None and getattr(optimizer, 'flat_grad16', None) is not None
         # lookahead: the next batch's march under this iteration (see the module docstring); single rank + autograd-free iteration only
+        self.geo_loss = geo_loss
+        if geo_loss is not None:
+            from fused import GeoLoss
+            if not isinstance(geo_loss, GeoLoss):
+                raise TypeError('GraphedTrainStep: geo_loss must be a fused.GeoLoss')
+            if geo_loss.lambda_depth > 0:
+                raise ValueError('GraphedTrainStep: lambda_depth > 0 is not supported under the graphs (depth targets are per-batch tensors); '
+                                 'use fused.fused_train_iteration(geo_loss=) eagerly')
+            if not self.direct or self.render_kwargs.get('geo', False) or self.render_kwargs.get('staged', False):
+                raise ValueError('GraphedTrainStep: geo_loss needs the autograd-free iteration (direct=True, the default loss_fn, scaler=None, '
+                                 "optim.NGPAdam) and render_kwargs without 'geo' / 'staged'")
         self.lookahead = bool(lookahead) and self.direct and (averager is None or (averager is optimizer and getattr(optimizer, 'shard', False)))
         self.la = None                      # [(march graph, rest graph, loss)] x 2 once captured
         self.la_cur = 0                     # buffer set of the CURRENT batch
@@ -215,6 +233,7 @@ class GraphedTrainStep:
         before = self.captures
         cap = self._capacity()
         if cap is not None and self.capture_error is None and not self._fits(cap):
+            self._geo_loss_needs_direct()
             self.captured_capacity = cap
             try:
                 self._capture()
@@ -316,7 +335,9 @@ class GraphedTrainStep:
         m, kw = self.model, self.render_kwargs
         if not (self.direct and m.training and getattr(m, 'bg_radius', 0) <= 0 and hasattr(m, '_fused_render_ok')):
             return False
-        if kw.get('staged', False) or kw.get('geo', False):  # geo: the fused iteration has no depth_raw / distortion outputs
+        # geo: the caller wants depth_raw / distortion in the render's results and its own loss on them; the direct iteration serves the
+        # geometry terms it knows through `geo_loss` (read with getattr in _iteration_args: _direct_ok does not depend on it)
+        if kw.get('staged', False) or kw.get('geo', False):
             return False
         bg = kw.get('bg_color', None)
         with torch.autocast('cuda', dtype=self.autocast_dtype):  # the fused path IS the fp16-autocast arithmetic; it checks for it
@@ -337,7 +358,7 @@ class GraphedTrainStep:
         args = (m, *batch, m.aabb_train, counter, self.captured_capacity, opt.scalars[0:1], 1 if bg is None else bg, kw.get('perturb', False),
                 kw.get('dt_gamma', 0), kw.get('max_steps', 1024), kw.get('T_thresh', 1e-4))
         return args, dict(noise_seed=seed, found_inf=opt.scalars[2:3] if checked else None, overwrite_table=self._overwrites_table(),
-                          table_adam=opt if checked and self.table_fused else None)
+                          table_adam=opt if checked and self.table_fused else None, geo_loss=getattr(self, 'geo_loss', None))
 
     def _iteration_front(self):
         """zero_grad -> render -> loss -> scaled backward, with the model's bookkeeping pinned for capture"""
@@ -349,9 +370,10 @@ class GraphedTrainStep:
             # After an all-reduce the sweep has to see the REDUCED values, so the replicated data-parallel path keeps it.
             self.producers_check = self._checked_ok and (self.averager is None)
             args, kwargs = self._iteration_args(self.producers_check)
-            loss, _, _, _ = fused_train_iteration(*args, **kwargs)
+            loss = fused_train_iteration(*args, **kwargs)[0]
             self.used_direct = True
             return loss[0]
+        self._geo_loss_needs_direct()
         self.used_direct = False
         self.producers_check = False
         saved_counter, saved_mc, saved_ls = m._buffers['step_counter'], m.mean_count, m.local_step
@@ -367,6 +389,12 @@ class GraphedTrainStep:
         finally:
             m._buffers['step_counter'], m.mean_count, m.local_step = saved_counter, saved_mc, saved_ls
         return loss
+
+    def _geo_loss_needs_direct(self):
+        """a geo_loss is served by the autograd-free iteration alone: raise where the graphs about to be captured would leave it out"""
+        if getattr(self, 'geo_loss', None) is not None and not self._direct_ok():
+            raise RuntimeError('GraphedTrainStep: geo_loss needs the autograd-free iteration and this model / render configuration is not '
+                               'eligible for it (GraphedTrainStep._direct_ok)')
 
     def _scaled(self, loss):
         # torch.optim + GradScaler, or an optimizer that owns its loss scale (optim.NGPAdam: scale / step, no scaler object)
@@ -584,9 +612,14 @@ class GraphedTrainStep:
 
     def _eager(self, rays_o, rays_d, target):
         self.optimizer.zero_grad(set_to_none=True)
+        geo = getattr(self, 'geo_loss', None)
         with torch.autocast('cuda', dtype=self.autocast_dtype):
-            out = self.model.render(rays_o, rays_d, **self.render_kwargs)
-            loss = self.loss_fn(out, target)
+            if geo is None:
+                out = self.model.render(rays_o, rays_d, **self.render_kwargs)
+                loss = self.loss_fn(out, target)
+            else:   # the same term through autograd (the steps before the sample estimate exists)
+                out = self.model.render(rays_o, rays_d, **dict(self.render_kwargs, geo=True))
+                loss = self.loss_fn(out, target) + geo.lambda_distortion * out['distortion'].float().mean()
         self._scaled(loss).backward()
         if self.averager is not None and not getattr(self.optimizer, 'shard', False):
             self.averager.all_reduce()
@@ -701,6 +734,7 @@ class GraphedTrainStep:
             if pick != self.captured_capacity:
                 self._activate(pick)     # another captured capacity serves this estimate: no capture, no device work
         elif not self._fits(cap):
+            self._geo_loss_needs_direct()
             self.captured_capacity = cap
             try:
                 self._capture()
