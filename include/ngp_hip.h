@@ -645,6 +645,32 @@ int ngp_composite_rays_train_geo_backward_f64(const double* grad_weights_sum, co
                                               const double* image, const double* distortion, uint32_t M, uint32_t N, float T_thresh,
                                               double* grad_sigmas, double* grad_rgbs, ngp_stream_t stream);
 
+/* EXTENSION (not in the reference): composite arbitrary per-sample feature channels with the weights of composite_rays_train
+ * (raymarching.cu:501-577: a ray with num == 0 or offset + num > M composites nothing, the sample that drives T below T_thresh is still
+ * composited, alpha_i = 1 - exp(-sigma_i deltas[i,0]), T_i = prod_{j<i} (1 - alpha_j), w_i = alpha_i T_i):
+ *   out[index, c] = sum_i w_i feats[offset + i, c],   c = 0 .. C-1,  1 <= C <= 256          (zeros for a ray that composites nothing)
+ * sigmas [M], deltas [M,2], out [N,C] fp32; feats [M,C] of feat_dtype (NGP_F32 or NGP_F16; fp16 is converted at the load and
+ * accumulated in fp32: the bits of the fp32 call on the up-cast values); rays [N,3] int32 (index, offset, num).
+ * Backward, from grad_out [N,C] and the forward's out, with T_{i+1} the transmittance behind sample i:
+ *   grad_feats[offset+i, c] = w_i grad_out[index, c]                                         (feat_dtype; fp16: the fp32 product rounded once)
+ *   q_i = sum_c grad_out[index,c] feats[offset+i,c],   Q = sum_c grad_out[index,c] out[index,c]
+ *   grad_sigmas[offset+i]   = deltas[offset+i,0] (T_{i+1} q_i - (Q - sum_{j<=i} w_j q_j))
+ * grad_sigmas [M] fp32 / grad_feats [M,C] are written for composited rows only, the caller pre-zeroes them (the contract of
+ * ngp_composite_rays_train_geo_backward).  deltas and rays get no gradient.  Deterministic: fixed-order reductions, no atomics.
+ * C outside 1 .. 256, an unknown feat_dtype or a NULL tensor: NGP_ERR_INVALID.  N == 0 or M == 0: nothing is launched. */
+int ngp_composite_rays_train_features_forward(const float* sigmas, const void* feats, const float* deltas, const int32_t* rays, uint32_t M,
+                                              uint32_t N, uint32_t C, float T_thresh, int feat_dtype, float* out, ngp_stream_t stream);
+int ngp_composite_rays_train_features_backward(const float* grad_out, const float* sigmas, const void* feats, const float* deltas,
+                                               const int32_t* rays, const float* out, uint32_t M, uint32_t N, uint32_t C, float T_thresh,
+                                               int feat_dtype, float* grad_sigmas, void* grad_feats, ngp_stream_t stream);
+/* fp64 twins of the two entries above (one lane per ray): the same arguments with every floating tensor double and no feat_dtype, for
+ * torch.autograd.gradcheck */
+int ngp_composite_rays_train_features_forward_f64(const double* sigmas, const double* feats, const double* deltas, const int32_t* rays,
+                                                  uint32_t M, uint32_t N, uint32_t C, float T_thresh, double* out, ngp_stream_t stream);
+int ngp_composite_rays_train_features_backward_f64(const double* grad_out, const double* sigmas, const double* feats, const double* deltas,
+                                                   const int32_t* rays, const double* out, uint32_t M, uint32_t N, uint32_t C,
+                                                   float T_thresh, double* grad_sigmas, double* grad_feats, ngp_stream_t stream);
+
 /* The image-space middle of one TRAINING iteration in one launch (optional extension; what the four calls
  * ngp_composite_rays_train_forward_ex -> ngp_pipeline_mse_loss -> ngp_composite_rays_train_backward_ex -> ngp_pipeline_rgb_backward
  * compute, expression for expression: raymarching.cu:501-577 forward, renderer.py:316-318 finish, nerf/utils.py:516,557 loss,

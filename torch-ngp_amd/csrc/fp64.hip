@@ -610,6 +610,61 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_bwd(con
     }
 }
 
+// compositing of per-sample feature channels (raymarching.hip: k_composite_feat_fwd / _bwd): out[index, c] = sum_i w_i feats[i, c]
+__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_feat_fwd(const double* __restrict__ sigmas, const double* __restrict__ feats,
+                                                                         const double* __restrict__ deltas, const int32_t* __restrict__ rays, uint32_t M,
+                                                                         uint32_t N, uint32_t C, float T_thresh, double* __restrict__ out) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    const double th = (double)T_thresh;
+    double* __restrict__ acc = out + (size_t)index * C;  // the ray's own output row is its accumulator
+    for (uint32_t c = 0; c < C; c++) acc[c] = 0.0;
+    if (num == 0u || offset + num > M) return;
+    double T = 1.0;
+    for (uint32_t s = 0; s < num; s++) {
+        const size_t o = (size_t)offset + s;
+        const double alpha = 1.0 - exp(-sigmas[o] * deltas[o * 2]);
+        const double w = alpha * T;
+        for (uint32_t c = 0; c < C; c++) acc[c] += w * feats[o * C + c];
+        T *= 1.0 - alpha;
+        if (T < th) break;  // the sample that drives T below the threshold is composited (raymarching.cu:557-560)
+    }
+}
+
+// q_i = sum_c grad_out[c] feats[i, c], Q = sum_c grad_out[c] out[c]:  grad_feats[i, c] = w_i grad_out[c],
+// grad_sigmas[i] = d0_i (T_{i+1} q_i - (Q - sum_{j<=i} w_j q_j))
+__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_feat_bwd(const double* __restrict__ grad_out, const double* __restrict__ sigmas,
+                                                                         const double* __restrict__ feats, const double* __restrict__ deltas,
+                                                                         const int32_t* __restrict__ rays, const double* __restrict__ out, uint32_t M,
+                                                                         uint32_t N, uint32_t C, float T_thresh, double* __restrict__ grad_sigmas,
+                                                                         double* __restrict__ grad_feats) {
+    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    if (num == 0u || offset + num > M) return;
+    const double th = (double)T_thresh;
+    const double* __restrict__ g = grad_out + (size_t)index * C;
+    double Q = 0.0;
+    for (uint32_t c = 0; c < C; c++) Q += g[c] * out[(size_t)index * C + c];
+    double T = 1.0, done = 0.0;
+    for (uint32_t s = 0; s < num; s++) {
+        const size_t o = (size_t)offset + s;
+        const double d0 = deltas[o * 2];
+        const double alpha = 1.0 - exp(-sigmas[o] * d0);
+        const double w = alpha * T;
+        double q = 0.0;
+        for (uint32_t c = 0; c < C; c++) {
+            q += g[c] * feats[o * C + c];
+            grad_feats[o * C + c] = g[c] * w;
+        }
+        done += w * q;
+        T *= 1.0 - alpha;  // transmittance after this sample
+        grad_sigmas[o] = d0 * (T * q - (Q - done));
+        if (T < th) break;
+    }
+}
+
 __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* __restrict__ rays_alive,
                                                                      double* __restrict__ rays_t, const double* __restrict__ sigmas,
                                                                      const double* __restrict__ rgbs, const double* __restrict__ deltas,
@@ -882,6 +937,27 @@ extern "C" int ngp_composite_rays_train_geo_backward_f64(const double* grad_weig
     F64_LAUNCH_1D(k_f64_composite_train_geo_bwd, N, as_stream(stream), grad_weights_sum, grad_depth, grad_image, grad_distortion, sigmas, rgbs,
                   deltas, rays, weights_sum, depth, image, distortion, M, N, T_thresh, grad_sigmas, grad_rgbs);
     return check_launch("composite_rays_train_geo_backward_f64");
+}
+
+extern "C" int ngp_composite_rays_train_features_forward_f64(const double* sigmas, const double* feats, const double* deltas, const int32_t* rays,
+                                                             uint32_t M, uint32_t N, uint32_t C, float T_thresh, double* out, ngp_stream_t stream) {
+    NGP_REQUIRE(C >= 1 && C <= 256, NGP_ERR_INVALID, "composite_rays_train_features_forward_f64: C = %u is outside 1 .. 256", C);
+    if (N == 0 || M == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && feats && deltas && rays && out, NGP_ERR_INVALID, "composite_rays_train_features_forward_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_composite_feat_fwd, N, as_stream(stream), sigmas, feats, deltas, rays, M, N, C, T_thresh, out);
+    return check_launch("composite_rays_train_features_forward_f64");
+}
+
+extern "C" int ngp_composite_rays_train_features_backward_f64(const double* grad_out, const double* sigmas, const double* feats, const double* deltas,
+                                                              const int32_t* rays, const double* out, uint32_t M, uint32_t N, uint32_t C,
+                                                              float T_thresh, double* grad_sigmas, double* grad_feats, ngp_stream_t stream) {
+    NGP_REQUIRE(C >= 1 && C <= 256, NGP_ERR_INVALID, "composite_rays_train_features_backward_f64: C = %u is outside 1 .. 256", C);
+    if (N == 0 || M == 0) return NGP_OK;
+    NGP_REQUIRE(grad_out && sigmas && feats && deltas && rays && out && grad_sigmas && grad_feats, NGP_ERR_INVALID,
+                "composite_rays_train_features_backward_f64: NULL tensor");
+    F64_LAUNCH_1D(k_f64_composite_feat_bwd, N, as_stream(stream), grad_out, sigmas, feats, deltas, rays, out, M, N, C, T_thresh, grad_sigmas,
+                  grad_feats);
+    return check_launch("composite_rays_train_features_backward_f64");
 }
 
 extern "C" int ngp_composite_rays_f64(uint32_t n_alive, uint32_t n_step, float T_thresh, int32_t* rays_alive, double* rays_t, const double* sigmas,

@@ -1713,6 +1713,230 @@ __global__ __launch_bounds__(RM_THREADS) void k_cull_rays(const float* __restric
     rays_alive[n] = keep ? (int32_t)n : -1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// compositing of per-sample feature channels (extension): out[index, c] = sum_i w_i feats[offset + i, c], 1 <= C <= 256,
+// over the live samples and with the weights of k_composite_train_fwd (the same expressions, the same live set)
+// ---------------------------------------------------------------------------------------------
+// The weight / transmittance scan is the compositors' (lanes over the 64 samples of a row).  The channel work never strides by C between
+// lanes: a row's features are one slab of 64 C contiguous elements, walked so that the busy lanes of a load read consecutive addresses.
+//   C <= 32 (narrow): P = C rounded up to a power of two (1 << lp), 64 / P samples per pass, lane = (sample-in-pass j = lane / P, channel
+//                     c = lane % P); lanes with c >= C idle (more than half are busy), the busy ones cover (64 / P) C consecutive elements.
+//                     The sample's weight comes over by a lane read (ds_bpermute), the backward's q goes back the same way.
+//   C  > 32 (wide):   one sample per step, lane = channel within blocks of 64 (up to four); the weight is a v_readlane.
+// A power-of-two segment keeps every reduction on the DPP butterflies below: a fixed order, no atomics, no LDS memory.
+template <int CTRL>
+__device__ __forceinline__ float dpp_perm(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float lane_at(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+// sum over each aligned group of 1 << lp lanes (lp <= 5), every lane of the group gets it; all 64 lanes must be active.  Butterfly:
+// a + b and b + a are the same bits, so the lanes of a group agree.
+__device__ __forceinline__ float seg_sum(float v, uint32_t lp, int lane) {
+    if (lp >= 1) v += dpp_perm<0xB1>(v);    // quad_perm [1,0,3,2]
+    if (lp >= 2) v += dpp_perm<0x4E>(v);    // quad_perm [2,3,0,1]
+    if (lp >= 3) v += dpp_perm<0x141>(v);   // row_half_mirror
+    if (lp >= 4) v += dpp_perm<0x140>(v);   // row_mirror
+    if (lp >= 5) {
+        const float lo = lane_at(v, 0) + lane_at(v, 16), hi = lane_at(v, 32) + lane_at(v, 48);
+        v = lane < 32 ? lo : hi;
+    }
+    return v;
+}
+// sum over the wave, wave-uniform
+__device__ __forceinline__ float wave_all_sum(float v) {
+    v += dpp_perm<0xB1>(v);
+    v += dpp_perm<0x4E>(v);
+    v += dpp_perm<0x141>(v);
+    v += dpp_perm<0x140>(v);
+    return (lane_at(v, 0) + lane_at(v, 16)) + (lane_at(v, 32) + lane_at(v, 48));
+}
+__device__ __forceinline__ void store_feat(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store_feat(_Float16* p, float v) { *p = to_half_rne(v); }  // fp32 product, rounded once
+
+constexpr int CF_BLOCKS = 4;  // channel blocks of 64 in the wide layout: C <= 256
+constexpr int CF_UNROLL = 4;  // passes whose loads are in flight together (the pass loops hold convergent lane reads: unrolled by hand)
+
+template <typename F, bool WIDE>
+__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_feat_fwd(const float* __restrict__ sigmas, const F* __restrict__ feats,
+                                                                      const float* __restrict__ deltas, const int32_t* __restrict__ rays,
+                                                                      uint32_t M, uint32_t N, uint32_t C, uint32_t lp, float T_thresh,
+                                                                      float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    const uint32_t spp = 64u >> lp, j = (uint32_t)lane >> lp, c = (uint32_t)lane & ((1u << lp) - 1u);  // narrow layout
+    float acc[WIDE ? CF_BLOCKS : 1] = {};
+    if (num != 0 && offset + num <= M) {
+        float T = 1.0f;
+        for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+            const uint32_t s = s0 + lane;
+            const bool valid = s < num;
+            float sg = 0.0f, d0 = 0.0f;
+            if (valid) {
+                sg = sigmas[offset + s];
+                d0 = deltas[(size_t)(offset + s) * 2];
+            }
+            const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
+            const float pin = wave_incl_prod(1.0f - alpha, lane);
+            const float T_before = T * prev_lane(1.0f, pin);
+            const bool live = valid && !(T_before < T_thresh);
+            const float w = live ? alpha * T_before : 0.0f;
+            const uint32_t nl = (uint32_t)__popcll(__ballot(live));  // the live samples are a prefix of the row
+            const F* __restrict__ row = feats + (size_t)(offset + s0) * C;
+            if constexpr (WIDE) {
+                for (uint32_t i0 = 0; i0 < nl; i0 += CF_UNROLL) {  // CF_UNROLL samples' loads are issued before the first is used
+                    float f[CF_UNROLL][CF_BLOCKS];
+#pragma unroll
+                    for (int u = 0; u < CF_UNROLL; u++)
+#pragma unroll
+                        for (int b = 0; b < CF_BLOCKS; b++) {
+                            const uint32_t ch = b * 64 + lane;
+                            f[u][b] = (ch < C && i0 + u < nl) ? (float)row[(i0 + u) * C + ch] : 0.0f;
+                        }
+#pragma unroll
+                    for (int u = 0; u < CF_UNROLL; u++) {
+                        const float wi = lane_at(w, (int)((i0 + u) & 63u));
+#pragma unroll
+                        for (int b = 0; b < CF_BLOCKS; b++) acc[b] = __builtin_fmaf(wi, f[u][b], acc[b]);  // a sample past nl adds w * 0
+                    }
+                }
+            } else {
+                const uint32_t npass = (nl + spp - 1u) >> (6u - lp);
+                for (uint32_t p0 = 0; p0 < npass; p0 += CF_UNROLL) {
+                    float f[CF_UNROLL];
+#pragma unroll
+                    for (int u = 0; u < CF_UNROLL; u++) {
+                        const uint32_t i = (p0 + u) * spp + j;  // a pass past npass: i >= nl
+                        f[u] = (c < C && i < nl) ? (float)row[i * C + c] : 0.0f;
+                    }
+#pragma unroll
+                    for (int u = 0; u < CF_UNROLL; u++) {
+                        const float wi = __shfl(w, (int)(((p0 + u) * spp + j) & 63u), 64);
+                        acc[0] = __builtin_fmaf(wi, f[u], acc[0]);
+                    }
+                }
+            }
+            T = T * lane63(pin);
+            if (T < T_thresh) break;  // wave-uniform
+        }
+    }
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int b = 0; b < CF_BLOCKS; b++) {
+            const uint32_t ch = b * 64 + lane;
+            if (ch < C) out[(size_t)index * C + ch] = acc[b];
+        }
+    } else {
+        float a = acc[0];  // lane (j, c): the samples j, j + spp, ... of every row; the segments are added in a butterfly
+        for (uint32_t o = 1u << lp; o < 64u; o <<= 1) a += __shfl_xor(a, (int)o, 64);
+        if ((uint32_t)lane < C) out[(size_t)index * C + lane] = a;  // segment 0: c == lane
+    }
+}
+
+// Backward.  With q_i = sum_c grad_out[c] feats[i, c] and Q = sum_c grad_out[c] out[c] (the saved output):
+//   grad_feats[i, c] = w_i grad_out[c],   grad_sigmas[i] = d0_i (T_{i+1} q_i - (Q - sum_{j<=i} w_j q_j))
+// -- the colour term of k_composite_train_bwd with the scalar q as the colour.  The channel pass reads feats and writes grad_feats at the
+// same consecutive addresses and reduces q_i over the channel lanes; q_i lands in lane i for the sample-layout scan.  Writes live rows only.
+template <typename F, bool WIDE>
+__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_feat_bwd(const float* __restrict__ grad_out, const float* __restrict__ sigmas,
+                                                                      const F* __restrict__ feats, const float* __restrict__ deltas,
+                                                                      const int32_t* __restrict__ rays, const float* __restrict__ out, uint32_t M,
+                                                                      uint32_t N, uint32_t C, uint32_t lp, float T_thresh,
+                                                                      float* __restrict__ grad_sigmas, F* __restrict__ grad_feats) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
+    if (n >= N) return;
+    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+    if (num == 0 || offset + num > M) return;
+    const uint32_t spp = 64u >> lp, j = (uint32_t)lane >> lp, c = (uint32_t)lane & ((1u << lp) - 1u);  // narrow layout
+    float g[WIDE ? CF_BLOCKS : 1];
+    float qt = 0.0f;
+    if constexpr (WIDE) {
+#pragma unroll
+        for (int b = 0; b < CF_BLOCKS; b++) {
+            const uint32_t ch = b * 64 + lane;
+            g[b] = ch < C ? grad_out[(size_t)index * C + ch] : 0.0f;
+            qt = __builtin_fmaf(g[b], ch < C ? out[(size_t)index * C + ch] : 0.0f, qt);
+        }
+    } else {
+        g[0] = c < C ? grad_out[(size_t)index * C + c] : 0.0f;
+        qt = (uint32_t)lane < C ? g[0] * out[(size_t)index * C + lane] : 0.0f;  // segment 0 only
+    }
+    const float Q = wave_all_sum(qt);
+    float T = 1.0f, carry = 0.0f;  // carries from previous rows
+    for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        const bool valid = s < num;
+        float sg = 0.0f, d0 = 0.0f;
+        if (valid) {
+            sg = sigmas[offset + s];
+            d0 = deltas[(size_t)(offset + s) * 2];
+        }
+        const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
+        const float pin = wave_incl_prod(1.0f - alpha, lane);
+        const float T_before = T * prev_lane(1.0f, pin);
+        const float T_after = T * pin;
+        const bool live = valid && !(T_before < T_thresh);
+        const float w = live ? alpha * T_before : 0.0f;
+        const uint32_t nl = (uint32_t)__popcll(__ballot(live));
+        const F* __restrict__ row = feats + (size_t)(offset + s0) * C;
+        F* __restrict__ grow = grad_feats + (size_t)(offset + s0) * C;
+        float q = 0.0f;  // q of sample s0 + lane
+        if constexpr (WIDE) {
+            for (uint32_t i0 = 0; i0 < nl; i0 += CF_UNROLL) {
+                float f[CF_UNROLL][CF_BLOCKS];
+#pragma unroll
+                for (int u = 0; u < CF_UNROLL; u++)
+#pragma unroll
+                    for (int b = 0; b < CF_BLOCKS; b++) {
+                        const uint32_t ch = b * 64 + lane;
+                        f[u][b] = (ch < C && i0 + u < nl) ? (float)row[(i0 + u) * C + ch] : 0.0f;
+                    }
+#pragma unroll
+                for (int u = 0; u < CF_UNROLL; u++) {
+                    const uint32_t i = i0 + u;
+                    const float wi = lane_at(w, (int)(i & 63u));
+                    float pr = 0.0f;
+#pragma unroll
+                    for (int b = 0; b < CF_BLOCKS; b++) {
+                        const uint32_t ch = b * 64 + lane;
+                        pr = __builtin_fmaf(g[b], f[u][b], pr);
+                        if (ch < C && i < nl) store_feat(grow + i * C + ch, wi * g[b]);
+                    }
+                    const float qi = wave_all_sum(pr);
+                    q = (uint32_t)lane == i ? qi : q;  // i >= nl: a dead lane, q stays unused there (w = 0)
+                }
+            }
+        } else {
+            const uint32_t npass = (nl + spp - 1u) >> (6u - lp);
+            for (uint32_t p0 = 0; p0 < npass; p0 += CF_UNROLL) {
+                float f[CF_UNROLL];
+#pragma unroll
+                for (int u = 0; u < CF_UNROLL; u++) {
+                    const uint32_t i = (p0 + u) * spp + j;  // a pass past npass: i >= nl
+                    f[u] = (c < C && i < nl) ? (float)row[i * C + c] : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < CF_UNROLL; u++) {
+                    const uint32_t p = p0 + u, i = p * spp + j;
+                    const float wi = __shfl(w, (int)(i & 63u), 64);
+                    if (c < C && i < nl) store_feat(grow + i * C + c, wi * g[0]);
+                    const float qs = seg_sum(g[0] * f[u], lp, lane);
+                    // sample L of the row was segment L % spp of pass L / spp
+                    const float got = __shfl(qs, (int)(((uint32_t)lane & (spp - 1u)) << lp), 64);
+                    q = ((uint32_t)lane >> (6u - lp)) == p ? got : q;
+                }
+            }
+        }
+        const float sa = carry + wave_incl_sum(w * q, lane);  // sum_{j<=i} w_j q_j
+        if (live) grad_sigmas[offset + s] = d0 * (T_after * q - (Q - sa));
+        T = T * lane63(pin);
+        carry = lane63(sa);
+        if (T < T_thresh) break;
+    }
+}
+
 }  // namespace ngp
 
 using namespace ngp;
@@ -1944,6 +2168,58 @@ extern "C" int ngp_composite_rays_train_geo_backward(const float* grad_weights_s
                        grad_depth, grad_image, grad_distortion, sigmas, rgbs, deltas, rays, weights_sum, depth, image, distortion, M, N,
                        T_thresh, grad_sigmas, grad_rgbs);
     return check_launch("composite_rays_train_geo_backward");
+}
+
+// lp of the narrow layout (C <= 32): the power of two that holds C
+static uint32_t feat_log2_segment(uint32_t C) {
+    uint32_t lp = 0;
+    while ((1u << lp) < C) lp++;
+    return lp;
+}
+
+static int feat_args_ok(const char* what, uint32_t C, int feat_dtype) {
+    NGP_REQUIRE(C >= 1 && C <= 64u * CF_BLOCKS, NGP_ERR_INVALID, "%s: C = %u is outside 1 .. %u", what, C, 64u * CF_BLOCKS);
+    NGP_REQUIRE(feat_dtype == NGP_F32 || feat_dtype == NGP_F16, NGP_ERR_INVALID, "%s: feat_dtype %d is neither NGP_F32 nor NGP_F16 (C = %u)", what,
+                feat_dtype, C);
+    return NGP_OK;
+}
+
+extern "C" int ngp_composite_rays_train_features_forward(const float* sigmas, const void* feats, const float* deltas, const int32_t* rays, uint32_t M,
+                                                         uint32_t N, uint32_t C, float T_thresh, int feat_dtype, float* out, ngp_stream_t stream) {
+    const int rc = feat_args_ok("composite_rays_train_features_forward", C, feat_dtype);
+    if (rc != NGP_OK) return rc;
+    if (N == 0 || M == 0) return NGP_OK;
+    NGP_REQUIRE(sigmas && feats && deltas && rays && out, NGP_ERR_INVALID, "composite_rays_train_features_forward: NULL tensor");
+    const dim3 grid(cdiv(N, CT_WAVES)), block(CT_WAVES * 64);
+    const bool wide = C > 32;
+    const uint32_t lp = wide ? 6u : feat_log2_segment(C);
+#define NGP_FEAT_FWD(F, WIDE)                                                                                                         \
+    hipLaunchKernelGGL((k_composite_feat_fwd<F, WIDE>), grid, block, 0, as_stream(stream), sigmas, static_cast<const F*>(feats), deltas, rays, M, N, \
+                       C, lp, T_thresh, out)
+    if (feat_dtype == NGP_F16) { if (wide) NGP_FEAT_FWD(_Float16, true); else NGP_FEAT_FWD(_Float16, false); }
+    else { if (wide) NGP_FEAT_FWD(float, true); else NGP_FEAT_FWD(float, false); }
+#undef NGP_FEAT_FWD
+    return check_launch("composite_rays_train_features_forward");
+}
+
+extern "C" int ngp_composite_rays_train_features_backward(const float* grad_out, const float* sigmas, const void* feats, const float* deltas,
+                                                          const int32_t* rays, const float* out, uint32_t M, uint32_t N, uint32_t C, float T_thresh,
+                                                          int feat_dtype, float* grad_sigmas, void* grad_feats, ngp_stream_t stream) {
+    const int rc = feat_args_ok("composite_rays_train_features_backward", C, feat_dtype);
+    if (rc != NGP_OK) return rc;
+    if (N == 0 || M == 0) return NGP_OK;
+    NGP_REQUIRE(grad_out && sigmas && feats && deltas && rays && out && grad_sigmas && grad_feats, NGP_ERR_INVALID,
+                "composite_rays_train_features_backward: NULL tensor");
+    const dim3 grid(cdiv(N, CT_WAVES)), block(CT_WAVES * 64);
+    const bool wide = C > 32;
+    const uint32_t lp = wide ? 6u : feat_log2_segment(C);
+#define NGP_FEAT_BWD(F, WIDE)                                                                                                              \
+    hipLaunchKernelGGL((k_composite_feat_bwd<F, WIDE>), grid, block, 0, as_stream(stream), grad_out, sigmas, static_cast<const F*>(feats), deltas, rays, \
+                       out, M, N, C, lp, T_thresh, grad_sigmas, static_cast<F*>(grad_feats))
+    if (feat_dtype == NGP_F16) { if (wide) NGP_FEAT_BWD(_Float16, true); else NGP_FEAT_BWD(_Float16, false); }
+    else { if (wide) NGP_FEAT_BWD(float, true); else NGP_FEAT_BWD(float, false); }
+#undef NGP_FEAT_BWD
+    return check_launch("composite_rays_train_features_backward");
 }
 
 extern "C" int ngp_composite_train_loss_backward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,

@@ -105,6 +105,8 @@ def render_sharded(model, rays_o, rays_d, rank=None, world=None, group=None, **k
     one caveat, the same as in nerf/renderer.py's eval loop: the loop stops once the sum of n_step = clamp(N // n_alive, 1, 8) reaches
     max_steps, and that sequence depends on how many rays share the launch, so a ray that still needs samples at that point (bound > 1
     with dt_gamma = 0 can need more than max_steps) is cut off at a different sample when the frame is sharded."""
+    if kwargs.get('aux') is not None:
+        raise NotImplementedError("render_sharded(aux=...): the sharded frame gathers image and depth only; the 'aux' channels are a training output")
     rank = dist.get_rank(group) if rank is None else rank
     world = dist.get_world_size(group) if world is None else world
     n = rays_o.shape[-2]

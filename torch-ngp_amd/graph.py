@@ -337,7 +337,8 @@ class GraphedTrainStep:
             return False
         # geo: the caller wants depth_raw / distortion in the render's results and its own loss on them; the direct iteration serves the
         # geometry terms it knows through `geo_loss` (read with getattr in _iteration_args: _direct_ok does not depend on it)
-        if kw.get('staged', False) or kw.get('geo', False):
+        # aux: the caller's own channels are composited on the autograd path only
+        if kw.get('staged', False) or kw.get('geo', False) or kw.get('aux', None) is not None:
             return False
         bg = kw.get('bg_color', None)
         with torch.autocast('cuda', dtype=self.autocast_dtype):  # the fused path IS the fp16-autocast arithmetic; it checks for it

@@ -160,10 +160,11 @@ class NeRFRenderer(nn.Module):
         depth = torch.clamp(depth - nears, min=0) / (fars - nears)
         return image.view(*lead, 3), depth.view(*lead)
 
-    def _fused_render_ok(self, rays_o, rays_d, bg_color, force_all_rays, geo=False):
+    def _fused_render_ok(self, rays_o, rays_d, bg_color, force_all_rays, geo=False, aux=None):
         """the fused training render needs the estimate-sized sample buffer (no host read-back), a plain colour background and a
-        network the fused sample pipeline accepts (network_ff.NeRFNetwork._fused_ok); it has no geometry outputs (geo)"""
-        if geo or not getattr(self, 'fused', False) or force_all_rays or self.mean_count <= 0 or self.bg_radius > 0:
+        network the fused sample pipeline accepts (network_ff.NeRFNetwork._fused_ok); it has no geometry outputs (geo) and composites no
+        channels of the caller's (aux)"""
+        if geo or aux is not None or not getattr(self, 'fused', False) or force_all_rays or self.mean_count <= 0 or self.bg_radius > 0:
             return False
         if not (rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32):
             return False
@@ -178,10 +179,15 @@ class NeRFRenderer(nn.Module):
         return bool(probe(dummy, dummy)) and torch.is_grad_enabled()
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
-                 T_thresh=1e-4, geo=False, **kwargs):
+                 T_thresh=1e-4, geo=False, aux=None, **kwargs):
         # rays_o, rays_d [B, N, 3] (B == 1) -> {'image' [B,N,3], 'depth' [B,N], ('weights_sum' when training)}
         # geo (extension, training only): composite with raymarching.composite_rays_train_geo -- 'depth' becomes differentiable
         # and the results gain 'depth_raw' [N] (the compositor's un-normalised depth) and 'distortion' [N] (EffDistLoss per ray / (far - near))
+        # aux (extension, training only): a callable (xyzs, dirs, sigmas, rgbs) -> [M,C] evaluated on the marched samples; the
+        # results gain 'aux' [N,C], its raw composite under the rays' weights (raymarching.composite_rays_train_features, no background blend)
+        if aux is not None and not self.training:
+            raise NotImplementedError("render(aux=...): the 'aux' channels are composited by the training compositor only (model.train()); the "
+                                      "inference loop has no feature compositor")
         lead = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -190,7 +196,7 @@ class NeRFRenderer(nn.Module):
         box = self.aabb_train if self.training else self.aabb_infer
         results = {}
 
-        if self.training and self.bg_radius <= 0 and self._fused_render_ok(rays_o, rays_d, 1 if bg_color is None else bg_color, force_all_rays, geo):
+        if self.training and self.bg_radius <= 0 and self._fused_render_ok(rays_o, rays_d, 1 if bg_color is None else bg_color, force_all_rays, geo, aux):
             bg_color = 1 if bg_color is None else bg_color
             # extension (fused.py): the whole training branch below as one autograd Function, identical arithmetic
             from fused import fused_render_train
@@ -215,6 +221,10 @@ class NeRFRenderer(nn.Module):
                 self.mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps)
             sigmas, rgbs = self(xyzs, dirs)
             sigmas = self.density_scale * sigmas
+            if aux is not None:
+                if sigmas.dim() == 2:
+                    raise NotImplementedError("render(aux=...): 'aux' is not provided for stacked residual models")
+                results['aux'] = raymarching.composite_rays_train_features(sigmas, aux(xyzs, dirs, sigmas, rgbs), deltas, rays, T_thresh)
             if geo:
                 composite = raymarching.composite_rays_train_geo
             else:
@@ -694,6 +704,9 @@ class NeRFRenderer(nn.Module):
 
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
         """renderer.py:540-574: run_cuda with cuda_ray (never staged), else `run`, in ray batches of `max_ray_batch` when staged"""
+        if kwargs.get('aux') is not None and (staged or not self.cuda_ray):
+            raise NotImplementedError("render(aux=...): the 'aux' channels need the cuda_ray training render; the staged / non-cuda_ray path "
+                                      "does not composite them")
         if self.cuda_ray:
             return self.run_cuda(rays_o, rays_d, **kwargs)
         if not staged:

@@ -147,6 +147,48 @@ def composite_rays_train_geo_backward(grad_weights_sum, grad_depth, grad_image, 
         capi.ptr(grad_sigmas), capi.ptr(grad_rgbs), capi.stream()))
 
 
+def composite_rays_train_features_forward(sigmas, feats, deltas, rays, M, N, C, T_thresh, out):
+    """extension (include/ngp_hip.h, ngp_composite_rays_train_features_forward): out [N,C] = the composite of the per-sample channels feats
+    [M,C].  float64 everywhere, or sigmas / deltas / out float32 with feats float32 or float16 (converted at the load).  ctypes-only, like the
+    geometry compositor's entries."""
+    _i32(rays, 'rays')
+    if _f64(((sigmas, 'sigmas'), (feats, 'feats'), (deltas, 'deltas'), (out, 'out'))):
+        capi.check(capi.lib.ngp_composite_rays_train_features_forward_f64(capi.ptr(sigmas), capi.ptr(feats), capi.ptr(deltas), capi.ptr(rays), M, N, C,
+                                                                          float(T_thresh), capi.ptr(out), capi.stream()))
+        return
+    for t, n in ((sigmas, 'sigmas'), (deltas, 'deltas'), (out, 'out')):
+        _f32(t, n)
+    capi.check(capi.lib.ngp_composite_rays_train_features_forward(capi.ptr(sigmas), capi.ptr(capi.dense(feats, 'feats')), capi.ptr(deltas),
+                                                                  capi.ptr(rays), M, N, C, float(T_thresh), _feat_code(feats, 'feats'), capi.ptr(out),
+                                                                  capi.stream()))
+
+
+def composite_rays_train_features_backward(grad_out, sigmas, feats, deltas, rays, out, M, N, C, T_thresh, grad_sigmas, grad_feats):
+    """extension (ngp_composite_rays_train_features_backward): grad_sigmas [M] and grad_feats [M,C] (the dtype of feats), pre-zeroed by the
+    caller -- rows no ray composites are not written"""
+    _i32(rays, 'rays')
+    if _f64(((grad_out, 'grad_out'), (sigmas, 'sigmas'), (feats, 'feats'), (deltas, 'deltas'), (out, 'out'), (grad_sigmas, 'grad_sigmas'),
+             (grad_feats, 'grad_feats'))):
+        capi.check(capi.lib.ngp_composite_rays_train_features_backward_f64(
+            capi.ptr(grad_out), capi.ptr(sigmas), capi.ptr(feats), capi.ptr(deltas), capi.ptr(rays), capi.ptr(out), M, N, C, float(T_thresh),
+            capi.ptr(grad_sigmas), capi.ptr(grad_feats), capi.stream()))
+        return
+    for t, n in ((grad_out, 'grad_out'), (sigmas, 'sigmas'), (deltas, 'deltas'), (out, 'out'), (grad_sigmas, 'grad_sigmas')):
+        _f32(t, n)
+    capi.dense(feats, 'feats'); capi.dense(grad_feats, 'grad_feats')
+    if grad_feats.dtype != feats.dtype:
+        raise RuntimeError(f"grad_feats must have the dtype of feats ({feats.dtype}, got {grad_feats.dtype})")
+    capi.check(capi.lib.ngp_composite_rays_train_features_backward(
+        capi.ptr(grad_out), capi.ptr(sigmas), capi.ptr(feats), capi.ptr(deltas), capi.ptr(rays), capi.ptr(out), M, N, C, float(T_thresh),
+        _feat_code(feats, 'feats'), capi.ptr(grad_sigmas), capi.ptr(grad_feats), capi.stream()))
+
+
+def _feat_code(t, name):
+    if t.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"{name} must be a float32 or float16 tensor (got {t.dtype})")
+    return capi.float_code(t, name)
+
+
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears, fars, xyzs, dirs,
                deltas, noises):
     for t, n in ((rays_t, 'rays_t'), (rays_o, 'rays_o'), (rays_d, 'rays_d'), (nears, 'nears'), (fars, 'fars'), (xyzs, 'xyzs'),

@@ -22,7 +22,7 @@ except ImportError:
 from . import backend as _geo  # the geometry compositor's entries are ctypes-only: the compiled module's table is the reference's
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'packbits_capped', 'march_rays_train',
-           'composite_rays_train', 'composite_rays_train_geo', 'march_rays', 'composite_rays', 'compact_rays', 'update_density_grid', 'density_grid_state']
+           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'march_rays', 'composite_rays', 'compact_rays', 'update_density_grid', 'density_grid_state']
 
 _f32_fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 
@@ -266,6 +266,51 @@ class _composite_rays_train_geo(Function):
 
 
 composite_rays_train_geo = _composite_rays_train_geo.apply
+
+
+class _composite_rays_train_features(Function):
+    """Extension (not in the reference): composite arbitrary per-sample channels with the volume-rendering weights of
+    composite_rays_train,  out[n, c] = sum_i w_i feats[i, c]  over the samples ray n composites -- a normal map, semantic logits, a distilled
+    feature field, any per-sample regulariser -- in one launch each way for 1 <= C <= 256 channels, without materialising the weights.
+    A channel of ones gives weights_sum; dividing by it gives the expectation of the channels under the ray's weights.  No background is
+    blended in.  float64 goes in and out as float64.  Otherwise sigmas and deltas are taken as float32 and out is float32, while float16
+    features stay float16 (also under autocast; they are converted at the load and accumulated in float32) and get a float16 gradient.
+    First order only; features that come out of a create_graph=True gradient are fine (grad_feats flows back into that graph)."""
+
+    @staticmethod
+    def forward(ctx, sigmas, feats, deltas, rays, T_thresh=1e-4):
+        """sigmas [M], feats [M,C], deltas [M,2], rays [N,3] -> out [N,C]"""
+        if sigmas.dtype == torch.float64 or feats.dtype == torch.float64 or deltas.dtype == torch.float64:
+            sigmas, feats, deltas = sigmas.double(), feats.double(), deltas.double()
+        else:  # no custom_fwd cast: it would up-cast float16 features
+            sigmas, deltas = sigmas.float(), deltas.float()
+            feats = feats if feats.dtype == torch.float16 else feats.float()
+        if feats.dim() != 2 or feats.shape[0] != sigmas.shape[0]:
+            raise RuntimeError(f"composite_rays_train_features: feats must be [M,C] with M = {sigmas.shape[0]} (got {tuple(feats.shape)})")
+        sigmas, feats, deltas = sigmas.contiguous(), feats.contiguous(), deltas.contiguous()
+        n_samples, n_rays, n_ch = sigmas.shape[0], rays.shape[0], feats.shape[1]
+        # every ray's row is written by the kernel; without samples nothing is launched
+        out = (torch.zeros if n_samples == 0 else torch.empty)(n_rays, n_ch, dtype=sigmas.dtype, device=sigmas.device)
+        _geo.composite_rays_train_features_forward(sigmas, feats, deltas, rays, n_samples, n_rays, n_ch, T_thresh, out)
+        ctx.save_for_backward(sigmas, feats, deltas, rays, out)
+        ctx.sizes = (n_samples, n_rays, n_ch, T_thresh)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled() and grad_out.requires_grad:
+            raise RuntimeError("composite_rays_train_features: second-order gradients are not provided (the compositor's backward is not "
+                               "differentiable; raymarching stays first-order)")
+        sigmas, feats, deltas, rays, out = ctx.saved_tensors
+        n_samples, n_rays, n_ch, T_thresh = ctx.sizes
+        grad_sigmas = torch.zeros_like(sigmas)
+        grad_feats = torch.zeros_like(feats)
+        _geo.composite_rays_train_features_backward(grad_out.to(out.dtype).contiguous(), sigmas, feats, deltas, rays, out, n_samples, n_rays, n_ch,
+                                                    T_thresh, grad_sigmas, grad_feats)
+        return grad_sigmas, grad_feats, None, None, None
+
+
+composite_rays_train_features = _composite_rays_train_features.apply
 
 
 # ----------------------------------------------------------------------------------------------
