@@ -6,6 +6,7 @@ import torch
 
 import oracle
 import synthetic_scene as sc
+from render_loop_cases import fields as _fields, random_rays as _random_rays, scene as _scene   # shared with tests/test_gpu_render_loop.py
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +20,6 @@ def cu(a):
 def _rm():
     import raymarching
     return raymarching
-
-
-def _random_rays(N, seed, radius=3.2, spread=0.6):
-    rng = np.random.default_rng(seed)
-    o = rng.normal(size=(N, 3))
-    o = (radius * o / np.linalg.norm(o, axis=1, keepdims=True)).astype(np.float32)
-    t = rng.uniform(-spread, spread, size=(N, 3))
-    d = t - o
-    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
-    return o, d
 
 
 def test_near_far_bit_exact():
@@ -80,17 +71,6 @@ def test_packbits_bit_exact_and_in_place():
     assert out[0].item() == 0xF0
     out2 = _rm().packbits(cu(g), 3.5)
     assert torch.equal(out2, bf)
-
-
-def _scene(bound, cascade, seed=0, fill=0.05):
-    if bound == 1 and cascade == 1:
-        grid = sc.occupancy_density()
-        return oracle.packbits(grid, 10.0)
-    rng = np.random.default_rng(seed)
-    # blocky random occupancy so that rays see runs of occupied and empty voxels in every cascade
-    coarse = rng.uniform(size=(cascade, 16, 16, 16)) < fill * 3
-    g = np.repeat(np.repeat(np.repeat(coarse, 8, 1), 8, 2), 8, 3).reshape(cascade, -1).astype(np.float32)
-    return oracle.packbits(g, 0.5)
 
 
 @pytest.mark.parametrize('bound,cascade,dt_gamma,perturb,N', [
@@ -236,12 +216,6 @@ def test_march_rays_train_wrapper_semantics():
     assert np.array_equal(x2.cpu().numpy(), ref2[0]) and np.array_equal(de2.cpu().numpy(), ref2[2])
 
 
-def _fields(xyzs):
-    sig = (25.0 * np.exp(-3.0 * (xyzs ** 2).sum(-1)) + 2.0 * (xyzs[:, 0] > 0.2)).astype(np.float32)
-    rgb = (0.5 + 0.5 * np.sin(3.0 * xyzs + np.array([0.0, 1.0, 2.0]))).astype(np.float32)
-    return sig, rgb
-
-
 def test_composite_train_forward_backward():
     bits = _scene(1.0, 1)
     o, d = _random_rays(4096, 7)
@@ -310,6 +284,11 @@ def test_inference_loop_matches_oracle_loop():
         alive2, rt, ws, dep, img = oracle.composite_rays(n_alive, n_step, alive, rt, sig, rgb, de, ws, dep, img, T_thresh=1e-4)
         rm.composite_rays(n_alive, n_step, galive, grt, cu(sig), cu(rgb), gde, gws, gdep, gimg, 1e-4)
         ga = galive.cpu().numpy()
+        # the kernel's accumulators against the oracle's on the rays whose alive verdict agrees (before both loops are re-synchronised below)
+        agree = alive[(ga >= 0) == (alive2 >= 0)]
+        np.testing.assert_allclose(gws.cpu().numpy()[agree], ws[agree], rtol=1e-4, atol=2e-5)
+        np.testing.assert_allclose(gimg.cpu().numpy()[agree], img[agree], rtol=1e-4, atol=2e-5)
+        np.testing.assert_allclose(gdep.cpu().numpy()[agree], dep[agree], rtol=1e-4, atol=5e-5)
         # fp32 transmittance (1 - weights_sum near 1 resolves 6e-8) vs the oracle's double may flip the T < T_thresh test
         # of a ray sitting on the threshold: tolerate a couple of rays per step
         assert (ga != alive2).sum() <= max(2, int(1e-3 * n_alive))
