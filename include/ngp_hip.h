@@ -390,6 +390,11 @@ int ngp_density_grid_update(const float* sigmas, const int64_t* cells, uint32_t 
 #define NGP_FF_RECOMPUTE 32u   /* backward of a 64-wide ReLU net with 32 inputs and 2 / 3 layers: forward_buffer is not read (may be NULL); the
                                  * hidden activations are recomputed from `inputs` -- bit for bit what the forward pass would have stored.
                                  * ngp_network_forward(training) with both forward buffers NULL is the matching forward: it does not store them */
+#define NGP_FF_SERIAL_FLUSH 64u /* testing: the register-resident backward kernels sum their waves' weight-gradient accumulators in the reference
+                                 * form -- one wave after the other into one LDS copy -- instead of the staged parallel sum; same additions in
+                                 * the same order, so the same bits (tests/test_gpu_ffmlp_slab_sum.py).  No effect on the shapes that only have the
+                                 * serial form: the layered kernels, the paired kernel of 64-wide 3-layer nets with more than 32 inputs, the
+                                 * single-wave kernel of 64-wide nets with 3 or 4 layers */
 int ngp_ffmlp_forward_ex(const void* inputs, const void* weights, uint32_t B, uint32_t input_dim, uint32_t output_dim,
                          uint32_t hidden_dim, uint32_t num_layers, uint32_t activation, uint32_t output_activation,
                          void* forward_buffer, void* outputs, uint32_t flags, ngp_stream_t stream);
@@ -454,7 +459,7 @@ int ngp_network_forward_rows(const void* enc, const float* dirs, uint32_t M, uin
  *  - ngp_network_backward_color = ngp_ffmlp_backward_ex of the colour MLP (32 -> 64 x (n-1) -> 16, ReLU, n = 2 or 3) whose input-gradient
  *    epilogue writes the sigma net's output gradient grad_h16 [M,16] directly (what ngp_pipeline_mid_backward would assemble from
  *    grad_sigma [M], h16 [M,16] and dL/d(colour input)[:,16:31]); same bits, one launch and a [M,32] round trip less.
- *    flags: 0, NGP_FF_DEFER_REDUCE, NGP_FF_RECOMPUTE (forward_buffer_color may then be NULL).
+ *    flags: 0, NGP_FF_DEFER_REDUCE, NGP_FF_RECOMPUTE (forward_buffer_color may then be NULL), NGP_FF_SERIAL_FLUSH.
  *  - ngp_ffmlp_backward_slab_count: how many fp32 slabs [n_params] a deferred backward of that shape leaves at the start of its
  *    backward_buffer (0: the gradients were stored directly, nothing to sum).
  *  - ngp_ffmlp_reduce_slabs_pair: sums two slab sets (n_slabs x n_params fp32 each, either may be empty) into fp16 weight

@@ -863,12 +863,84 @@ __device__ __forceinline__ half8_t tile_x(const unsigned char* xb, uint32_t kb, 
     return v;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The workgroup's slab from its waves' weight-gradient accumulators (both register-resident backward kernels).
+// SS_COPIES waves (or wave pairs) hold a partial sum of every slab entry.  Each stages its accumulators in an LDS copy of its own -- plain
+// stores, all waves at once --, then all threads walk the entries and add the copies in copy order:  (((0 + c0) + c1) + c2) + c3,  the
+// additions the serial form (NGP_FF_SERIAL_FLUSH: one wave after the other into one zeroed copy) performs, in its order, so the same bits;
+// the leading 0 + keeps the sign of a zero what it was.  The sum goes straight to global memory.  The LDS behind it is the weight image
+// and the tile buffers, dead once every wave has left the tile loop.  Where SS_COPIES copies of the whole slab do not fit the LDS, the
+// slab is summed in contiguous parts, one pass each (the paired kernel says how it cuts it; slab_stage_bytes is the launcher's side of it).
+// Whether they fit is decided per kernel instantiation, from the largest slab it serves (in_dim <= 32 IN_JB): one form of the epilogue each.
+// ------------------------------------------------------------------------------------------------
+constexpr int SS_COPIES = 4;
+constexpr size_t SS_LDS_LIMIT = 160 * 1024;
+struct SlabPart { uint32_t p0, len; };  // slab entries [p0, p0 + len)
+template <int WIDTH, int IN_JB, int NHM>
+constexpr bool slab_fits_whole = (size_t)SS_COPIES * sizeof(float) * WIDTH * (32 * IN_JB + WIDTH * NHM + 16) <= SS_LDS_LIMIT;
+// The staged form is compiled into the instantiations whose accumulators leave registers for it.  Those that fill the register file as
+// they are -- more than ten 32x32 blocks in the one wave of k_ffmlp_backward (64-wide nets with 3 or 4 layers), more than six in a wave
+// of k_ffmlp_backward_paired (64-wide 3-layer nets with more than 32 inputs): on no training path of the NeRF networks, most of them
+// spilling already (tests/test_isa_invariants.py pins by how much) -- keep the serial form alone; a second consumer of every accumulator
+// costs them further spills.
+template <int WIDTH, int IN_JB, int NHM>
+constexpr bool slab_staged_single = Shape<WIDTH>::NIB * (1 + IN_JB + NHM * Shape<WIDTH>::NIB) <= 10;
+template <int WIDTH, int IN_JB, int NHM>
+constexpr bool slab_staged_paired = Shape<WIDTH>::NIB * (IN_JB + (NHM == 2 ? Shape<WIDTH>::NIB : 0)) <= 6 && Shape<WIDTH>::NIB * (1 + Shape<WIDTH>::NIB) <= 6;
+// the launcher's side: the whole slab, or the larger of the paired kernel's two parts -- everything behind the input layer's matrix, and that matrix
+constexpr size_t slab_stage_bytes(bool whole, uint32_t n_params, uint32_t len_in) {
+    const uint32_t rest = n_params - len_in;
+    return (size_t)SS_COPIES * sizeof(float) * (whole ? n_params : (rest > len_in ? rest : len_in));
+}
+
+// one wave's copy of a part; put() = the serial form's flush without its read: accumulator block (ib, jb) of the matrix at slab offset base
+struct SlabCopy {
+    float* at;
+    uint32_t p0;
+    int n, h;
+    __device__ __forceinline__ void put(const float16_t& a, uint32_t base, uint32_t ld, int ib, int jb, uint32_t rws, uint32_t cols) const {
+        const uint32_t i = 32 * jb + n;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t o = (uint32_t)acc_row(ib, h, r);
+            if (o < rws && i < cols) at[base - p0 + o * ld + i] = a[r];
+        }
+    }
+};
+
+// one pass, called by ALL threads of the workgroup: stage_fn(SlabCopy) stores this wave's accumulators of the part (a wave that holds none
+// stores nothing), copy = which of the SS_COPIES this wave fills.  Every entry of the part is stored by exactly one lane of each copy.
+template <int THREADS, typename StageFn>
+__device__ __forceinline__ void slab_sum_pass(float* stage, uint32_t lds_bytes, SlabPart p, int copy, float* __restrict__ slab,
+                                              half_t* __restrict__ direct, int n, int h, StageFn&& stage_fn) {
+    NGP_BOUNDS((size_t)SS_COPIES * p.len * sizeof(float) <= lds_bytes && p.len % 4 == 0);
+    (void)lds_bytes;
+    __syncthreads();  // the LDS is free: the tile loop, or the sum of the pass before, is over
+    stage_fn(SlabCopy{stage + (size_t)copy * p.len, p.p0, n, h});
+    __syncthreads();
+    for (uint32_t i = 4 * threadIdx.x; i < p.len; i += 4 * THREADS) {
+        float4_t c[SS_COPIES];
+#pragma unroll
+        for (int k = 0; k < SS_COPIES; k++) c[k] = *reinterpret_cast<const float4_t*>(stage + (size_t)k * p.len + i);
+        float4_t s = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < SS_COPIES; k++) s = s + c[k];
+        if (direct) {
+            const half4_t v = {to_half_rne(s[0]), to_half_rne(s[1]), to_half_rne(s[2]), to_half_rne(s[3])};
+            *reinterpret_cast<half4_t*>(direct + p.p0 + i) = v;
+        } else {
+            *reinterpret_cast<float4_t*>(slab + p.p0 + i) = s;
+        }
+    }
+}
+
 template <int WIDTH, int IN_JB /* ceil(in_dim/32) */, int NHM /* hidden matmuls = num_layers-1 */, bool RELU /* hidden activation is ReLU */>
 __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __restrict__ grad, const half_t* __restrict__ inputs,
                                                                const half_t* __restrict__ weights, const half_t* __restrict__ forward_buffer,
                                                                uint32_t n_tiles, uint32_t in_dim, uint32_t num_layers, uint32_t act,
                                                                bool with_dx, half_t* __restrict__ grad_inputs, float* __restrict__ slabs,
-                                                               half_t* __restrict__ grad_weights_direct, bool in_planar, bool dx_planar, uint32_t pf_depth) {
+                                                               half_t* __restrict__ grad_weights_direct, bool in_planar, bool dx_planar, uint32_t pf_depth,
+                                                               uint32_t lds_bytes, bool serial_flush) {
     constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half8_t* img = reinterpret_cast<half8_t*>(smem);
@@ -1027,9 +1099,33 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
     }
 
     // ---- combine the four waves' partial weight gradients in LDS, emit one slab per workgroup ----
-    __syncthreads();  // every wave is done with the weight image and the stages
     float* red = reinterpret_cast<float*>(smem);
     const uint32_t n_params = ff_param_count(in_dim, WIDTH, num_layers);
+    if (slab_staged_single<WIDTH, IN_JB, NHM> && !serial_flush) {
+        // every wave holds every matrix; the shapes that take this form are small enough for four copies of the whole slab: one pass
+        static_assert(!slab_staged_single<WIDTH, IN_JB, NHM> || slab_fits_whole<WIDTH, IN_JB, NHM>, "the single-wave staged sum is one pass");
+        slab_sum_pass<FF_THREADS>(red, lds_bytes, SlabPart{0, n_params}, wid, slabs + (size_t)blockIdx.x * n_params, grad_weights_direct, n, h,
+                                  [&](const SlabCopy& c) {
+#pragma unroll
+            for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                for (int jb = 0; jb < IN_JB; jb++) c.put(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
+#pragma unroll
+            for (int li = 0; li < NHM; li++) {
+                const uint32_t base = WIDTH * in_dim + (num_layers - 2 - li) * WIDTH * WIDTH;  // gw_hid[li]: the matmul into hidden layer num_layers-1-li
+#pragma unroll
+                for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                    for (int jb = 0; jb < NIB; jb++) c.put(gw_hid[li][ib][jb], base, WIDTH, ib, jb, WIDTH, WIDTH);
+            }
+            const uint32_t base_out = WIDTH * in_dim + (num_layers - 1) * WIDTH * WIDTH;
+#pragma unroll
+            for (int jb = 0; jb < NIB; jb++) c.put(gw_out[jb], base_out, WIDTH, 0, jb, 16, WIDTH);
+        });
+        return;
+    }
+    // the reference form (NGP_FF_SERIAL_FLUSH): the waves add into one zeroed copy, one after the other
+    __syncthreads();  // every wave is done with the weight image and the stages
     for (uint32_t i = threadIdx.x; i < n_params; i += FF_THREADS) red[i] = 0.0f;
     __syncthreads();
     // accumulator (row = output feature o, col = input feature i = lane&31)
@@ -1154,7 +1250,8 @@ __global__ __launch_bounds__(FP_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __restrict__ inputs, const half_t* __restrict__ weights,
                              const half_t* __restrict__ forward_buffer, uint32_t n_tiles, uint32_t in_dim, uint32_t num_layers, uint32_t act,
                              bool with_dx, half_t* __restrict__ grad_inputs, float* __restrict__ slabs,
-                             half_t* __restrict__ grad_weights_direct, bool in_planar, bool dx_planar, uint32_t pf_depth, MidEpilogue mid) {
+                             half_t* __restrict__ grad_weights_direct, bool in_planar, bool dx_planar, uint32_t pf_depth, MidEpilogue mid,
+                             uint32_t lds_bytes, bool serial_flush) {
     static_assert(NHM == 1 || NHM == 2, "the paired backward covers 2- and 3-layer networks");
     constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1262,6 +1359,14 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
     };
     const uint32_t base_out = WIDTH * in_dim + (num_layers - 1) * WIDTH * WIDTH;
     const uint32_t base_top = WIDTH * in_dim + (num_layers - 2) * WIDTH * WIDTH;  // hidden matmul into the last hidden layer
+    const uint32_t base_low = WIDTH * in_dim;                                     // (NHM == 2) hidden matmul into hidden layer 1
+    // the staged sum (slab_sum_pass): the pairs are the copies.  Four copies of the whole slab in one pass where they fit the LDS; else everything
+    // behind the input layer's matrix first -- both roles stage at once --, then that matrix, which only role 1 holds
+    constexpr bool whole = slab_fits_whole<WIDTH, IN_JB, NHM>;
+    const SlabPart part_a = whole ? SlabPart{0u, n_params} : SlabPart{base_low, n_params - base_low}, part_b = SlabPart{0u, base_low};
+    auto pass = [&](SlabPart p, auto&& stage_fn) {
+        slab_sum_pass<FP_THREADS>(red, lds_bytes, p, pair, slabs + (size_t)blockIdx.x * n_params, grad_weights_direct, n, h, stage_fn);
+    };
 
     if (role == 0) {
         // ---- dW_out and dW of the top hidden matmul ----
@@ -1320,6 +1425,19 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
             }
             end_of_round(base);
         }
+        if (slab_staged_paired<WIDTH, IN_JB, NHM> && !serial_flush) {
+            pass(part_a, [&](const SlabCopy& c) {
+#pragma unroll
+                for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                    for (int jb = 0; jb < NIB; jb++) c.put(gw_top[ib][jb], base_top, WIDTH, ib, jb, WIDTH, WIDTH);
+#pragma unroll
+                for (int jb = 0; jb < NIB; jb++) c.put(gw_out[jb], base_out, WIDTH, 0, jb, 16, WIDTH);
+            });
+            if constexpr (!whole) pass(part_b, [](const SlabCopy&) {});
+            return;
+        }
+        // the reference form (NGP_FF_SERIAL_FLUSH):
         begin_reduction();
         // the waves of a role add into the same entries, one after the other (a fixed order: deterministic); the two roles own disjoint
         // parts of the slab and take their turns at the same time
@@ -1480,6 +1598,25 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
             }
             end_of_round(base);
         }
+        if (slab_staged_paired<WIDTH, IN_JB, NHM> && !serial_flush) {
+            auto put_in = [&](const SlabCopy& c) {
+#pragma unroll
+                for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                    for (int jb = 0; jb < IN_JB; jb++) c.put(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
+            };
+            pass(part_a, [&](const SlabCopy& c) {
+                if constexpr (whole) put_in(c);
+                if constexpr (NHM == 2) {
+#pragma unroll
+                    for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                        for (int jb = 0; jb < NIB; jb++) c.put(gw_low[ib][jb], base_low, WIDTH, ib, jb, WIDTH, WIDTH);
+                }
+            });
+            if constexpr (!whole) pass(part_b, put_in);
+            return;
+        }
         begin_reduction();
         for (int turn = 0; turn < FP_PAIRS; turn++) {
             if (pair == turn) {
@@ -1488,7 +1625,6 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
 #pragma unroll
                     for (int jb = 0; jb < IN_JB; jb++) flush(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
                 if constexpr (NHM == 2) {
-                    const uint32_t base_low = WIDTH * in_dim;  // hidden matmul into hidden layer 1
 #pragma unroll
                     for (int ib = 0; ib < NIB; ib++)
 #pragma unroll
@@ -2012,6 +2148,13 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
     // counts cover the shapes should that change -- the recomputing variant, whose tiles are 3 KiB, does run three deep)
     size_t lds = (size_t)nfrag * 1024 + (size_t)pf_depth * FF_WAVES * tile_bytes;
     if (lds < (size_t)n_params * 4) lds = (size_t)n_params * 4;
+    // the epilogue stages the waves' accumulators in the same LDS (slab_sum_pass): four copies of the slab, or of its largest part
+    const bool serial = (flags & NGP_FF_SERIAL_FLUSH) != 0;
+    const bool paired = (NHM == 1 || NHM == 2) && !(flags & NGP_FF_SINGLE_WAVE);
+    constexpr bool whole = slab_fits_whole<WIDTH, IN_JB, NHM>;
+    const bool staged = !serial && (paired ? slab_staged_paired<WIDTH, IN_JB, NHM> : slab_staged_single<WIDTH, IN_JB, NHM>);
+    const size_t stage = staged ? slab_stage_bytes(whole, n_params, WIDTH * in_dim) : 0;
+    if (lds < stage) lds = stage;
     NGP_REQUIRE(lds <= 160 * 1024, NGP_ERR_INVALID, "ffmlp_backward: LDS need (%zu B) exceeds 160 KiB", lds);
     // one fp32 slab per workgroup lives in the caller's backward_buffer ([num_layers, B, hidden] fp16)
     const uint32_t blocks = backward_slab_count<WIDTH>(B, in_dim, num_layers);
@@ -2024,6 +2167,8 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             const uint32_t depth = 3;
             size_t lds_r = (size_t)(nfrag + ffrag) * 1024 + (size_t)depth * FP_PAIRS * tile_b + (size_t)FP_PAIRS * NHM * NKB * 1024;
             if (lds_r < (size_t)n_params * 4) lds_r = (size_t)n_params * 4;
+            if (lds_r < stage) lds_r = stage;
+            NGP_REQUIRE(lds_r <= 160 * 1024, NGP_ERR_INVALID, "ffmlp_backward: LDS need (%zu B) exceeds 160 KiB", lds_r);
             auto pk = k_ffmlp_backward_paired<WIDTH, IN_JB, NHM, RELU, true>;
             if (lds_r > 64 * 1024) {
                 hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
@@ -2033,7 +2178,7 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             hipLaunchKernelGGL(pk, dim3(direct ? 1 : blocks), dim3(FP_THREADS), lds_r, st, (const half_t*)grad, (const half_t*)inputs,
                                (const half_t*)weights, (const half_t*)nullptr, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs,
                                direct ? (float*)nullptr : (float*)backward_buffer, direct ? (half_t*)grad_weights : (half_t*)nullptr, in_planar,
-                               dx_planar, depth, mid);
+                               dx_planar, depth, mid, (uint32_t)lds_r, serial);
             int rc = check_launch("ffmlp_backward");
             if (rc || direct || defer) return rc;
             hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st,
@@ -2055,7 +2200,7 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             hipLaunchKernelGGL(pk, dim3(direct ? 1 : blocks), dim3(FP_THREADS), lds, st, (const half_t*)grad, (const half_t*)inputs,
                                (const half_t*)weights, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs,
                                direct ? (float*)nullptr : (float*)backward_buffer, direct ? (half_t*)grad_weights : (half_t*)nullptr, in_planar,
-                               dx_planar, pf_depth, mid);
+                               dx_planar, pf_depth, mid, (uint32_t)lds, serial);
             int rc = check_launch("ffmlp_backward");
             if (rc || direct || defer) return rc;  // deferred: the caller sums the slabs (ngp_ffmlp_reduce_slabs_pair)
             hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st,
@@ -2072,12 +2217,12 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
     if (blocks <= 1) {
         hipLaunchKernelGGL(kern, dim3(1), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)inputs, (const half_t*)weights,
                            (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs, (float*)nullptr,
-                           (half_t*)grad_weights, in_planar, dx_planar, pf_depth);
+                           (half_t*)grad_weights, in_planar, dx_planar, pf_depth, (uint32_t)lds, serial);
         return check_launch("ffmlp_backward");
     }
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)inputs, (const half_t*)weights,
                        (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs, (float*)backward_buffer,
-                       (half_t*)nullptr, in_planar, dx_planar, pf_depth);
+                       (half_t*)nullptr, in_planar, dx_planar, pf_depth, (uint32_t)lds, serial);
     int rc = check_launch("ffmlp_backward");
     if (rc) return rc;
     hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st, (const float*)backward_buffer, blocks, n_params,
@@ -2230,8 +2375,8 @@ extern "C" int ngp_network_backward_color(const void* grad_out16, const void* co
                                           ngp_stream_t stream) {
     NGP_REQUIRE(num_layers_color == 2 || num_layers_color == 3, NGP_ERR_INVALID,
                 "network_backward_color: 2 or 3 layers (got %u); use ngp_ffmlp_backward_ex + ngp_pipeline_mid_backward", num_layers_color);
-    NGP_REQUIRE(!(flags & ~(NGP_FF_DEFER_REDUCE | NGP_FF_RECOMPUTE)), NGP_ERR_INVALID,
-                "network_backward_color: only NGP_FF_DEFER_REDUCE and NGP_FF_RECOMPUTE are accepted");
+    NGP_REQUIRE(!(flags & ~(NGP_FF_DEFER_REDUCE | NGP_FF_RECOMPUTE | NGP_FF_SERIAL_FLUSH)), NGP_ERR_INVALID,
+                "network_backward_color: only NGP_FF_DEFER_REDUCE, NGP_FF_RECOMPUTE and NGP_FF_SERIAL_FLUSH are accepted");
     int rc = check_ff_args("network_backward_color", M, 32, 16, 64, num_layers_color);
     if (rc) return rc;
     if (M == 0) return NGP_OK;
