@@ -482,7 +482,8 @@ int ngp_pipeline_rgb_forward(const void* out16, float* rgb, uint32_t M, ngp_stre
 /* grad_out16 [M,16] fp16: columns 0..2 = grad_rgb * y (1 - y), the rest 0 */
 int ngp_pipeline_rgb_backward(const float* grad_rgb, const float* rgb, void* grad_out16, uint32_t M, ngp_stream_t stream);
 /* grad_h16 [M,16] fp16: column 0 = grad_sigma * exp(clamp(h0, -15, 15)) (activation.py:12-17), columns 1..15 =
- * grad_color_in[:,16:31] */
+ * grad_color_in[:,16:31].  A NaN h0 gives a NaN in column 0 (torch's clamp propagates it), here and in the epilogue of
+ * ngp_network_backward_color: the optimizer's non-finite sweep then sees it. */
 int ngp_pipeline_mid_backward(const float* grad_sigma, const void* h16, const void* grad_color_in, void* grad_h16, uint32_t M,
                               float density_scale, ngp_stream_t stream);
 

@@ -1560,7 +1560,8 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
                         half4_t a, b;
                         if (h == 0) {
                             const float x0 = (float)mid.h16[srow * 16];
-                            const float gs = (mid.density_scale * mid.grad_sigma[srow]) * expf(fminf(15.0f, fmaxf(-15.0f, x0)));
+                            // (a NaN h0 stays a NaN, as in k_mid_backward: fminf / fmaxf alone would clamp it to exp(-15))
+                            const float gs = (mid.density_scale * mid.grad_sigma[srow]) * (x0 != x0 ? x0 : expf(fminf(15.0f, fmaxf(-15.0f, x0))));
                             a = half4_t{to_half_rne(gs), v2[0], v2[1], v2[2]};          // columns 0..3
                             b = half4_t{(half_t)sib2, v3[0], v3[1], v3[2]};             // columns 8..11 (f23 from the sibling)
                         } else {

@@ -5,7 +5,8 @@
 //                  color_in = [ half(SH_4(dir)) | h[:,1:16] | 0 ]    (network_ff.py:64-68)
 //   rgb forward  : rgb = float(half(sigmoid(float(out[:, :3]))))     (network_ff.py:72: torch.sigmoid on the fp16 output)
 //   rgb backward : g_out[:, :3] = half(g_rgb * y * (1 - y)), g_out[:, 3:] = 0
-//   mid backward : g_h[:,0] = half(g_sigma * exp(clamp(float(h[:,0]), -15, 15))) (trunc_exp backward), g_h[:,1:16] = g_color_in[:,16:31]
+//   mid backward : g_h[:,0] = half(g_sigma * exp(clamp(float(h[:,0]), -15, 15))) (trunc_exp backward; a NaN h stays a NaN, as torch's clamp
+//                  keeps it), g_h[:,1:16] = g_color_in[:,16:31]
 // All are pure streams (HBM-bound, 60-130 B per sample); one lane handles one sample row with 16-byte accesses.
 #include "common.h"
 #include "sh_poly.inc"
@@ -79,7 +80,8 @@ __global__ __launch_bounds__(PL_THREADS) void k_mid_backward(const float* __rest
     const uint32_t b = blockIdx.x * PL_THREADS + threadIdx.x;
     if (b >= M) return;
     const float x = (float)h[(size_t)b * 16];
-    const float gs = (density_scale * grad_sigma[b]) * expf(fminf(15.0f, fmaxf(-15.0f, x)));
+    // fminf / fmaxf drop a NaN operand (the clamp would turn a NaN h0 into exp(-15)); x.clamp(-15, 15) of activation.py:16 propagates it
+    const float gs = (density_scale * grad_sigma[b]) * (x != x ? x : expf(fminf(15.0f, fmaxf(-15.0f, x))));
     const half8_t g2 = *reinterpret_cast<const half8_t*>(grad_color_in + (size_t)b * 32 + 16);
     const half8_t g3 = *reinterpret_cast<const half8_t*>(grad_color_in + (size_t)b * 32 + 24);
     half8_t lo, hi;
