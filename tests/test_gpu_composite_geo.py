@@ -1,7 +1,7 @@
 """GPU checks of the geometry compositor raymarching.composite_rays_train_geo (k_composite_train_geo_fwd / _bwd and their fp64 twins;
 DESIGN.md 3.9) on the shared ray table of tests/composite_geo_cases.py: fp64 against the O(K^2) definition and autograd (+ gradcheck); fp32
 bit-identical to composite_rays_train in everything the two share, the distortion and the full backward inside a yardstick measured from the
-float32 rounding of the same formulas on the CPU; depth's gradient (zero through composite_rays_train, as in the reference); determinism;
+float32 rounding of the same formulas on the CPU; the plain backward's zero fill (rows_used) against the pre-zeroed call; depth's gradient (zero through composite_rays_train, as in the reference); determinism;
 NeRFRenderer.run_cuda(geo=True).
 
 Figures measured on MI355X (kernel error against the float64 reference, bound = 4 x the CPU float32 error of the same formulas + 1e-7
@@ -144,6 +144,35 @@ def test_fp32_backward_leaves_uncomposited_rows_exactly_zero():
     assert dead.sum() > 600   # behind the two early stops, the overflowing ray's rows, the padding
     assert (got['grad_sigmas'][dead] == 0).all() and (got['grad_rgbs'][dead] == 0).all()
     assert (got['grad_sigmas'][~dead] != 0).all()
+
+
+@pytest.mark.parametrize('bg_mode, with_grad_ws', [(0, True), (2, False)])
+@pytest.mark.parametrize('early', [True, False])
+def test_fp32_backward_zero_fill_equals_the_prezeroed_call(early, bg_mode, with_grad_ws):
+    """ngp_composite_rays_train_backward_ex with rows_used into NaN-filled outputs (the kernel zeroes every row the compositing does not
+    reach) against the same call with rows_used = NULL into zero-filled ones: the run-time zero_fill of the sweep's fp32 sink"""
+    import _ngp_capi as capi
+    t, up, N = C.ray_table(early), C.upstream(), len(C.RAYS)
+    f32 = lambda a: cu(a, torch.float32)
+    sigmas, rgbs, deltas, rays = f32(t['sigmas']), f32(t['rgbs']), f32(t['deltas']), cu(t['rays'])
+    g_ws, g_img = (f32(up['weights_sum']) if with_grad_ws else None), f32(up['image'])
+    bg = f32(np.random.default_rng(11).uniform(0, 1, (N, 3))) if bg_mode == 2 else None
+    ws, depth, image = (torch.full(s, float('nan'), device='cuda') for s in ((N,), (N,), (N, 3)))
+    st = capi.stream()
+    capi.check(capi.lib.ngp_composite_rays_train_forward(sigmas.data_ptr(), rgbs.data_ptr(), deltas.data_ptr(), rays.data_ptr(), C.M, N, C.T_THRESH,
+                                                         ws.data_ptr(), depth.data_ptr(), image.data_ptr(), st))
+    rows_used = torch.tensor([t['used']], dtype=torch.int32, device='cuda')
+    got = {}
+    for filled in (True, False):
+        fill = float('nan') if filled else 0.0
+        gs, gc = torch.full((C.M,), fill, device='cuda'), torch.full((C.M, 3), fill, device='cuda')
+        capi.check(capi.lib.ngp_composite_rays_train_backward_ex(capi.ptr(g_ws), g_img.data_ptr(), sigmas.data_ptr(), rgbs.data_ptr(), deltas.data_ptr(),
+                                                                 rays.data_ptr(), ws.data_ptr(), image.data_ptr(), C.M, N, C.T_THRESH, gs.data_ptr(),
+                                                                 gc.data_ptr(), bg_mode, 0.0, capi.ptr(bg), rows_used.data_ptr() if filled else None, st))
+        got[filled] = (gs, gc)
+    assert torch.equal(got[True][0], got[False][0]) and torch.equal(got[True][1], got[False][1])
+    dead = torch.from_numpy(_dead_rows(early)).cuda()
+    assert bool((got[True][0][dead] == 0).all()) and bool((got[True][1][dead] == 0).all()) and bool(torch.isfinite(got[True][0]).all())
 
 
 # ------------------------------------------------------------------------------------------------

@@ -464,76 +464,15 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_packbits(const double* __re
 // ------------------------------------------------------------------------------------------------
 // compositing (raymarching.cu:488-661, 819-905): the reference's per-ray loops, one lane per ray
 // ------------------------------------------------------------------------------------------------
+// GEO (raymarching.hip: k_composite_train_geo_fwd / _bwd): differentiable depth and the distortion
+// L = sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 d0_i as L = sum_i 2 w_i (t_i W_<i - D_<i) + 1/3 sum_i w_i^2 d0_i, running sums in double.
+// Its terms sit under `if constexpr`, not behind zero factors: 0 * inf and -0 + 0 would change the plain op's bits.
+template <bool GEO>
 __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_fwd(const double* __restrict__ sigmas, const double* __restrict__ rgbs,
                                                                           const double* __restrict__ deltas, const int32_t* __restrict__ rays, uint32_t M,
                                                                           uint32_t N, float T_thresh, double* __restrict__ weights_sum,
-                                                                          double* __restrict__ depth, double* __restrict__ image) {
-    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
-    if (n >= N) return;
-    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
-    const double th = (double)T_thresh;
-    double r = 0.0, g = 0.0, b = 0.0, ws = 0.0, d = 0.0, T = 1.0, t = 0.0;
-    if (num != 0u && offset + num <= M) {
-        for (uint32_t s = 0; s < num; s++) {
-            const size_t o = (size_t)offset + s;
-            const double alpha = 1.0 - exp(-sigmas[o] * deltas[o * 2]);
-            const double w = alpha * T;
-            r += w * rgbs[o * 3];
-            g += w * rgbs[o * 3 + 1];
-            b += w * rgbs[o * 3 + 2];
-            t += deltas[o * 2 + 1];
-            d += w * t;
-            ws += w;
-            T *= 1.0 - alpha;
-            if (T < th) break;  // the sample that drives T below the threshold is composited (raymarching.cu:557-560)
-        }
-    }
-    weights_sum[index] = ws;
-    depth[index] = d;
-    image[index * 3] = r;
-    image[index * 3 + 1] = g;
-    image[index * 3 + 2] = b;
-}
-
-__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_bwd(const double* __restrict__ grad_ws, const double* __restrict__ grad_image,
-                                                                          const double* __restrict__ sigmas, const double* __restrict__ rgbs,
-                                                                          const double* __restrict__ deltas, const int32_t* __restrict__ rays,
-                                                                          const double* __restrict__ weights_sum, const double* __restrict__ image,
-                                                                          uint32_t M, uint32_t N, float T_thresh, double* __restrict__ grad_sigmas,
-                                                                          double* __restrict__ grad_rgbs) {
-    const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
-    if (n >= N) return;
-    const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
-    if (num == 0u || offset + num > M) return;
-    const double th = (double)T_thresh;
-    const double gi0 = grad_image[index * 3], gi1 = grad_image[index * 3 + 1], gi2 = grad_image[index * 3 + 2], gw = grad_ws[index];
-    const double rf = image[index * 3], gf = image[index * 3 + 1], bf = image[index * 3 + 2], wsf = weights_sum[index];
-    double r = 0.0, g = 0.0, b = 0.0, T = 1.0;
-    for (uint32_t s = 0; s < num; s++) {
-        const size_t o = (size_t)offset + s;
-        const double d0 = deltas[o * 2];
-        const double cr = rgbs[o * 3], cg = rgbs[o * 3 + 1], cb = rgbs[o * 3 + 2];
-        const double alpha = 1.0 - exp(-sigmas[o] * d0);
-        const double w = alpha * T;
-        r += w * cr;
-        g += w * cg;
-        b += w * cb;
-        T *= 1.0 - alpha;  // transmittance after this sample
-        grad_rgbs[o * 3] = gi0 * w;
-        grad_rgbs[o * 3 + 1] = gi1 * w;
-        grad_rgbs[o * 3 + 2] = gi2 * w;
-        grad_sigmas[o] = d0 * (gi0 * (T * cr - (rf - r)) + gi1 * (T * cg - (gf - g)) + gi2 * (T * cb - (bf - b)) + gw * (1.0 - wsf));
-        if (T < th) break;
-    }
-}
-
-// compositing for geometry losses (raymarching.hip: k_composite_train_geo_fwd / _bwd): differentiable depth and the distortion
-// L = sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 d0_i as L = sum_i 2 w_i (t_i W_<i - D_<i) + 1/3 sum_i w_i^2 d0_i, running sums in double
-__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_fwd(const double* __restrict__ sigmas, const double* __restrict__ rgbs,
-                                                                              const double* __restrict__ deltas, const int32_t* __restrict__ rays,
-                                                                              uint32_t M, uint32_t N, float T_thresh, double* __restrict__ weights_sum,
-                                                                              double* __restrict__ depth, double* __restrict__ image,
-                                                                              double* __restrict__ distortion) {
+                                                                          double* __restrict__ depth, double* __restrict__ image,
+                                                                          double* __restrict__ distortion) {
     const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
@@ -549,7 +488,7 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_fwd(con
             g += w * rgbs[o * 3 + 1];
             b += w * rgbs[o * 3 + 2];
             t += deltas[o * 2 + 1];
-            dist += 2.0 * w * (t * ws - d) + (1.0 / 3.0) * (w * w * d0);  // ws, d: the exclusive prefixes W_<i, D_<i
+            if constexpr (GEO) dist += 2.0 * w * (t * ws - d) + (1.0 / 3.0) * (w * w * d0);  // ws, d: the exclusive prefixes W_<i, D_<i
             d += w * t;
             ws += w;
             T *= 1.0 - alpha;
@@ -561,19 +500,20 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_fwd(con
     image[index * 3] = r;
     image[index * 3 + 1] = g;
     image[index * 3 + 2] = b;
-    distortion[index] = dist;
+    if constexpr (GEO) distortion[index] = dist;
 }
 
-// one sweep: g_i = dL/dw_i = 2 (t_i W_<i - D_<i) + 2 ((D - D_<=i) - t_i (W - W_<=i)) + 2/3 w_i d0_i, dD/dsigma_i = d0_i (T_{i+1} t_i - (D - D_<=i)),
-// dL/dsigma_i = d0_i (g_i T_{i+1} - (G - G_<=i)) with G = sum_j g_j w_j = 2 L; a NULL gradient is a zero gradient
-__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_bwd(const double* __restrict__ grad_ws, const double* __restrict__ grad_depth,
-                                                                              const double* __restrict__ grad_image, const double* __restrict__ grad_dist,
-                                                                              const double* __restrict__ sigmas, const double* __restrict__ rgbs,
-                                                                              const double* __restrict__ deltas, const int32_t* __restrict__ rays,
-                                                                              const double* __restrict__ weights_sum, const double* __restrict__ depth,
-                                                                              const double* __restrict__ image, const double* __restrict__ distortion,
-                                                                              uint32_t M, uint32_t N, float T_thresh, double* __restrict__ grad_sigmas,
-                                                                              double* __restrict__ grad_rgbs) {
+// one sweep.  GEO: g_i = dL/dw_i = 2 (t_i W_<i - D_<i) + 2 ((D - D_<=i) - t_i (W - W_<=i)) + 2/3 w_i d0_i, dD/dsigma_i = d0_i (T_{i+1} t_i - (D - D_<=i)),
+// dL/dsigma_i = d0_i (g_i T_{i+1} - (G - G_<=i)) with G = sum_j g_j w_j = 2 L; a NULL gradient is a zero gradient (the plain entry requires its two)
+template <bool GEO>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_bwd(const double* __restrict__ grad_ws, const double* __restrict__ grad_depth,
+                                                                          const double* __restrict__ grad_image, const double* __restrict__ grad_dist,
+                                                                          const double* __restrict__ sigmas, const double* __restrict__ rgbs,
+                                                                          const double* __restrict__ deltas, const int32_t* __restrict__ rays,
+                                                                          const double* __restrict__ weights_sum, const double* __restrict__ depth,
+                                                                          const double* __restrict__ image, const double* __restrict__ distortion,
+                                                                          uint32_t M, uint32_t N, float T_thresh, double* __restrict__ grad_sigmas,
+                                                                          double* __restrict__ grad_rgbs) {
     const uint32_t n = blockIdx.x * F64_THREADS + threadIdx.x;
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
@@ -581,9 +521,15 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_bwd(con
     const double th = (double)T_thresh;
     const double gi0 = grad_image ? grad_image[index * 3] : 0.0, gi1 = grad_image ? grad_image[index * 3 + 1] : 0.0,
                  gi2 = grad_image ? grad_image[index * 3 + 2] : 0.0;
-    const double gw = grad_ws ? grad_ws[index] : 0.0, gd = grad_depth ? grad_depth[index] : 0.0, gl = grad_dist ? grad_dist[index] : 0.0;
+    const double gw = grad_ws ? grad_ws[index] : 0.0;
     const double rf = image[index * 3], gf = image[index * 3 + 1], bf = image[index * 3 + 2], wsf = weights_sum[index];
-    const double df = depth[index], gtot = 2.0 * distortion[index];
+    double gd = 0.0, gl = 0.0, df = 0.0, gtot = 0.0;
+    if constexpr (GEO) {
+        gd = grad_depth ? grad_depth[index] : 0.0;
+        gl = grad_dist ? grad_dist[index] : 0.0;
+        df = depth[index];
+        gtot = 2.0 * distortion[index];
+    }
     double r = 0.0, g = 0.0, b = 0.0, ws = 0.0, d = 0.0, gg = 0.0, T = 1.0, t = 0.0;
     for (uint32_t s = 0; s < num; s++) {
         const size_t o = (size_t)offset + s;
@@ -591,21 +537,24 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_composite_train_geo_bwd(con
         const double cr = rgbs[o * 3], cg = rgbs[o * 3 + 1], cb = rgbs[o * 3 + 2];
         const double alpha = 1.0 - exp(-sigmas[o] * d0);
         const double w = alpha * T;
-        t += deltas[o * 2 + 1];
-        const double before = t * ws - d;  // t_i W_<i - D_<i
         r += w * cr;
         g += w * cg;
         b += w * cb;
-        ws += w;
-        d += w * t;
-        const double gwi = 2.0 * before + 2.0 * ((df - d) - t * (wsf - ws)) + (2.0 / 3.0) * (w * d0);
-        gg += gwi * w;
         T *= 1.0 - alpha;  // transmittance after this sample
+        double plain = gi0 * (T * cr - (rf - r)) + gi1 * (T * cg - (gf - g)) + gi2 * (T * cb - (bf - b)) + gw * (1.0 - wsf);
+        if constexpr (GEO) {
+            t += deltas[o * 2 + 1];
+            const double before = t * ws - d;  // t_i W_<i - D_<i
+            ws += w;
+            d += w * t;
+            const double gwi = 2.0 * before + 2.0 * ((df - d) - t * (wsf - ws)) + (2.0 / 3.0) * (w * d0);
+            gg += gwi * w;
+            plain = plain + gd * (T * t - (df - d)) + gl * (gwi * T - (gtot - gg));
+        }
         grad_rgbs[o * 3] = gi0 * w;
         grad_rgbs[o * 3 + 1] = gi1 * w;
         grad_rgbs[o * 3 + 2] = gi2 * w;
-        grad_sigmas[o] = d0 * (gi0 * (T * cr - (rf - r)) + gi1 * (T * cg - (gf - g)) + gi2 * (T * cb - (bf - b)) + gw * (1.0 - wsf) +
-                               gd * (T * t - (df - d)) + gl * (gwi * T - (gtot - gg)));
+        grad_sigmas[o] = d0 * plain;
         if (T < th) break;
     }
 }
@@ -899,7 +848,8 @@ extern "C" int ngp_composite_rays_train_forward_f64(const double* sigmas, const 
                                                     ngp_stream_t stream) {
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image, NGP_ERR_INVALID, "composite_rays_train_forward_f64: NULL tensor");
-    F64_LAUNCH_1D(k_f64_composite_train_fwd, N, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image);
+    F64_LAUNCH_1D(k_f64_composite_train_fwd<false>, N, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image,
+                  (double*)nullptr);
     return check_launch("composite_rays_train_forward_f64");
 }
 
@@ -910,8 +860,9 @@ extern "C" int ngp_composite_rays_train_backward_f64(const double* grad_weights_
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(grad_weights_sum && grad_image && sigmas && rgbs && deltas && rays && weights_sum && image && grad_sigmas && grad_rgbs, NGP_ERR_INVALID,
                 "composite_rays_train_backward_f64: NULL tensor");
-    F64_LAUNCH_1D(k_f64_composite_train_bwd, N, as_stream(stream), grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
-                  T_thresh, grad_sigmas, grad_rgbs);
+    const double* none = nullptr;  // the geometry arguments of the shared kernel
+    F64_LAUNCH_1D(k_f64_composite_train_bwd<false>, N, as_stream(stream), grad_weights_sum, none, grad_image, none, sigmas, rgbs, deltas, rays,
+                  weights_sum, none, image, none, M, N, T_thresh, grad_sigmas, grad_rgbs);
     return check_launch("composite_rays_train_backward_f64");
 }
 
@@ -921,7 +872,7 @@ extern "C" int ngp_composite_rays_train_geo_forward_f64(const double* sigmas, co
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && distortion, NGP_ERR_INVALID,
                 "composite_rays_train_geo_forward_f64: NULL tensor");
-    F64_LAUNCH_1D(k_f64_composite_train_geo_fwd, N, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image,
+    F64_LAUNCH_1D(k_f64_composite_train_fwd<true>, N, as_stream(stream), sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image,
                   distortion);
     return check_launch("composite_rays_train_geo_forward_f64");
 }
@@ -934,7 +885,7 @@ extern "C" int ngp_composite_rays_train_geo_backward_f64(const double* grad_weig
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && distortion && grad_sigmas && grad_rgbs, NGP_ERR_INVALID,
                 "composite_rays_train_geo_backward_f64: NULL tensor");
-    F64_LAUNCH_1D(k_f64_composite_train_geo_bwd, N, as_stream(stream), grad_weights_sum, grad_depth, grad_image, grad_distortion, sigmas, rgbs,
+    F64_LAUNCH_1D(k_f64_composite_train_bwd<true>, N, as_stream(stream), grad_weights_sum, grad_depth, grad_image, grad_distortion, sigmas, rgbs,
                   deltas, rays, weights_sum, depth, image, distortion, M, N, T_thresh, grad_sigmas, grad_rgbs);
     return check_launch("composite_rays_train_geo_backward_f64");
 }

@@ -886,6 +886,210 @@ struct Finish {
     float* depth_out;
 };
 
+// ---------------------------------------------------------------------------------------------
+// The two row sweeps of the training compositor.  ONE statement of the compositing rule (alpha, the transmittance product, the `live`
+// test, the early stop) for the six kernels below: the stand-alone forward / backward (k_composite_train_fwd / _bwd), their geometry
+// forms (GEO: differentiable depth and the mip-NeRF-360 distortion, raymarching.cu:501-577, 602-682 + loss.py::EffDistLoss, DESIGN.md
+// 3.9) and the two one-launch training steps (k_composite_train_loss_bwd / _geo_loss_bwd).  What GEO adds sits under
+// `if constexpr`: a plain instantiation holds none of it, and a geometry instantiation computes weights_sum / depth / image with the
+// plain one's expressions in the plain one's order -- the same bits (tests/test_gpu_composite_geo.py, tests/test_gpu_fused_geo_loss.py).
+// ---------------------------------------------------------------------------------------------
+// The distortion  L = sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 d0_i  in the same wave-per-ray scan:
+// t is non-decreasing, so L = sum_i 2 w_i A_i + 1/3 sum_i w_i^2 d0_i with A_i = sum_{j<i} w_j (t_i - t_j) = t_i W_<i - D_<i (W_<i, D_<i: the
+// exclusive prefixes of w and w t).  A_i is scanned in the form that has no cancellation, A_i = sum_{k<=i} W_<k d1_k (each step of t
+// moves every weight in front of it): a sum of non-negative terms, where t_i W_<i - D_<i loses t_i / (t_i - t_j) in relative accuracy on
+// a long ray.
+// The distortion does not take its weights from the transmittance product.  alpha = 1 - __expf(-x) at a small optical depth x = sigma d0
+// carries the exponential's absolute error into a number 1 / x times smaller, and T = prod (1 - alpha_j) multiplies one rounded
+// exponential per sample: on a 300-sample ray weights_sum ends 4.5 ulp from its float64 value (measured), and L, of degree two in the
+// weights, 6 ulp.  weights_sum, depth and image keep those weights, but L is summed over weights from the log domain:
+// T'_i = exp(-X_<i) with X the scanned optical depth (ONE exponential per sample instead of a product of i), alpha'_i = -expm1(-x_i)
+// (series below 1/4), w'_i = alpha'_i T'_i, W'_<k = 1 - T'_k (the weights telescope; the backward sweep uses the same identity for its
+// weights_sum term).  The live set is the shared one (T_thresh is compared against the product).  Two scans more than the plain sweep (X, A).
+// 1 - exp(-x) = x - x^2/2 + x^3/6 - ... : the eighth term is below 2^-29 of the sum for |x| < 1/4
+__device__ __forceinline__ float one_minus_exp_neg(float x, float e) {  // e = exp(-x), used where the subtraction is harmless
+    float p = __builtin_fmaf(x, 1.0f / 5040.0f, -1.0f / 720.0f);
+    p = __builtin_fmaf(x, p, 1.0f / 120.0f);
+    p = __builtin_fmaf(x, p, -1.0f / 24.0f);
+    p = __builtin_fmaf(x, p, 1.0f / 6.0f);
+    p = __builtin_fmaf(x, p, -0.5f);
+    p = __builtin_fmaf(x, p, 1.0f);
+    return fabsf(x) < 0.25f ? x * p : 1.0f - e;
+}
+
+struct RayTotals { float r, g, b, ws, d, dist; };  // image, weights_sum, depth, distortion (GEO only) of one ray, wave-uniform
+
+// forward sweep over the rows [offset, offset + num) of one ray (num != 0, the rows fit), one wavefront, 64 samples per turn
+template <bool GEO>
+__device__ __forceinline__ RayTotals composite_forward_sweep(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                             const float* __restrict__ deltas, uint32_t offset, uint32_t num, float T_thresh,
+                                                             int lane) {
+    float r = 0, g = 0, b = 0, ws = 0, d = 0, dist = 0;
+    float T = 1.0f, tcarry = 0.0f, xcarry = 0.0f, acarry = 0.0f;  // transmittance / accumulated real-delta / optical depth / A before this row
+    for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        const bool valid = s < num;
+        float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+        if (valid) {
+            sg = sigmas[offset + s];
+            const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
+            d0 = dl.x; d1 = dl.y;
+            cr = rgbs[(size_t)(offset + s) * 3];
+            cg = rgbs[(size_t)(offset + s) * 3 + 1];
+            cb = rgbs[(size_t)(offset + s) * 3 + 2];
+        }
+        const float e = __expf(-sg * d0);
+        const float alpha = valid ? 1.0f - e : 0.0f;
+        const float om = 1.0f - alpha;
+        const float pin = wave_incl_prod(om, lane);          // prod_{j<=lane} (1-alpha_j)
+        const float T_before = T * prev_lane(1.0f, pin);     // transmittance in front of this sample
+        const float tt = tcarry + wave_incl_sum(d1, lane);   // t after this sample
+        // the sample that drives T below the threshold is still composited (raymarching.cu:557-560)
+        const bool live = valid && !(T_before < T_thresh);
+        const float w = live ? alpha * T_before : 0.0f;
+        r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
+        if constexpr (GEO) {  // the distortion's own weights (invalid lanes: sg = d0 = d1 = 0)
+            const float x = sg * d0;
+            const float xa = xcarry + wave_incl_sum(x, lane);         // X_<=i
+            const float Tq = __expf(-prev_lane(xcarry, xa));          // T'_i = exp(-X_<i)
+            const float wq = live ? one_minus_exp_neg(x, e) * Tq : 0.0f;
+            const float a = acarry + wave_incl_sum((1.0f - Tq) * d1, lane);  // A_i (lanes behind the stop: w' = 0)
+            dist += 2.0f * wq * a + (1.0f / 3.0f) * (wq * wq * d0);
+            xcarry = lane63(xa);
+            acarry = lane63(a);
+        }
+        T = T * lane63(pin);
+        tcarry = lane63(tt);
+        if (T < T_thresh) break;  // wave-uniform
+    }
+    r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d);
+    if constexpr (GEO) dist = wave_total(dist);
+    return RayTotals{r, g, b, ws, d, dist};
+}
+
+struct RayGrads { float gi0, gi1, gi2, gw, gd, gl; };  // upstream gradients of image, weights_sum and (GEO only) depth, distortion of one ray
+
+// Where the backward sweep leaves a row.  write: a live sample (w: its weight, c*: its colour, gs: its finished grad_sigmas); zero: a row
+// the compositing does not reach -- behind a ray's early stop, or owned by no ray (zero_unowned_rows) -- when the outputs arrive
+// uninitialised (zero_fill; otherwise the caller pre-zeroes and only live rows are written).
+struct RgbSink {  // grad_rgbs [M,3] fp32
+    float* __restrict__ grad_sigmas;
+    float* __restrict__ grad_rgbs;
+    bool zero_fill;
+    __device__ __forceinline__ void write(uint32_t o, const RayGrads& u, float w, float, float, float, float gs) const {
+        grad_rgbs[(size_t)o * 3] = u.gi0 * w;
+        grad_rgbs[(size_t)o * 3 + 1] = u.gi1 * w;
+        grad_rgbs[(size_t)o * 3 + 2] = u.gi2 * w;
+        grad_sigmas[o] = gs;
+    }
+    __device__ __forceinline__ void zero(uint32_t o) const {
+        grad_rgbs[(size_t)o * 3] = 0.0f; grad_rgbs[(size_t)o * 3 + 1] = 0.0f; grad_rgbs[(size_t)o * 3 + 2] = 0.0f;
+        grad_sigmas[o] = 0.0f;
+    }
+};
+struct SigmoidHalfSink {  // the colour head's sigmoid backward (k_rgb_backward) into the 16-half row of grad_out16; every row is written
+    float* __restrict__ grad_sigmas;
+    half_t* __restrict__ grad_out16;
+    static constexpr bool zero_fill = true;
+    __device__ __forceinline__ void write(uint32_t o, const RayGrads& u, float w, float cr, float cg, float cb, float gs) const {
+        half8_t lo, hi;
+#pragma unroll
+        for (int i = 0; i < 8; i++) { lo[i] = (half_t)0.0f; hi[i] = (half_t)0.0f; }
+        lo[0] = to_half_rne((u.gi0 * w) * (cr * (1.0f - cr)));
+        lo[1] = to_half_rne((u.gi1 * w) * (cg * (1.0f - cg)));
+        lo[2] = to_half_rne((u.gi2 * w) * (cb * (1.0f - cb)));
+        half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
+        dst[0] = lo; dst[1] = hi;
+        grad_sigmas[o] = gs;
+    }
+    __device__ __forceinline__ void zero(uint32_t o) const {
+        half8_t z;
+#pragma unroll
+        for (int i = 0; i < 8; i++) z[i] = (half_t)0.0f;
+        half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
+        dst[0] = z; dst[1] = z;
+        grad_sigmas[o] = 0.0f;
+    }
+};
+
+// Backward sweep over the same rows; f: the forward totals (saved outputs, or the registers of the forward sweep in front of it).
+// GEO: the backward of all four outputs in ONE sweep.  With g_i = dL/dw_i = 2 (t_i W_<i - D_<i) + 2 ((D - D_<=i) - t_i (W - W_<=i)) + 2/3 w_i d0_i:
+//   dD/dsigma_i = d0_i (T_{i+1} t_i - (D - D_<=i))                 (the colour term with t as the colour)
+//   dL/dsigma_i = d0_i (g_i T_{i+1} - (G - G_<=i)),  G = sum_j g_j w_j = 2 L   (L is homogeneous of degree 2 in w)
+// so every ray total is a saved forward output and nothing is swept twice.  Three scans more than the plain sweep (t, D, G); the two new
+// terms are added to the finished plain sum: with zero gd / gl the plain sweep's bits.
+template <bool GEO, class Sink>
+__device__ __forceinline__ void composite_backward_sweep(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                                         const float* __restrict__ deltas, uint32_t offset, uint32_t num, float T_thresh, int lane,
+                                                         const RayTotals& f, const RayGrads& u, const Sink& sink) {
+    const float gtot = 2.0f * f.dist;
+    float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f, tcarry = 0.0f, dcarry = 0.0f, gcarry = 0.0f;  // carries from previous rows
+    for (uint32_t s0 = 0; s0 < num; s0 += 64) {
+        const uint32_t s = s0 + lane;
+        const bool valid = s < num;
+        float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+        if (valid) {
+            sg = sigmas[offset + s];
+            if constexpr (GEO) {
+                const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
+                d0 = dl.x; d1 = dl.y;
+            } else {
+                d0 = deltas[(size_t)(offset + s) * 2];
+            }
+            cr = rgbs[(size_t)(offset + s) * 3];
+            cg = rgbs[(size_t)(offset + s) * 3 + 1];
+            cb = rgbs[(size_t)(offset + s) * 3 + 2];
+        }
+        const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
+        const float pin = wave_incl_prod(1.0f - alpha, lane);
+        const float T_before = T * prev_lane(1.0f, pin);
+        const float T_after = T * pin;
+        float tt = 0.0f;
+        if constexpr (GEO) tt = tcarry + wave_incl_sum(d1, lane);
+        const bool live = valid && !(T_before < T_thresh);
+        const float w = live ? alpha * T_before : 0.0f;
+        const float ra = rc + wave_incl_sum(w * cr, lane);
+        const float ga = gc + wave_incl_sum(w * cg, lane);
+        const float ba = bc + wave_incl_sum(w * cb, lane);
+        float da = 0.0f, d_rest = 0.0f, gwi = 0.0f, gga = 0.0f;
+        if constexpr (GEO) {
+            da = dcarry + wave_incl_sum(w * tt, lane);               // D_<=i
+            const float d_before = prev_lane(dcarry, da);            // D_<i
+            d_rest = f.d - da;                                       // D - D_<=i
+            const float w_rest = f.ws - (1.0f - T_after);            // W - W_<=i
+            gwi = 2.0f * (tt * (1.0f - T_before) - d_before) + 2.0f * (d_rest - tt * w_rest) + (2.0f / 3.0f) * (w * d0);
+            gga = gcarry + wave_incl_sum(gwi * w, lane);             // G_<=i
+        }
+        if (live) {
+            const float plain = u.gi0 * (T_after * cr - (f.r - ra)) + u.gi1 * (T_after * cg - (f.g - ga)) + u.gi2 * (T_after * cb - (f.b - ba)) +
+                                u.gw * (1.0f - f.ws);
+            if constexpr (GEO)
+                sink.write(offset + s, u, w, cr, cg, cb, d0 * (plain + u.gd * (T_after * tt - d_rest) + u.gl * (gwi * T_after - (gtot - gga))));
+            else
+                sink.write(offset + s, u, w, cr, cg, cb, d0 * plain);
+        } else if (sink.zero_fill && valid) {
+            sink.zero(offset + s);
+        }
+        T = T * lane63(pin);
+        if constexpr (GEO) tcarry = lane63(tt);
+        rc = lane63(ra); gc = lane63(ga); bc = lane63(ba);
+        if constexpr (GEO) { dcarry = lane63(da); gcarry = lane63(gga); }
+        if (T < T_thresh) {
+            if (sink.zero_fill)
+                for (uint32_t z = s0 + 64 + lane; z < num; z += 64) sink.zero(offset + z);
+            break;
+        }
+    }
+}
+
+// the workgroups behind the ray ones (blockIdx.x >= ray_blocks) zero the rows >= *rows_used that no ray owns
+template <class Sink>
+__device__ __forceinline__ void zero_unowned_rows(const Sink& sink, const uint32_t* __restrict__ rows_used, uint32_t M, uint32_t ray_blocks) {
+    const uint32_t first = min(rows_used[0], M);
+    const uint32_t stride = (gridDim.x - ray_blocks) * CT_WAVES * 64;
+    for (uint32_t o = first + (blockIdx.x - ray_blocks) * CT_WAVES * 64 + threadIdx.x; o < M; o += stride) sink.zero(o);
+}
+
 __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                        const float* __restrict__ deltas, const int32_t* __restrict__ rays,
                                                                        uint32_t M, uint32_t N, float T_thresh,
@@ -895,50 +1099,22 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_fwd(const flo
     const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
-    float r = 0, g = 0, b = 0, ws = 0, d = 0;
-    if (num != 0 && offset + num <= M) {
-        float T = 1.0f, tcarry = 0.0f;  // transmittance / accumulated real-delta before this row
-        for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-            const uint32_t s = s0 + lane;
-            const bool valid = s < num;
-            float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-            if (valid) {
-                sg = sigmas[offset + s];
-                const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
-                d0 = dl.x; d1 = dl.y;
-                cr = rgbs[(size_t)(offset + s) * 3];
-                cg = rgbs[(size_t)(offset + s) * 3 + 1];
-                cb = rgbs[(size_t)(offset + s) * 3 + 2];
-            }
-            const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
-            const float om = 1.0f - alpha;
-            const float pin = wave_incl_prod(om, lane);          // prod_{j<=lane} (1-alpha_j)
-                        const float T_before = T * prev_lane(1.0f, pin);  // transmittance in front of this sample
-            const float tt = tcarry + wave_incl_sum(d1, lane);    // t after this sample
-            // the sample that drives T below the threshold is still composited (raymarching.cu:557-560)
-            const bool live = valid && !(T_before < T_thresh);
-            const float w = live ? alpha * T_before : 0.0f;
-            r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
-            T = T * lane63(pin);
-            tcarry = lane63(tt);
-            if (T < T_thresh) break;  // wave-uniform
-        }
-        r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d);
-    }
+    RayTotals f{};
+    if (num != 0 && offset + num <= M) f = composite_forward_sweep<false>(sigmas, rgbs, deltas, offset, num, T_thresh, lane);
     if (lane == 0) {
-        weights_sum[index] = ws;
-        depth[index] = d;
-        image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+        weights_sum[index] = f.ws;
+        depth[index] = f.d;
+        image[index * 3] = f.r; image[index * 3 + 1] = f.g; image[index * 3 + 2] = f.b;
         if (fin.mode != 0) {
             // NeRFRenderer.run_cuda's epilogue (renderer.py:316-318): image + (1 - weights_sum) * bg ; clamp(depth - near, 0) / (far - near)
-            const float t1 = 1.0f - ws;
+            const float t1 = 1.0f - f.ws;
             const float b0 = fin.mode == 2 ? fin.bg[index * 3] : fin.bg_scalar, b1 = fin.mode == 2 ? fin.bg[index * 3 + 1] : fin.bg_scalar,
                         b2 = fin.mode == 2 ? fin.bg[index * 3 + 2] : fin.bg_scalar;
-            fin.image_out[index * 3] = r + t1 * b0;
-            fin.image_out[index * 3 + 1] = g + t1 * b1;
-            fin.image_out[index * 3 + 2] = b + t1 * b2;
+            fin.image_out[index * 3] = f.r + t1 * b0;
+            fin.image_out[index * 3 + 1] = f.g + t1 * b1;
+            fin.image_out[index * 3 + 2] = f.b + t1 * b2;
             const float nr = fin.nears[index], fr = fin.fars[index];
-            fin.depth_out[index] = fmaxf(d - nr, 0.0f) / (fr - nr);
+            fin.depth_out[index] = fmaxf(f.d - nr, 0.0f) / (fr - nr);
         }
     }
 }
@@ -952,17 +1128,9 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_bwd(const flo
                                                                        const uint32_t* __restrict__ rows_used, uint32_t ray_blocks) {
     const int lane = threadIdx.x & 63;
     // rows_used != NULL: the outputs arrive UNINITIALISED and every row the compositing does not reach is zeroed here -- the rows of
-    // a ray behind its early termination (below) and the rows >= *rows_used that no ray owns (the workgroups after the ray ones)
-    if (blockIdx.x >= ray_blocks) {
-        const uint32_t first = min(rows_used[0], M);
-        const uint32_t stride = (gridDim.x - ray_blocks) * CT_WAVES * 64;
-        for (uint32_t o = first + (blockIdx.x - ray_blocks) * CT_WAVES * 64 + threadIdx.x; o < M; o += stride) {
-            grad_sigmas[o] = 0.0f;
-            grad_rgbs[(size_t)o * 3] = 0.0f; grad_rgbs[(size_t)o * 3 + 1] = 0.0f; grad_rgbs[(size_t)o * 3 + 2] = 0.0f;
-        }
-        return;
-    }
-    const bool zero_fill = rows_used != nullptr;
+    // a ray behind its early termination and the rows >= *rows_used that no ray owns (the workgroups after the ray ones)
+    const RgbSink sink{grad_sigmas, grad_rgbs, rows_used != nullptr};
+    if (blockIdx.x >= ray_blocks) return zero_unowned_rows(sink, rows_used, M, ray_blocks);
     const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
@@ -974,80 +1142,10 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_bwd(const flo
                     b2 = fin.mode == 2 ? fin.bg[index * 3 + 2] : fin.bg_scalar;
         gw -= gi0 * b0 + gi1 * b1 + gi2 * b2;
     }
-    const float rf = image[index * 3], gf = image[index * 3 + 1], bf = image[index * 3 + 2], wsf = weights_sum[index];
-    float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f;  // carries from previous rows
-    for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-        const uint32_t s = s0 + lane;
-        const bool valid = s < num;
-        float sg = 0.0f, d0 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-        if (valid) {
-            sg = sigmas[offset + s];
-            d0 = deltas[(size_t)(offset + s) * 2];
-            cr = rgbs[(size_t)(offset + s) * 3];
-            cg = rgbs[(size_t)(offset + s) * 3 + 1];
-            cb = rgbs[(size_t)(offset + s) * 3 + 2];
-        }
-        const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
-        const float pin = wave_incl_prod(1.0f - alpha, lane);
-                const float T_before = T * prev_lane(1.0f, pin);
-        const float T_after = T * pin;
-        const bool live = valid && !(T_before < T_thresh);
-        const float w = live ? alpha * T_before : 0.0f;
-        const float ra = rc + wave_incl_sum(w * cr, lane);
-        const float ga = gc + wave_incl_sum(w * cg, lane);
-        const float ba = bc + wave_incl_sum(w * cb, lane);
-        if (live) {
-            const uint32_t o = offset + s;
-            grad_rgbs[(size_t)o * 3] = gi0 * w;
-            grad_rgbs[(size_t)o * 3 + 1] = gi1 * w;
-            grad_rgbs[(size_t)o * 3 + 2] = gi2 * w;
-            grad_sigmas[o] = d0 * (gi0 * (T_after * cr - (rf - ra)) + gi1 * (T_after * cg - (gf - ga)) +
-                                   gi2 * (T_after * cb - (bf - ba)) + gw * (1.0f - wsf));
-        } else if (zero_fill && valid) {
-            const uint32_t o = offset + s;
-            grad_rgbs[(size_t)o * 3] = 0.0f; grad_rgbs[(size_t)o * 3 + 1] = 0.0f; grad_rgbs[(size_t)o * 3 + 2] = 0.0f;
-            grad_sigmas[o] = 0.0f;
-        }
-        T = T * lane63(pin);
-        rc = lane63(ra); gc = lane63(ga); bc = lane63(ba);
-        if (T < T_thresh) {
-            if (zero_fill)
-                for (uint32_t z = s0 + 64 + lane; z < num; z += 64) {
-                    const uint32_t o = offset + z;
-                    grad_rgbs[(size_t)o * 3] = 0.0f; grad_rgbs[(size_t)o * 3 + 1] = 0.0f; grad_rgbs[(size_t)o * 3 + 2] = 0.0f;
-                    grad_sigmas[o] = 0.0f;
-                }
-            break;
-        }
-    }
+    const RayTotals f{image[index * 3], image[index * 3 + 1], image[index * 3 + 2], weights_sum[index], 0.0f, 0.0f};
+    composite_backward_sweep<false>(sigmas, rgbs, deltas, offset, num, T_thresh, lane, f, RayGrads{gi0, gi1, gi2, gw, 0.0f, 0.0f}, sink);
 }
 
-// ---------------------------------------------------------------------------------------------
-// compositing for geometry losses (extension: raymarching.cu:501-577, 602-682 + loss.py::EffDistLoss): differentiable depth and the
-// mip-NeRF-360 distortion  L = sum_ij w_i w_j |t_i - t_j| + 1/3 sum_i w_i^2 d0_i  in the same wave-per-ray scan
-// ---------------------------------------------------------------------------------------------
-// t is non-decreasing, so L = sum_i 2 w_i A_i + 1/3 sum_i w_i^2 d0_i with A_i = sum_{j<i} w_j (t_i - t_j) = t_i W_<i - D_<i (W_<i, D_<i: the
-// exclusive prefixes of w and w t).  A_i is scanned in the form that has no cancellation, A_i = sum_{k<=i} W_<k d1_k (each step of t
-// moves every weight in front of it): a sum of non-negative terms, where t_i W_<i - D_<i loses t_i / (t_i - t_j) in relative accuracy on
-// a long ray.
-// The distortion does not take its weights from the transmittance product.  alpha = 1 - __expf(-x) at a small optical depth x = sigma d0
-// carries the exponential's absolute error into a number 1 / x times smaller, and T = prod (1 - alpha_j) multiplies one rounded
-// exponential per sample: on a 300-sample ray weights_sum ends 4.5 ulp from its float64 value (measured), and L, of degree two in the
-// weights, 6 ulp.  weights_sum, depth and image keep those weights -- their expressions are k_composite_train_fwd's term for term, the
-// same bits -- but L is summed over weights from the log domain: T'_i = exp(-X_<i) with X the scanned optical depth (ONE exponential
-// per sample instead of a product of i), alpha'_i = -expm1(-x_i) (series below 1/4), w'_i = alpha'_i T'_i, W'_<k = 1 - T'_k (the weights
-// telescope; k_composite_train_bwd uses the same identity for its weights_sum term).  The live set is the shared one (T_thresh is
-// compared against the product).  Two scans more than k_composite_train_fwd (X, A).
-// 1 - exp(-x) = x - x^2/2 + x^3/6 - ... : the eighth term is below 2^-29 of the sum for |x| < 1/4
-__device__ __forceinline__ float one_minus_exp_neg(float x, float e) {  // e = exp(-x), used where the subtraction is harmless
-    float p = __builtin_fmaf(x, 1.0f / 5040.0f, -1.0f / 720.0f);
-    p = __builtin_fmaf(x, p, 1.0f / 120.0f);
-    p = __builtin_fmaf(x, p, -1.0f / 24.0f);
-    p = __builtin_fmaf(x, p, 1.0f / 6.0f);
-    p = __builtin_fmaf(x, p, -0.5f);
-    p = __builtin_fmaf(x, p, 1.0f);
-    return fabsf(x) < 0.25f ? x * p : 1.0f - e;
-}
 __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                            const float* __restrict__ deltas, const int32_t* __restrict__ rays,
                                                                            uint32_t M, uint32_t N, float T_thresh,
@@ -1057,58 +1155,16 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_fwd(const
     const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
-    float r = 0, g = 0, b = 0, ws = 0, d = 0, dist = 0;
-    if (num != 0 && offset + num <= M) {
-        float T = 1.0f, tcarry = 0.0f, xcarry = 0.0f, acarry = 0.0f;  // transmittance / accumulated real-delta / optical depth / A before this row
-        for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-            const uint32_t s = s0 + lane;
-            const bool valid = s < num;
-            float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-            if (valid) {
-                sg = sigmas[offset + s];
-                const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
-                d0 = dl.x; d1 = dl.y;
-                cr = rgbs[(size_t)(offset + s) * 3];
-                cg = rgbs[(size_t)(offset + s) * 3 + 1];
-                cb = rgbs[(size_t)(offset + s) * 3 + 2];
-            }
-            const float e = __expf(-sg * d0);
-            const float alpha = valid ? 1.0f - e : 0.0f;
-            const float om = 1.0f - alpha;
-            const float pin = wave_incl_prod(om, lane);
-            const float T_before = T * prev_lane(1.0f, pin);
-            const float tt = tcarry + wave_incl_sum(d1, lane);
-            const bool live = valid && !(T_before < T_thresh);
-            const float w = live ? alpha * T_before : 0.0f;
-            r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
-            // the distortion's own weights (invalid lanes: sg = d0 = d1 = 0)
-            const float x = sg * d0;
-            const float xa = xcarry + wave_incl_sum(x, lane);         // X_<=i
-            const float Tq = __expf(-prev_lane(xcarry, xa));          // T'_i = exp(-X_<i)
-            const float wq = live ? one_minus_exp_neg(x, e) * Tq : 0.0f;
-            const float a = acarry + wave_incl_sum((1.0f - Tq) * d1, lane);  // A_i (lanes behind the stop: w' = 0)
-            dist += 2.0f * wq * a + (1.0f / 3.0f) * (wq * wq * d0);
-            T = T * lane63(pin);
-            tcarry = lane63(tt);
-            xcarry = lane63(xa);
-            acarry = lane63(a);
-            if (T < T_thresh) break;  // wave-uniform
-        }
-        r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d); dist = wave_total(dist);
-    }
+    RayTotals f{};
+    if (num != 0 && offset + num <= M) f = composite_forward_sweep<true>(sigmas, rgbs, deltas, offset, num, T_thresh, lane);
     if (lane == 0) {
-        weights_sum[index] = ws;
-        depth[index] = d;
-        image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
-        distortion[index] = dist;
+        weights_sum[index] = f.ws;
+        depth[index] = f.d;
+        image[index * 3] = f.r; image[index * 3 + 1] = f.g; image[index * 3 + 2] = f.b;
+        distortion[index] = f.dist;
     }
 }
 
-// Backward of the four outputs in ONE sweep.  With g_i = dL/dw_i = 2 (t_i W_<i - D_<i) + 2 ((D - D_<=i) - t_i (W - W_<=i)) + 2/3 w_i d0_i:
-//   dD/dsigma_i = d0_i (T_{i+1} t_i - (D - D_<=i))                 (the colour term of k_composite_train_bwd with t as the colour)
-//   dL/dsigma_i = d0_i (g_i T_{i+1} - (G - G_<=i)),  G = sum_j g_j w_j = 2 L   (L is homogeneous of degree 2 in w)
-// so every ray total is a saved forward output and nothing is swept twice.  Three scans more than k_composite_train_bwd (t, D, G); its
-// grad_sigmas sum is kept term for term and the two new terms are added to it: with zero grad_depth / grad_distortion the same bits.
 // A NULL gradient pointer is a zero gradient.  Writes live rows only (the caller pre-zeroes, as for ngp_composite_rays_train_backward).
 __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_bwd(const float* __restrict__ grad_ws, const float* __restrict__ grad_depth,
                                                                            const float* __restrict__ grad_image, const float* __restrict__ grad_dist,
@@ -1126,183 +1182,16 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_bwd(const
     const float gi0 = grad_image ? grad_image[index * 3] : 0.0f, gi1 = grad_image ? grad_image[index * 3 + 1] : 0.0f,
                 gi2 = grad_image ? grad_image[index * 3 + 2] : 0.0f;
     const float gw = grad_ws ? grad_ws[index] : 0.0f, gd = grad_depth ? grad_depth[index] : 0.0f, gl = grad_dist ? grad_dist[index] : 0.0f;
-    const float rf = image[index * 3], gf = image[index * 3 + 1], bf = image[index * 3 + 2], wsf = weights_sum[index];
-    const float df = depth[index], gtot = 2.0f * distortion[index];
-    float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f, tcarry = 0.0f, dcarry = 0.0f, gcarry = 0.0f;  // carries from previous rows
-    for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-        const uint32_t s = s0 + lane;
-        const bool valid = s < num;
-        float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-        if (valid) {
-            sg = sigmas[offset + s];
-            const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
-            d0 = dl.x; d1 = dl.y;
-            cr = rgbs[(size_t)(offset + s) * 3];
-            cg = rgbs[(size_t)(offset + s) * 3 + 1];
-            cb = rgbs[(size_t)(offset + s) * 3 + 2];
-        }
-        const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
-        const float pin = wave_incl_prod(1.0f - alpha, lane);
-        const float T_before = T * prev_lane(1.0f, pin);
-        const float T_after = T * pin;
-        const float tt = tcarry + wave_incl_sum(d1, lane);
-        const bool live = valid && !(T_before < T_thresh);
-        const float w = live ? alpha * T_before : 0.0f;
-        const float ra = rc + wave_incl_sum(w * cr, lane);
-        const float ga = gc + wave_incl_sum(w * cg, lane);
-        const float ba = bc + wave_incl_sum(w * cb, lane);
-        const float da = dcarry + wave_incl_sum(w * tt, lane);  // D_<=i
-        const float d_before = prev_lane(dcarry, da);           // D_<i
-        const float d_rest = df - da;                            // D - D_<=i
-        const float w_rest = wsf - (1.0f - T_after);             // W - W_<=i
-        const float gwi = 2.0f * (tt * (1.0f - T_before) - d_before) + 2.0f * (d_rest - tt * w_rest) + (2.0f / 3.0f) * (w * d0);
-        const float gga = gcarry + wave_incl_sum(gwi * w, lane);  // G_<=i
-        if (live) {
-            const uint32_t o = offset + s;
-            grad_rgbs[(size_t)o * 3] = gi0 * w;
-            grad_rgbs[(size_t)o * 3 + 1] = gi1 * w;
-            grad_rgbs[(size_t)o * 3 + 2] = gi2 * w;
-            const float plain = gi0 * (T_after * cr - (rf - ra)) + gi1 * (T_after * cg - (gf - ga)) + gi2 * (T_after * cb - (bf - ba)) +
-                                gw * (1.0f - wsf);
-            grad_sigmas[o] = d0 * (plain + gd * (T_after * tt - d_rest) + gl * (gwi * T_after - (gtot - gga)));
-        }
-        T = T * lane63(pin);
-        tcarry = lane63(tt);
-        rc = lane63(ra); gc = lane63(ga); bc = lane63(ba); dcarry = lane63(da); gcarry = lane63(gga);
-        if (T < T_thresh) break;
-    }
+    const RayTotals f{image[index * 3], image[index * 3 + 1], image[index * 3 + 2], weights_sum[index], depth[index], distortion[index]};
+    composite_backward_sweep<true>(sigmas, rgbs, deltas, offset, num, T_thresh, lane, f, RayGrads{gi0, gi1, gi2, gw, gd, gl},
+                                   RgbSink{grad_sigmas, grad_rgbs, false});
 }
 
-// The image-space middle of a training iteration in ONE launch, one wavefront per ray:
-//   k_composite_train_fwd (+ finish)  ->  the Trainer's MSE loss and its scaled gradient (k_mse_loss)  ->  k_composite_train_bwd  ->
-//   the colour head's sigmoid backward (k_rgb_backward),
-// with the arithmetic of those four kernels expression for expression, so the gradients are the same bits.  What a ray needs from the
-// loss is its own three pixels, so nothing crosses rays except the loss VALUE (a logged scalar): every ray deposits its squared error,
-// the last workgroup to finish (a ticket) adds them up in a fixed order -> deterministic.  Four launches, their tails and the
-// [N,3] / [M,3] fp32 intermediates (grad_image, grad_rgbs) are gone; the second sweep re-reads sigma / rgb / delta from L2.
-// ticket[0] and the group tickets must be 0 on entry (the marcher clears them every step); the kernel leaves them 0.
-__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_loss_bwd(
-    const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas, const int32_t* __restrict__ rays,
-    uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum, Finish fin, const float* __restrict__ target,
-    const float* __restrict__ loss_scale, float* __restrict__ ray_err, uint32_t* __restrict__ ticket, float* __restrict__ loss,
-    float* __restrict__ grad_sigmas, half_t* __restrict__ grad_out16, const uint32_t* __restrict__ rows_used, uint32_t ray_blocks,
-    uint32_t* __restrict__ group_tickets) {
-    const int lane = threadIdx.x & 63;
-    auto zero_row = [&](uint32_t o) {
-        half8_t z;
-#pragma unroll
-        for (int i = 0; i < 8; i++) z[i] = (half_t)0.0f;
-        half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
-        dst[0] = z; dst[1] = z;
-        grad_sigmas[o] = 0.0f;
-    };
-    if (blockIdx.x >= ray_blocks) {  // rows >= *rows_used that no ray owns
-        const uint32_t first = min(rows_used[0], M);
-        const uint32_t stride = (gridDim.x - ray_blocks) * CT_WAVES * 64;
-        for (uint32_t o = first + (blockIdx.x - ray_blocks) * CT_WAVES * 64 + threadIdx.x; o < M; o += stride) zero_row(o);
-        return;
-    }
-    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
-    if (n < N) {
-        const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
-        const bool has_rows = num != 0 && offset + num <= M;
-        // ---- forward sweep (k_composite_train_fwd) ----
-        float r = 0, g = 0, b = 0, ws = 0, d = 0;
-        if (has_rows) {
-            float T = 1.0f, tcarry = 0.0f;
-            for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-                const uint32_t s = s0 + lane;
-                const bool valid = s < num;
-                float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-                if (valid) {
-                    sg = sigmas[offset + s];
-                    const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
-                    d0 = dl.x; d1 = dl.y;
-                    cr = rgbs[(size_t)(offset + s) * 3];
-                    cg = rgbs[(size_t)(offset + s) * 3 + 1];
-                    cb = rgbs[(size_t)(offset + s) * 3 + 2];
-                }
-                const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
-                const float om = 1.0f - alpha;
-                const float pin = wave_incl_prod(om, lane);
-                                const float T_before = T * prev_lane(1.0f, pin);
-                const float tt = tcarry + wave_incl_sum(d1, lane);
-                const bool live = valid && !(T_before < T_thresh);
-                const float w = live ? alpha * T_before : 0.0f;
-                r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
-                T = T * lane63(pin);
-                tcarry = lane63(tt);
-                if (T < T_thresh) break;
-            }
-            r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d);
-        }
-        // ---- finish (renderer.py:316-318) + loss (nerf/utils.py:516,557), every lane the same values ----
-        const float b0 = fin.mode == 2 ? fin.bg[index * 3] : fin.bg_scalar, b1 = fin.mode == 2 ? fin.bg[index * 3 + 1] : fin.bg_scalar,
-                    b2 = fin.mode == 2 ? fin.bg[index * 3 + 2] : fin.bg_scalar;
-        const float t1 = 1.0f - ws;
-        const float i0 = r + t1 * b0, i1 = g + t1 * b1, i2 = b + t1 * b2;
-        const float scale = loss_scale ? loss_scale[0] : 1.0f;
-        const float norm = 2.0f / (float)(3u * N);
-        const float e0 = i0 - target[index * 3], e1 = i1 - target[index * 3 + 1], e2 = i2 - target[index * 3 + 2];
-        const float gi0 = (norm * e0) * scale, gi1 = (norm * e1) * scale, gi2 = (norm * e2) * scale;
-        if (lane == 0) {
-            weights_sum[index] = ws;
-            fin.image_out[index * 3] = i0; fin.image_out[index * 3 + 1] = i1; fin.image_out[index * 3 + 2] = i2;
-            const float nr = fin.nears[index], fr = fin.fars[index];
-            fin.depth_out[index] = fmaxf(d - nr, 0.0f) / (fr - nr);
-            // write-through store (agent scope): the last workgroup reads it from another XCD without anybody flushing an L2
-            __hip_atomic_store(&ray_err[n], __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, e0 * e0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // ---- backward sweep (k_composite_train_bwd with grad_weights_sum = 0, then k_rgb_backward) ----
-        if (has_rows) {
-            const float gw = 0.0f - (gi0 * b0 + gi1 * b1 + gi2 * b2);
-            const float rf = r, gf = g, bf = b, wsf = ws;
-            float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f;
-            for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-                const uint32_t s = s0 + lane;
-                const bool valid = s < num;
-                float sg = 0.0f, d0 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-                if (valid) {
-                    sg = sigmas[offset + s];
-                    d0 = deltas[(size_t)(offset + s) * 2];
-                    cr = rgbs[(size_t)(offset + s) * 3];
-                    cg = rgbs[(size_t)(offset + s) * 3 + 1];
-                    cb = rgbs[(size_t)(offset + s) * 3 + 2];
-                }
-                const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
-                const float pin = wave_incl_prod(1.0f - alpha, lane);
-                                const float T_before = T * prev_lane(1.0f, pin);
-                const float T_after = T * pin;
-                const bool live = valid && !(T_before < T_thresh);
-                const float w = live ? alpha * T_before : 0.0f;
-                const float ra = rc + wave_incl_sum(w * cr, lane);
-                const float ga = gc + wave_incl_sum(w * cg, lane);
-                const float ba = bc + wave_incl_sum(w * cb, lane);
-                if (live) {
-                    const uint32_t o = offset + s;
-                    half8_t lo, hi;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) { lo[i] = (half_t)0.0f; hi[i] = (half_t)0.0f; }
-                    lo[0] = to_half_rne((gi0 * w) * (cr * (1.0f - cr)));
-                    lo[1] = to_half_rne((gi1 * w) * (cg * (1.0f - cg)));
-                    lo[2] = to_half_rne((gi2 * w) * (cb * (1.0f - cb)));
-                    half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
-                    dst[0] = lo; dst[1] = hi;
-                    grad_sigmas[o] = d0 * (gi0 * (T_after * cr - (rf - ra)) + gi1 * (T_after * cg - (gf - ga)) +
-                                           gi2 * (T_after * cb - (bf - ba)) + gw * (1.0f - wsf));
-                } else if (valid) {
-                    zero_row(offset + s);
-                }
-                T = T * lane63(pin);
-                rc = lane63(ra); gc = lane63(ga); bc = lane63(ba);
-                if (T < T_thresh) {
-                    for (uint32_t z = s0 + 64 + lane; z < num; z += 64) zero_row(offset + z);
-                    break;
-                }
-            }
-        }
-    }
-    // ---- the loss value: the last workgroup sums the per-ray errors in a fixed order ----
+// The loss VALUE of the two one-launch training steps below: every ray has deposited its error in ray_err (a write-through store), the
+// last workgroup to finish (a ticket) adds them up in a fixed order -> deterministic.  Called by every thread of every ray workgroup.
+// ticket[0] and the group tickets must be 0 on entry (the marcher clears them every step); they are left 0.
+__device__ __forceinline__ void composite_loss_tail(const float* __restrict__ ray_err, uint32_t N, uint32_t* __restrict__ ticket,
+                                                    float* __restrict__ loss, uint32_t ray_blocks, uint32_t* __restrict__ group_tickets) {
     // loss == NULL: the caller has the sum carried by a later launch (ngp_grid_encode_backward_checked_slabs: common.h loss_sum_block, the
     // same routine) -- no ticket, no device-scope round trip at the end of every workgroup, no serial tail: 19 -> 14 us.
     if (loss == nullptr) return;
@@ -1336,15 +1225,62 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_loss_bwd(
     if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The image-space middle of a training iteration in ONE launch, one wavefront per ray:
+//   k_composite_train_fwd (+ finish)  ->  the Trainer's MSE loss and its scaled gradient (k_mse_loss)  ->  k_composite_train_bwd  ->
+//   the colour head's sigmoid backward (k_rgb_backward),
+// the two sweeps being those kernels' own routines and the rest their arithmetic expression for expression, so the gradients are the
+// same bits.  What a ray needs from the loss is its own three pixels, so nothing crosses rays except the loss VALUE (a logged scalar,
+// composite_loss_tail).  Four launches, their tails and the [N,3] / [M,3] fp32 intermediates (grad_image, grad_rgbs) are gone; the second
+// sweep re-reads sigma / rgb / delta from L2.
+__global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_loss_bwd(
+    const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas, const int32_t* __restrict__ rays,
+    uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum, Finish fin, const float* __restrict__ target,
+    const float* __restrict__ loss_scale, float* __restrict__ ray_err, uint32_t* __restrict__ ticket, float* __restrict__ loss,
+    float* __restrict__ grad_sigmas, half_t* __restrict__ grad_out16, const uint32_t* __restrict__ rows_used, uint32_t ray_blocks,
+    uint32_t* __restrict__ group_tickets) {
+    const int lane = threadIdx.x & 63;
+    const SigmoidHalfSink sink{grad_sigmas, grad_out16};
+    if (blockIdx.x >= ray_blocks) return zero_unowned_rows(sink, rows_used, M, ray_blocks);
+    const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
+    if (n < N) {
+        const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
+        const bool has_rows = num != 0 && offset + num <= M;
+        RayTotals f{};
+        if (has_rows) f = composite_forward_sweep<false>(sigmas, rgbs, deltas, offset, num, T_thresh, lane);
+        // ---- finish (renderer.py:316-318) + loss (nerf/utils.py:516,557), every lane the same values ----
+        const float b0 = fin.mode == 2 ? fin.bg[index * 3] : fin.bg_scalar, b1 = fin.mode == 2 ? fin.bg[index * 3 + 1] : fin.bg_scalar,
+                    b2 = fin.mode == 2 ? fin.bg[index * 3 + 2] : fin.bg_scalar;
+        const float t1 = 1.0f - f.ws;
+        const float i0 = f.r + t1 * b0, i1 = f.g + t1 * b1, i2 = f.b + t1 * b2;
+        const float scale = loss_scale ? loss_scale[0] : 1.0f;
+        const float norm = 2.0f / (float)(3u * N);
+        const float e0 = i0 - target[index * 3], e1 = i1 - target[index * 3 + 1], e2 = i2 - target[index * 3 + 2];
+        const float gi0 = (norm * e0) * scale, gi1 = (norm * e1) * scale, gi2 = (norm * e2) * scale;
+        if (lane == 0) {
+            weights_sum[index] = f.ws;
+            fin.image_out[index * 3] = i0; fin.image_out[index * 3 + 1] = i1; fin.image_out[index * 3 + 2] = i2;
+            const float nr = fin.nears[index], fr = fin.fars[index];
+            fin.depth_out[index] = fmaxf(f.d - nr, 0.0f) / (fr - nr);
+            // write-through store (agent scope): the last workgroup reads it from another XCD without anybody flushing an L2
+            __hip_atomic_store(&ray_err[n], __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, e0 * e0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        // ---- backward sweep (grad_weights_sum = 0), the forward totals from registers ----
+        if (has_rows) {
+            const float gw = 0.0f - (gi0 * b0 + gi1 * b1 + gi2 * b2);
+            composite_backward_sweep<false>(sigmas, rgbs, deltas, offset, num, T_thresh, lane, f, RayGrads{gi0, gi1, gi2, gw, 0.0f, 0.0f}, sink);
+        }
+    }
+    composite_loss_tail(ray_err, N, ticket, loss, ray_blocks, group_tickets);
+}
+
 // k_composite_train_loss_bwd with the geometry terms in the loss, N rays:
 //   L = mean((image_out - target)^2) + lambda_distortion mean_n(dist_n / span_n) + lambda_depth mean_n(m_n (d_n - z_n)^2),
 //   span_n = max(fars_n - nears_n, FLT_MIN)   (dist_n, d_n: the raw distortion and depth of k_composite_train_geo_fwd; m: depth_weight, z: target_depth)
-// The same launch contract (tail workgroups, every row of grad_sigmas / grad_out16 written, tickets, loss == NULL).  Compositing, finish, MSE
-// and sigmoid backward are k_composite_train_loss_bwd's expressions, the distortion scans (X, A) k_composite_train_geo_fwd's, the backward
-// scans (t, D, G) k_composite_train_geo_bwd's, term for term; the ray totals the backward needs (depth, 2 dist) stay in registers.  With
-// both lambdas 0 the two new terms of grad_sigmas are zeros: the plain kernel's bits.  A ray without rows (empty, or not fitting M) adds
-// its terms to the loss VALUE (depth 0, distortion 0) and has no gradient, as in autograd.  ray_err carries 3 x the new terms: the
-// unchanged loss_sum_block (sum / 3N) then returns L.
+// The same launch contract (tail workgroups, every row of grad_sigmas / grad_out16 written, tickets, loss == NULL) and the same routines,
+// in their GEO form; finish and MSE are k_composite_train_loss_bwd's expressions; the ray totals the backward needs (depth, dist) stay in
+// registers.  With both lambdas 0 the two new terms of grad_sigmas are zeros: the plain kernel's bits.  A ray without rows (empty, or not
+// fitting M) adds its terms to the loss VALUE (depth 0, distortion 0) and has no gradient, as in autograd.  ray_err carries 3 x the new
+// terms: the unchanged loss_sum_block (sum / 3N) then returns L.
 __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_loss_bwd(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas, const int32_t* __restrict__ rays,
     uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum, Finish fin, const float* __restrict__ target,
@@ -1353,188 +1289,48 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_train_geo_loss_bwd(
     uint32_t* __restrict__ ticket, float* __restrict__ loss, float* __restrict__ grad_sigmas, half_t* __restrict__ grad_out16,
     const uint32_t* __restrict__ rows_used, uint32_t ray_blocks, uint32_t* __restrict__ group_tickets) {
     const int lane = threadIdx.x & 63;
-    auto zero_row = [&](uint32_t o) {
-        half8_t z;
-#pragma unroll
-        for (int i = 0; i < 8; i++) z[i] = (half_t)0.0f;
-        half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
-        dst[0] = z; dst[1] = z;
-        grad_sigmas[o] = 0.0f;
-    };
-    if (blockIdx.x >= ray_blocks) {  // rows >= *rows_used that no ray owns
-        const uint32_t first = min(rows_used[0], M);
-        const uint32_t stride = (gridDim.x - ray_blocks) * CT_WAVES * 64;
-        for (uint32_t o = first + (blockIdx.x - ray_blocks) * CT_WAVES * 64 + threadIdx.x; o < M; o += stride) zero_row(o);
-        return;
-    }
+    const SigmoidHalfSink sink{grad_sigmas, grad_out16};
+    if (blockIdx.x >= ray_blocks) return zero_unowned_rows(sink, rows_used, M, ray_blocks);
     const uint32_t n = blockIdx.x * CT_WAVES + (threadIdx.x >> 6);
     if (n < N) {
         const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num = (uint32_t)rays[n * 3 + 2];
         const bool has_rows = num != 0 && offset + num <= M;
-        // ---- forward sweep (k_composite_train_geo_fwd) ----
-        float r = 0, g = 0, b = 0, ws = 0, d = 0, dist = 0;
-        if (has_rows) {
-            float T = 1.0f, tcarry = 0.0f, xcarry = 0.0f, acarry = 0.0f;
-            for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-                const uint32_t s = s0 + lane;
-                const bool valid = s < num;
-                float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-                if (valid) {
-                    sg = sigmas[offset + s];
-                    const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
-                    d0 = dl.x; d1 = dl.y;
-                    cr = rgbs[(size_t)(offset + s) * 3];
-                    cg = rgbs[(size_t)(offset + s) * 3 + 1];
-                    cb = rgbs[(size_t)(offset + s) * 3 + 2];
-                }
-                const float e = __expf(-sg * d0);
-                const float alpha = valid ? 1.0f - e : 0.0f;
-                const float om = 1.0f - alpha;
-                const float pin = wave_incl_prod(om, lane);
-                const float T_before = T * prev_lane(1.0f, pin);
-                const float tt = tcarry + wave_incl_sum(d1, lane);
-                const bool live = valid && !(T_before < T_thresh);
-                const float w = live ? alpha * T_before : 0.0f;
-                r += w * cr; g += w * cg; b += w * cb; ws += w; d += w * tt;
-                // the distortion's own weights (invalid lanes: sg = d0 = d1 = 0)
-                const float x = sg * d0;
-                const float xa = xcarry + wave_incl_sum(x, lane);         // X_<=i
-                const float Tq = __expf(-prev_lane(xcarry, xa));          // T'_i = exp(-X_<i)
-                const float wq = live ? one_minus_exp_neg(x, e) * Tq : 0.0f;
-                const float a = acarry + wave_incl_sum((1.0f - Tq) * d1, lane);  // A_i (lanes behind the stop: w' = 0)
-                dist += 2.0f * wq * a + (1.0f / 3.0f) * (wq * wq * d0);
-                T = T * lane63(pin);
-                tcarry = lane63(tt);
-                xcarry = lane63(xa);
-                acarry = lane63(a);
-                if (T < T_thresh) break;  // wave-uniform
-            }
-            r = wave_total(r); g = wave_total(g); b = wave_total(b); ws = wave_total(ws); d = wave_total(d); dist = wave_total(dist);
-        }
+        RayTotals f{};
+        if (has_rows) f = composite_forward_sweep<true>(sigmas, rgbs, deltas, offset, num, T_thresh, lane);
         // ---- finish + loss (k_composite_train_loss_bwd) and the two geometry terms, every lane the same values ----
         const float b0 = fin.mode == 2 ? fin.bg[index * 3] : fin.bg_scalar, b1 = fin.mode == 2 ? fin.bg[index * 3 + 1] : fin.bg_scalar,
                     b2 = fin.mode == 2 ? fin.bg[index * 3 + 2] : fin.bg_scalar;
-        const float t1 = 1.0f - ws;
-        const float i0 = r + t1 * b0, i1 = g + t1 * b1, i2 = b + t1 * b2;
+        const float t1 = 1.0f - f.ws;
+        const float i0 = f.r + t1 * b0, i1 = f.g + t1 * b1, i2 = f.b + t1 * b2;
         const float scale = loss_scale ? loss_scale[0] : 1.0f;
         const float norm = 2.0f / (float)(3u * N);
         const float e0 = i0 - target[index * 3], e1 = i1 - target[index * 3 + 1], e2 = i2 - target[index * 3 + 2];
         const float gi0 = (norm * e0) * scale, gi1 = (norm * e1) * scale, gi2 = (norm * e2) * scale;
         const float nr = fin.nears[index], fr = fin.fars[index];
         const float span = fmaxf(fr - nr, FLT_MIN);   // the renderer's clamp_min(tiny): a ray that misses the box has near = far
-        const float dn = dist / span;
+        const float dn = f.dist / span;
         const float gl = ((lambda_distortion / (float)N) / span) * scale;          // dL/d dist_n, scaled
         const float m = depth_weight ? depth_weight[index] : 1.0f;
-        const float dz = d - (target_depth ? target_depth[index] : 0.0f);          // (NULL only with lambda_depth == 0)
+        const float dz = f.d - (target_depth ? target_depth[index] : 0.0f);        // (NULL only with lambda_depth == 0)
         const float gd = (((2.0f * lambda_depth) / (float)N) * m * dz) * scale;    // dL/d d_n, scaled
         if (lane == 0) {
-            weights_sum[index] = ws;
+            weights_sum[index] = f.ws;
             fin.image_out[index * 3] = i0; fin.image_out[index * 3 + 1] = i1; fin.image_out[index * 3 + 2] = i2;
-            fin.depth_out[index] = fmaxf(d - nr, 0.0f) / (fr - nr);
-            depth_raw[index] = d;
+            fin.depth_out[index] = fmaxf(f.d - nr, 0.0f) / (fr - nr);
+            depth_raw[index] = f.d;
             distortion[index] = dn;
             // write-through store (agent scope), as in k_composite_train_loss_bwd
             __hip_atomic_store(&ray_err[n], __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, e0 * e0)) +
                                                 3.0f * (lambda_distortion * dn + lambda_depth * (m * (dz * dz))),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        // ---- backward sweep (k_composite_train_geo_bwd with grad_weights_sum = gw, then k_rgb_backward) ----
+        // ---- backward sweep (grad_weights_sum = gw), the forward totals from registers ----
         if (has_rows) {
             const float gw = 0.0f - (gi0 * b0 + gi1 * b1 + gi2 * b2);
-            const float rf = r, gf = g, bf = b, wsf = ws, df = d, gtot = 2.0f * dist;
-            float T = 1.0f, rc = 0.0f, gc = 0.0f, bc = 0.0f, tcarry = 0.0f, dcarry = 0.0f, gcarry = 0.0f;
-            for (uint32_t s0 = 0; s0 < num; s0 += 64) {
-                const uint32_t s = s0 + lane;
-                const bool valid = s < num;
-                float sg = 0.0f, d0 = 0.0f, d1 = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-                if (valid) {
-                    sg = sigmas[offset + s];
-                    const float2_t dl = *reinterpret_cast<const float2_t*>(deltas + (size_t)(offset + s) * 2);
-                    d0 = dl.x; d1 = dl.y;
-                    cr = rgbs[(size_t)(offset + s) * 3];
-                    cg = rgbs[(size_t)(offset + s) * 3 + 1];
-                    cb = rgbs[(size_t)(offset + s) * 3 + 2];
-                }
-                const float alpha = valid ? 1.0f - __expf(-sg * d0) : 0.0f;
-                const float pin = wave_incl_prod(1.0f - alpha, lane);
-                const float T_before = T * prev_lane(1.0f, pin);
-                const float T_after = T * pin;
-                const float tt = tcarry + wave_incl_sum(d1, lane);
-                const bool live = valid && !(T_before < T_thresh);
-                const float w = live ? alpha * T_before : 0.0f;
-                const float ra = rc + wave_incl_sum(w * cr, lane);
-                const float ga = gc + wave_incl_sum(w * cg, lane);
-                const float ba = bc + wave_incl_sum(w * cb, lane);
-                const float da = dcarry + wave_incl_sum(w * tt, lane);  // D_<=i
-                const float d_before = prev_lane(dcarry, da);           // D_<i
-                const float d_rest = df - da;                            // D - D_<=i
-                const float w_rest = wsf - (1.0f - T_after);             // W - W_<=i
-                const float gwi = 2.0f * (tt * (1.0f - T_before) - d_before) + 2.0f * (d_rest - tt * w_rest) + (2.0f / 3.0f) * (w * d0);
-                const float gga = gcarry + wave_incl_sum(gwi * w, lane);  // G_<=i
-                if (live) {
-                    const uint32_t o = offset + s;
-                    half8_t lo, hi;
-#pragma unroll
-                    for (int i = 0; i < 8; i++) { lo[i] = (half_t)0.0f; hi[i] = (half_t)0.0f; }
-                    lo[0] = to_half_rne((gi0 * w) * (cr * (1.0f - cr)));
-                    lo[1] = to_half_rne((gi1 * w) * (cg * (1.0f - cg)));
-                    lo[2] = to_half_rne((gi2 * w) * (cb * (1.0f - cb)));
-                    half8_t* dst = reinterpret_cast<half8_t*>(grad_out16 + (size_t)o * 16);
-                    dst[0] = lo; dst[1] = hi;
-                    const float plain = gi0 * (T_after * cr - (rf - ra)) + gi1 * (T_after * cg - (gf - ga)) + gi2 * (T_after * cb - (bf - ba)) +
-                                        gw * (1.0f - wsf);
-                    grad_sigmas[o] = d0 * (plain + gd * (T_after * tt - d_rest) + gl * (gwi * T_after - (gtot - gga)));
-                } else if (valid) {
-                    zero_row(offset + s);
-                }
-                T = T * lane63(pin);
-                tcarry = lane63(tt);
-                rc = lane63(ra); gc = lane63(ga); bc = lane63(ba); dcarry = lane63(da); gcarry = lane63(gga);
-                if (T < T_thresh) {
-                    for (uint32_t z = s0 + 64 + lane; z < num; z += 64) zero_row(offset + z);
-                    break;
-                }
-            }
+            composite_backward_sweep<true>(sigmas, rgbs, deltas, offset, num, T_thresh, lane, f, RayGrads{gi0, gi1, gi2, gw, gd, gl}, sink);
         }
     }
-    // ---- the loss value: k_composite_train_loss_bwd's tail, statement for statement (see the notes there; a separate body so that the
-    // plain kernel keeps its code) ----
-    if (loss == nullptr) return;
-    __shared__ float part[CT_WAVES];
-    __shared__ bool last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every lane: its own stores (the write-through ray_err store among them) have completed
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t groups = ray_blocks < CT_GROUPS ? ray_blocks : CT_GROUPS;
-        const uint32_t group = blockIdx.x % groups, members = (ray_blocks - group + groups - 1u) / groups;
-        uint32_t* gt = group_tickets + group * CT_GROUP_STRIDE;
-        bool l = false;
-        if (__hip_atomic_fetch_add(gt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1u) {
-            __hip_atomic_store(gt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            l = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1u;
-        }
-        last = l;
-    }
-    __syncthreads();
-    if (!last) return;
-    // common.h loss_sum_block, statement for statement (the same order of additions: the same bits).  Not a call: with a second call site in
-    // this file the compiler stops specialising that routine for its single caller and k_composite_train_loss_bwd gets another register
-    // allocation (read off the disassembly, EXPERIMENTS.md)
-    static_assert(CT_WAVES == 4, "four wave sums");
-    const uint32_t t = threadIdx.x;
-    float acc = 0.0f;
-    for (uint32_t i = t; i < N; i += 256u) acc += __hip_atomic_load(&ray_err[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    acc = wave_total(acc);
-    if ((t & 63u) == 0u) part[t >> 6] = acc;
-    __syncthreads();
-    if (t == 0u) {
-        float v = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 4; w++) v += part[w];
-        loss[0] = v / (float)(3u * N);
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    composite_loss_tail(ray_err, N, ticket, loss, ray_blocks, group_tickets);
 }
 
 // raymarching.cu:819-905 -- at most 8 samples per ray and call: one lane per alive ray
@@ -2111,7 +1907,6 @@ extern "C" int ngp_composite_rays_train_forward_ex(const float* sigmas, const fl
     Finish fin;
     int rc = make_finish("composite_rays_train_forward", bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, true, &fin);
     if (rc) return rc;
-    if (N == 0) return NGP_OK;
     hipLaunchKernelGGL(k_composite_train_fwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs, deltas,
                        rays, M, N, T_thresh, weights_sum, depth, image, fin);
     return check_launch("composite_rays_train_forward");
@@ -2136,7 +1931,6 @@ extern "C" int ngp_composite_rays_train_backward_ex(const float* grad_weights_su
     Finish fin;
     int rc = make_finish("composite_rays_train_backward", bg_mode, bg_scalar, bg, nullptr, nullptr, nullptr, nullptr, false, &fin);
     if (rc) return rc;
-    if (N == 0) return NGP_OK;
     const uint32_t ray_blocks = cdiv(N, CT_WAVES);
     const uint32_t tail_blocks = rows_used ? 32u : 0u;
     hipLaunchKernelGGL(k_composite_train_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), grad_weights_sum,
@@ -2222,22 +2016,28 @@ extern "C" int ngp_composite_rays_train_features_backward(const float* grad_out,
     return check_launch("composite_rays_train_features_backward");
 }
 
+// the checks the two one-launch training steps share, and their Finish
+static int fused_loss_args(const char* fn, uint32_t N, size_t march_workspace_bytes, int bg_mode, float bg_scalar, const float* bg, const float* nears,
+                           const float* fars, float* image_out, float* depth_out, Finish* fin) {
+    NGP_REQUIRE(march_workspace_bytes >= ngp_march_rays_train_workspace_bytes(N), NGP_ERR_INVALID,
+                "%s: march_workspace of %zu bytes, needs ngp_march_rays_train_workspace_bytes(%u) = %zu (the group tickets sit at its end)", fn,
+                march_workspace_bytes, N, ngp_march_rays_train_workspace_bytes(N));
+    NGP_REQUIRE(bg_mode == 1 || bg_mode == 2, NGP_ERR_INVALID, "%s: bg_mode must be 1 (scalar) or 2 (per ray)", fn);
+    NGP_REQUIRE((uint64_t)N * 3u <= 0xffffffffull, NGP_ERR_INVALID, "%s: too many rays", fn);
+    return make_finish(fn, bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, true, fin);
+}
+
 extern "C" int ngp_composite_train_loss_backward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M,
                                                  uint32_t N, float T_thresh, int bg_mode, float bg_scalar, const float* bg, const float* nears,
                                                  const float* fars, const float* target, const float* loss_scale, float* weights_sum,
                                                  float* image_out, float* depth_out, float* loss, float* ray_err, float* grad_sigmas,
                                                  void* grad_out16, void* march_workspace, size_t march_workspace_bytes, ngp_stream_t stream) {
     NGP_REQUIRE(N > 0, NGP_ERR_INVALID, "composite_train_loss_backward: no rays");
-    NGP_REQUIRE(march_workspace_bytes >= ngp_march_rays_train_workspace_bytes(N), NGP_ERR_INVALID,
-                "composite_train_loss_backward: march_workspace of %zu bytes, needs ngp_march_rays_train_workspace_bytes(%u) = %zu (the group tickets sit at its end)",
-                march_workspace_bytes, N, ngp_march_rays_train_workspace_bytes(N));
     // (loss may be NULL: the sum of ray_err is then left to the caller -- ngp_grid_encode_backward_checked_slabs carries it)
     NGP_REQUIRE(sigmas && rgbs && deltas && rays && target && weights_sum && ray_err && grad_sigmas && grad_out16 && march_workspace,
                 NGP_ERR_INVALID, "composite_train_loss_backward: NULL tensor");
-    NGP_REQUIRE(bg_mode == 1 || bg_mode == 2, NGP_ERR_INVALID, "composite_train_loss_backward: bg_mode must be 1 (scalar) or 2 (per ray)");
-    NGP_REQUIRE((uint64_t)N * 3u <= 0xffffffffull, NGP_ERR_INVALID, "composite_train_loss_backward: too many rays");
     Finish fin;
-    int rc = make_finish("composite_train_loss_backward", bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, true, &fin);
+    int rc = fused_loss_args("composite_train_loss_backward", N, march_workspace_bytes, bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, &fin);
     if (rc) return rc;
     uint32_t* ws = reinterpret_cast<uint32_t*>(march_workspace);
     const uint32_t ray_blocks = cdiv(N, CT_WAVES), tail_blocks = 32u;
@@ -2263,13 +2063,9 @@ extern "C" int ngp_composite_train_geo_loss_backward(const float* sigmas, const 
                 "composite_train_geo_loss_backward: lambda_distortion = %g, lambda_depth = %g must be finite and >= 0", (double)lambda_distortion,
                 (double)lambda_depth);
     NGP_REQUIRE(target_depth || lambda_depth == 0.0f, NGP_ERR_INVALID, "composite_train_geo_loss_backward: lambda_depth > 0 needs target_depth");
-    NGP_REQUIRE(march_workspace_bytes >= ngp_march_rays_train_workspace_bytes(N), NGP_ERR_INVALID,
-                "composite_train_geo_loss_backward: march_workspace of %zu bytes, needs ngp_march_rays_train_workspace_bytes(%u) = %zu (the group tickets sit at its end)",
-                march_workspace_bytes, N, ngp_march_rays_train_workspace_bytes(N));
-    NGP_REQUIRE(bg_mode == 1 || bg_mode == 2, NGP_ERR_INVALID, "composite_train_geo_loss_backward: bg_mode must be 1 (scalar) or 2 (per ray)");
-    NGP_REQUIRE((uint64_t)N * 3u <= 0xffffffffull, NGP_ERR_INVALID, "composite_train_geo_loss_backward: too many rays");
     Finish fin;
-    int rc = make_finish("composite_train_geo_loss_backward", bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, true, &fin);
+    int rc = fused_loss_args("composite_train_geo_loss_backward", N, march_workspace_bytes, bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out,
+                             &fin);
     if (rc) return rc;
     uint32_t* ws = reinterpret_cast<uint32_t*>(march_workspace);
     const uint32_t ray_blocks = cdiv(N, CT_WAVES), tail_blocks = 32u;
