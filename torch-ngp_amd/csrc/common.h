@@ -182,6 +182,12 @@ struct SlabSets {
     float* loss;
     __host__ __device__ uint32_t total_blocks() const { return blocks[0] + blocks[1] + (loss ? 1u : 0u); }
 };
+// host side: fill set `set`.  THE block rule: a set with slabs to add gets blocks, and so does one without (its backward stored the gradients
+// directly) when `sweep` asks for the found_inf sweep over them; a set without parameters gets none.  Returns the set's blocks.
+inline uint32_t slab_set(SlabSets& s, int set, const void* slabs, uint32_t n_slabs, uint32_t n_params, void* grad_weights, bool sweep) {
+    s.slabs[set] = (const float*)slabs; s.n_slabs[set] = n_slabs; s.n_params[set] = n_params; s.grad_weights[set] = (_Float16*)grad_weights;
+    return s.blocks[set] = (n_slabs || sweep) && n_params ? cdiv(n_params, (uint32_t)RS_PARAMS) : 0u;
+}
 // block `b` of a grid row that carries the jobs (all threads of a RS_PARAMS x RS_GROUPS block; part: RS_GROUPS x RS_PARAMS floats of LDS)
 __device__ __forceinline__ void slab_reduce_block(const SlabSets& s, uint32_t b, float (*part)[RS_PARAMS], float* found_inf);
 __device__ __forceinline__ void carried_block(const SlabSets& s, uint32_t b, float (*part)[RS_PARAMS], float* found_inf) {

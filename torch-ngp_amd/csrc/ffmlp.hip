@@ -96,7 +96,7 @@ struct Shape {
 };
 
 template <int WIDTH>
-__device__ __forceinline__ uint32_t fwd_frag_count(uint32_t in_dim, uint32_t num_layers) {
+__host__ __device__ __forceinline__ uint32_t fwd_frag_count(uint32_t in_dim, uint32_t num_layers) {
     return Shape<WIDTH>::NIB * (in_dim / 16) + (num_layers - 1) * Shape<WIDTH>::NIB * Shape<WIDTH>::NKB + Shape<WIDTH>::NKB;
 }
 
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
 //   hid : layers NL-1 .. 1, each [ib<NIB][kb<NKB]   A[i][slot(kb,h,j)] = W_l[slot_feature][i]
 //   in  : [ib<in/32 rounded up][kb<NKB]             A[i=input feat][slot] = W_in[slot_feature][i]   (only if dL/dx wanted)
 template <int WIDTH>
-__device__ __forceinline__ uint32_t bwd_frag_count(uint32_t in_dim, uint32_t num_layers, bool with_dx) {
+__host__ __device__ __forceinline__ uint32_t bwd_frag_count(uint32_t in_dim, uint32_t num_layers, bool with_dx) {
     constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     return NIB + (num_layers - 1) * NIB * NKB + (with_dx ? ((in_dim + 31) / 32) * NKB : 0);
 }
@@ -784,9 +784,17 @@ __device__ __forceinline__ void activation_transfer(uint32_t act, const float16_
     }
 }
 
-// Number of fp32 words of one weight-gradient slab = number of parameters.
+// Where the matrices lie in the flat parameter vector (ffmlp.cu:631-634) and so in a weight-gradient slab, one fp32 word per parameter:
+// W_in [width, in_dim] | the matmuls into hidden layers 1 .. num_layers-1, [width, width] each | W_out [16, width].
+struct SlabLayout {
+    uint32_t width, in_dim, num_layers;
+    __host__ __device__ constexpr uint32_t in() const { return 0u; }
+    __host__ __device__ constexpr uint32_t hidden(uint32_t l) const { return width * in_dim + (l - 1) * width * width; }  // the matmul INTO hidden layer l
+    __host__ __device__ constexpr uint32_t out() const { return hidden(num_layers); }
+    __host__ __device__ constexpr uint32_t n_params() const { return width * (in_dim + width * (num_layers - 1) + 16u); }
+};
 __host__ __device__ inline uint32_t ff_param_count(uint32_t in_dim, uint32_t hidden, uint32_t num_layers) {
-    return hidden * (in_dim + hidden * (num_layers - 1) + 16);
+    return SlabLayout{hidden, in_dim, num_layers}.n_params();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -888,12 +896,12 @@ constexpr bool slab_staged_single = Shape<WIDTH>::NIB * (1 + IN_JB + NHM * Shape
 template <int WIDTH, int IN_JB, int NHM>
 constexpr bool slab_staged_paired = Shape<WIDTH>::NIB * (IN_JB + (NHM == 2 ? Shape<WIDTH>::NIB : 0)) <= 6 && Shape<WIDTH>::NIB * (1 + Shape<WIDTH>::NIB) <= 6;
 // the launcher's side: the whole slab, or the larger of the paired kernel's two parts -- everything behind the input layer's matrix, and that matrix
-constexpr size_t slab_stage_bytes(bool whole, uint32_t n_params, uint32_t len_in) {
-    const uint32_t rest = n_params - len_in;
-    return (size_t)SS_COPIES * sizeof(float) * (whole ? n_params : (rest > len_in ? rest : len_in));
+constexpr size_t slab_stage_bytes(bool whole, const SlabLayout& lay) {
+    const uint32_t len_in = lay.hidden(1), rest = lay.n_params() - len_in;
+    return (size_t)SS_COPIES * sizeof(float) * (whole ? lay.n_params() : (rest > len_in ? rest : len_in));
 }
 
-// one wave's copy of a part; put() = the serial form's flush without its read: accumulator block (ib, jb) of the matrix at slab offset base
+// one wave's copy of a part; put() = the serial form's (SlabSerial) without its read: accumulator block (ib, jb) of the matrix at slab offset base
 struct SlabCopy {
     float* at;
     uint32_t p0;
@@ -907,6 +915,47 @@ struct SlabCopy {
         }
     }
 };
+
+// the serial form's sink (NGP_FF_SERIAL_FLUSH, and the instantiations that keep it alone): the wave whose turn it is adds its block into the
+// one copy `red`.  Every (row, col) of a gradient matrix belongs to exactly one lane of a wave, so the waves add their partial sums one after
+// the other without atomics: the order is fixed => bit-reproducible.  The sixteen partial sums of a block are READ together, then added and
+// written: as `red[..] += a[r]` the compiler has to order every read behind the previous write (it cannot see that the sixteen addresses
+// differ) -- sixteen dependent LDS round trips per block and wave, ~20 of the paired kernel's 47 us when it was written so (round 4).
+struct SlabSerial {
+    float* red;
+    int n, h;
+    __device__ __forceinline__ void put(const float16_t& a, uint32_t base, uint32_t ld, int ib, int jb, uint32_t rws, uint32_t cols) const {
+        float t[16];
+        const uint32_t i = 32 * jb + n;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t o = (uint32_t)acc_row(ib, h, r);
+            t[r] = (o < rws && i < cols) ? red[base + o * ld + i] : 0.0f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const uint32_t o = (uint32_t)acc_row(ib, h, r);
+            if (o < rws && i < cols) red[base + o * ld + i] = t[r] + a[r];
+        }
+    }
+};
+// before the first turn (all threads): the zeroed copy
+template <int THREADS>
+__device__ __forceinline__ void slab_serial_begin(float* red, uint32_t n_params) {
+    __syncthreads();  // every wave is done with the weight image and the stages
+    for (uint32_t i = threadIdx.x; i < n_params; i += THREADS) red[i] = 0.0f;
+    __syncthreads();
+}
+// behind the barrier of the last turn (all threads): the copy becomes the workgroup's slab, or (one workgroup) the fp16 gradient itself
+template <int THREADS>
+__device__ __forceinline__ void slab_serial_store(const float* red, uint32_t n_params, float* __restrict__ slabs, half_t* __restrict__ direct) {
+    if (direct) {
+        for (uint32_t i = threadIdx.x; i < n_params; i += THREADS) direct[i] = (half_t)red[i];
+    } else {
+        float* slab = slabs + (size_t)blockIdx.x * n_params;
+        for (uint32_t i = threadIdx.x; i < n_params; i += THREADS) slab[i] = red[i];
+    }
+}
 
 // one pass, called by ALL threads of the workgroup: stage_fn(SlabCopy) stores this wave's accumulators of the part (a wave that holds none
 // stores nothing), copy = which of the SS_COPIES this wave fills.  Every entry of the part is stored by exactly one lane of each copy.
@@ -932,6 +981,89 @@ __device__ __forceinline__ void slab_sum_pass(float* stage, uint32_t lds_bytes, 
             *reinterpret_cast<float4_t*>(slab + p.p0 + i) = s;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The steps of a tile, shared by the single-wave kernel and the two roles of the paired one.
+// ------------------------------------------------------------------------------------------------
+// dW [32 NI x 32 NJ] += Z^T . A over the tile's 32 samples (two 16-sample groups); operands from transpose_hidden / pack_transposed
+template <int NI, int NJ>
+__device__ __forceinline__ void wgrad_blocks(const half8_t (&zT)[NI][2], const half8_t (&aT)[NJ][2], float16_t (&gw)[NI][NJ]) {
+#pragma unroll
+    for (int g = 0; g < 2; g++)
+#pragma unroll
+        for (int ib = 0; ib < NI; ib++)
+#pragma unroll
+            for (int jb = 0; jb < NJ; jb++) gw[ib][jb] = mfma(zT[ib][g], aT[jb][g], gw[ib][jb]);
+}
+// output layer: dH_{L-1}^T = W_out^T . dY^T   (K = 16: one k block)
+template <int WIDTH>
+__device__ __forceinline__ void dgrad_out(const half8_t* __restrict__ img_out, const half8_t& dy, float16_t (&acc)[Shape<WIDTH>::NIB]) {
+#pragma unroll
+    for (int ib = 0; ib < Shape<WIDTH>::NIB; ib++) acc[ib] = mfma(img_out[ib * 64], dy, zero16());
+}
+// hidden matmul: dH_{l-1}^T = W_l^T . dZ_l^T   (wl: this lane's view of the matmul's [ib][kb] fragments of the backward image)
+template <int WIDTH>
+__device__ __forceinline__ void dgrad_hidden(const half8_t* __restrict__ wl, const half8_t (&dz)[Shape<WIDTH>::NKB], float16_t (&acc)[Shape<WIDTH>::NIB]) {
+    constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
+#pragma unroll
+    for (int ib = 0; ib < NIB; ib++) {
+        acc[ib] = zero16();
+#pragma unroll
+        for (int kb = 0; kb < NKB; kb++) acc[ib] = mfma(wl[(ib * NKB + kb) * 64], dz[kb], acc[ib]);
+    }
+}
+// dX^T [in x samples] = W_in^T . dZ_0^T, stored row-major [rows][in_dim] or planar [in_dim/2][rows][2] (the layout grid_encode_backward
+// consumes); rows beyond in_dim are zero weights and are not stored
+template <int WIDTH, int IN_JB>
+__device__ __forceinline__ void store_dx(const half8_t* __restrict__ img_in, const half8_t (&dz)[Shape<WIDTH>::NKB], half_t* __restrict__ grad_inputs,
+                                         uint32_t tile, int n, int h, uint32_t in_dim, size_t rows, bool dx_planar) {
+    constexpr int NKB = Shape<WIDTH>::NKB;
+#pragma unroll
+    for (int ib = 0; ib < IN_JB; ib++) {
+        float16_t dx = zero16();
+#pragma unroll
+        for (int kb = 0; kb < NKB; kb++) dx = mfma(img_in[(ib * NKB + kb) * 64], dz[kb], dx);
+        const size_t srow = (size_t)tile * FF_TILE + n;
+        half_t* grow = grad_inputs + srow * in_dim;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t f0 = 32 * ib + 8 * q + 4 * h;
+            if (f0 < in_dim) {
+                if (dx_planar) {
+                    const half2_t lo = {(half_t)dx[4 * q], (half_t)dx[4 * q + 1]}, hi = {(half_t)dx[4 * q + 2], (half_t)dx[4 * q + 3]};
+                    *reinterpret_cast<half2_t*>(grad_inputs + ((size_t)(f0 / 2) * rows + srow) * 2) = lo;
+                    *reinterpret_cast<half2_t*>(grad_inputs + ((size_t)(f0 / 2 + 1) * rows + srow) * 2) = hi;
+                } else {
+                    half4_t v = {(half_t)dx[4 * q], (half_t)dx[4 * q + 1], (half_t)dx[4 * q + 2], (half_t)dx[4 * q + 3]};
+                    *reinterpret_cast<half4_t*>(grow + f0) = v;
+                }
+            }
+        }
+    }
+}
+
+// The single-wave kernel's accumulators (every wave holds every matrix), block by block, into a slab sink: sink.put(block, slab offset of its
+// matrix, leading dimension, ib, jb, rows, cols).  A function of its own, not the body of the kernel's `each`: written out there, the 64-wide
+// 3- and 4-layer instantiations -- which fill the register file -- spill past the bounds tests/test_isa_invariants.py pins (EXPERIMENTS.md).
+template <int WIDTH, int IN_JB, int NHM, typename Sink>
+__device__ __forceinline__ void slab_put_all(const Sink& sink, const SlabLayout& lay, const float16_t (&gw_in)[Shape<WIDTH>::NIB][IN_JB],
+                                             const float16_t (&gw_hid)[NHM][Shape<WIDTH>::NIB][Shape<WIDTH>::NIB], const float16_t (&gw_out)[Shape<WIDTH>::NIB]) {
+    constexpr int NIB = Shape<WIDTH>::NIB;
+#pragma unroll
+    for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+        for (int jb = 0; jb < IN_JB; jb++) sink.put(gw_in[ib][jb], lay.in(), lay.in_dim, ib, jb, WIDTH, lay.in_dim);
+#pragma unroll
+    for (int li = 0; li < NHM; li++) {
+        const uint32_t base = lay.hidden(lay.num_layers - 1 - li);
+#pragma unroll
+        for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+            for (int jb = 0; jb < NIB; jb++) sink.put(gw_hid[li][ib][jb], base, WIDTH, ib, jb, WIDTH, WIDTH);
+    }
+#pragma unroll
+    for (int jb = 0; jb < NIB; jb++) sink.put(gw_out[jb], lay.out(), WIDTH, 0, jb, 16, WIDTH);
 }
 
 template <int WIDTH, int IN_JB /* ceil(in_dim/32) */, int NHM /* hidden matmuls = num_layers-1 */, bool RELU /* hidden activation is ReLU */>
@@ -1012,10 +1144,8 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
 #pragma unroll
                 for (int jb = 0; jb < NIB; jb++) gw_out[jb] = mfma(yT[g], aT[jb][g], gw_out[jb]);
         }
-        // dH_{L-1}^T = W_out^T . dY^T   (K = 16: one k block)
         float16_t acc[NIB];
-#pragma unroll
-        for (int ib = 0; ib < NIB; ib++) acc[ib] = mfma(img_out[ib * 64], dy, zero16());
+        dgrad_out<WIDTH>(img_out, dy, acc);
 
         // ---- hidden layers, top down --------------------------------------------------------
         half8_t dz[NKB];
@@ -1028,21 +1158,8 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
             for (int kb = 0; kb < NKB; kb++) a_prev[kb] = tfrag[(1 + (lay - 1) * NKB + kb) * 64];
             transpose_hidden<WIDTH>(dz, sel, zT);
             transpose_hidden<WIDTH>(a_prev, sel, aT);
-            // dW_lay [WIDTH x WIDTH] += dZ_lay^T . A_{lay-1}
-#pragma unroll
-            for (int g = 0; g < 2; g++)
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                    for (int jb = 0; jb < NIB; jb++) gw_hid[li][ib][jb] = mfma(zT[ib][g], aT[jb][g], gw_hid[li][ib][jb]);
-            // dH_{lay-1}^T = W_lay^T . dZ_lay^T
-            const half8_t* wl = img_hid + (size_t)li * NIB * NKB * 64;
-#pragma unroll
-            for (int ib = 0; ib < NIB; ib++) {
-                acc[ib] = zero16();
-#pragma unroll
-                for (int kb = 0; kb < NKB; kb++) acc[ib] = mfma(wl[(ib * NKB + kb) * 64], dz[kb], acc[ib]);
-            }
+            wgrad_blocks(zT, aT, gw_hid[li]);  // dW_lay [WIDTH x WIDTH] += dZ_lay^T . A_{lay-1}
+            dgrad_hidden<WIDTH>(img_hid + (size_t)li * NIB * NKB * 64, dz, acc);
         }
         // ---- input layer --------------------------------------------------------------------
         activation_transfer<WIDTH, RELU>(act, acc, a_prev, dz);
@@ -1065,31 +1182,7 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
                     for (int ib = 0; ib < NIB; ib++) gw_in[ib][jb] = mfma(zT[ib][g], xT[g], gw_in[ib][jb]);
             }
         }
-        if (with_dx) {
-            // dX^T [in x samples] = W_in^T . dZ_0^T ; rows beyond in_dim are zero weights and are not stored
-#pragma unroll
-            for (int ib = 0; ib < IN_JB; ib++) {
-                float16_t dx = zero16();
-#pragma unroll
-                for (int kb = 0; kb < NKB; kb++) dx = mfma(img_in[(ib * NKB + kb) * 64], dz[kb], dx);
-                const size_t srow = (size_t)tile * FF_TILE + n;
-                half_t* grow = grad_inputs + srow * in_dim;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t f0 = 32 * ib + 8 * q + 4 * h;
-                    if (f0 < in_dim) {
-                        if (dx_planar) {  // [in_dim/2][rows][2]: the layout grid_encode_backward consumes
-                            const half2_t lo = {(half_t)dx[4 * q], (half_t)dx[4 * q + 1]}, hi = {(half_t)dx[4 * q + 2], (half_t)dx[4 * q + 3]};
-                            *reinterpret_cast<half2_t*>(grad_inputs + ((size_t)(f0 / 2) * rows + srow) * 2) = lo;
-                            *reinterpret_cast<half2_t*>(grad_inputs + ((size_t)(f0 / 2 + 1) * rows + srow) * 2) = hi;
-                        } else {
-                            half4_t v = {(half_t)dx[4 * q], (half_t)dx[4 * q + 1], (half_t)dx[4 * q + 2], (half_t)dx[4 * q + 3]};
-                            *reinterpret_cast<half4_t*>(grow + f0) = v;
-                        }
-                    }
-                }
-            }
-        }
+        if (with_dx) store_dx<WIDTH, IN_JB>(img_in, dz, grad_inputs, tile, n, h, in_dim, rows, dx_planar);
         if (pf_depth == 1 && tile + tile_step < n_tiles) {
             // single buffer (the weight image + two stages per wave do not fit 160 KiB): the next tile can only be requested once
             // this one has been consumed -- no overlap, but every tile is loaded
@@ -1100,80 +1193,24 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_backward(const half_t* __r
 
     // ---- combine the four waves' partial weight gradients in LDS, emit one slab per workgroup ----
     float* red = reinterpret_cast<float*>(smem);
-    const uint32_t n_params = ff_param_count(in_dim, WIDTH, num_layers);
+    const SlabLayout lay{WIDTH, in_dim, num_layers};
+    const uint32_t n_params = lay.n_params();
+    // every wave holds every matrix.  Accumulator block: row = output feature, col = input feature (32 * jb + lane & 31)
+    auto each = [&](const auto& sink) { slab_put_all<WIDTH, IN_JB, NHM>(sink, lay, gw_in, gw_hid, gw_out); };
     if (slab_staged_single<WIDTH, IN_JB, NHM> && !serial_flush) {
-        // every wave holds every matrix; the shapes that take this form are small enough for four copies of the whole slab: one pass
+        // the shapes that take this form are small enough for four copies of the whole slab: one pass
         static_assert(!slab_staged_single<WIDTH, IN_JB, NHM> || slab_fits_whole<WIDTH, IN_JB, NHM>, "the single-wave staged sum is one pass");
-        slab_sum_pass<FF_THREADS>(red, lds_bytes, SlabPart{0, n_params}, wid, slabs + (size_t)blockIdx.x * n_params, grad_weights_direct, n, h,
-                                  [&](const SlabCopy& c) {
-#pragma unroll
-            for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                for (int jb = 0; jb < IN_JB; jb++) c.put(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
-#pragma unroll
-            for (int li = 0; li < NHM; li++) {
-                const uint32_t base = WIDTH * in_dim + (num_layers - 2 - li) * WIDTH * WIDTH;  // gw_hid[li]: the matmul into hidden layer num_layers-1-li
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                    for (int jb = 0; jb < NIB; jb++) c.put(gw_hid[li][ib][jb], base, WIDTH, ib, jb, WIDTH, WIDTH);
-            }
-            const uint32_t base_out = WIDTH * in_dim + (num_layers - 1) * WIDTH * WIDTH;
-#pragma unroll
-            for (int jb = 0; jb < NIB; jb++) c.put(gw_out[jb], base_out, WIDTH, 0, jb, 16, WIDTH);
-        });
+        slab_sum_pass<FF_THREADS>(red, lds_bytes, SlabPart{0, n_params}, wid, slabs + (size_t)blockIdx.x * n_params, grad_weights_direct, n, h, each);
         return;
     }
     // the reference form (NGP_FF_SERIAL_FLUSH): the waves add into one zeroed copy, one after the other
-    __syncthreads();  // every wave is done with the weight image and the stages
-    for (uint32_t i = threadIdx.x; i < n_params; i += FF_THREADS) red[i] = 0.0f;
-    __syncthreads();
-    // accumulator (row = output feature o, col = input feature i = lane&31)
-    // every (row, col) of a gradient matrix belongs to exactly one lane of a wave, so the waves add their
-    // partial sums one after the other without atomics: the summation order is fixed => bit-reproducible.
-    // (the sixteen partial sums of a block are read together, then added and written: `red[..] += a[r]` in a loop is sixteen dependent LDS
-    // round trips, the compiler cannot see that the addresses differ)
-    auto flush = [&](const float16_t& a, uint32_t base, uint32_t ld, int ib, int jb, uint32_t rows, uint32_t cols) {
-        float t[16];
-        const uint32_t i = 32 * jb + n;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const uint32_t o = (uint32_t)acc_row(ib, h, r);
-            t[r] = (o < rows && i < cols) ? red[base + o * ld + i] : 0.0f;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const uint32_t o = (uint32_t)acc_row(ib, h, r);
-            if (o < rows && i < cols) red[base + o * ld + i] = t[r] + a[r];
-        }
-    };
+    slab_serial_begin<FF_THREADS>(red, n_params);
+    const SlabSerial serial{red, n, h};
     for (int turn = 0; turn < FF_WAVES; turn++) {
-        if (wid == turn) {
-#pragma unroll
-            for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                for (int jb = 0; jb < IN_JB; jb++) flush(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
-#pragma unroll
-            for (int li = 0; li < NHM; li++) {
-                const uint32_t lay = num_layers - 1 - li;
-                const uint32_t base = WIDTH * in_dim + (lay - 1) * WIDTH * WIDTH;
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                    for (int jb = 0; jb < NIB; jb++) flush(gw_hid[li][ib][jb], base, WIDTH, ib, jb, WIDTH, WIDTH);
-            }
-            const uint32_t base = WIDTH * in_dim + (num_layers - 1) * WIDTH * WIDTH;
-#pragma unroll
-            for (int jb = 0; jb < NIB; jb++) flush(gw_out[jb], base, WIDTH, 0, jb, 16, WIDTH);
-        }
+        if (wid == turn) each(serial);
         __syncthreads();
     }
-    if (grad_weights_direct) {
-        for (uint32_t i = threadIdx.x; i < n_params; i += FF_THREADS) grad_weights_direct[i] = (half_t)red[i];
-    } else {
-        float* slab = slabs + (size_t)blockIdx.x * n_params;
-        for (uint32_t i = threadIdx.x; i < n_params; i += FF_THREADS) slab[i] = red[i];
-    }
+    slab_serial_store<FF_THREADS>(red, n_params, slabs, grad_weights_direct);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1334,32 +1371,12 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
         }
     };
     float* red = reinterpret_cast<float*>(smem);
-    const uint32_t n_params = ff_param_count(in_dim, WIDTH, num_layers);
-    // (round 4) the sixteen partial sums of a block are READ together, then added and written: written as `red[..] += a[r]` the compiler
-    // has to order every read behind the previous write (it cannot see that the sixteen addresses differ), and the epilogue became
-    // sixteen dependent LDS round trips per block and wave -- with one wave flushing at a time, ~20 of the kernel's 47 us.
-    auto flush = [&](const float16_t& a, uint32_t base, uint32_t ld, int ib, int jb, uint32_t rws, uint32_t cols) {
-        float t[16];
-        const uint32_t i = 32 * jb + n;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const uint32_t o = (uint32_t)acc_row(ib, h, r);
-            t[r] = (o < rws && i < cols) ? red[base + o * ld + i] : 0.0f;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const uint32_t o = (uint32_t)acc_row(ib, h, r);
-            if (o < rws && i < cols) red[base + o * ld + i] = t[r] + a[r];
-        }
-    };
-    auto begin_reduction = [&]() {
-        __syncthreads();  // every wave is done with the weight image and the stages
-        for (uint32_t i = threadIdx.x; i < n_params; i += FP_THREADS) red[i] = 0.0f;
-        __syncthreads();
-    };
-    const uint32_t base_out = WIDTH * in_dim + (num_layers - 1) * WIDTH * WIDTH;
-    const uint32_t base_top = WIDTH * in_dim + (num_layers - 2) * WIDTH * WIDTH;  // hidden matmul into the last hidden layer
-    const uint32_t base_low = WIDTH * in_dim;                                     // (NHM == 2) hidden matmul into hidden layer 1
+    const SlabLayout lay{WIDTH, in_dim, num_layers};
+    const uint32_t n_params = lay.n_params();
+    const uint32_t base_out = lay.out();
+    const uint32_t base_top = lay.hidden(num_layers - 1);  // hidden matmul into the last hidden layer
+    const uint32_t base_low = lay.hidden(1);               // (NHM == 2) hidden matmul into hidden layer 1
+    const SlabSerial serial{red, n, h};
     // the staged sum (slab_sum_pass): the pairs are the copies.  Four copies of the whole slab in one pass where they fit the LDS; else everything
     // behind the input layer's matrix first -- both roles stage at once --, then that matrix, which only role 1 holds
     constexpr bool whole = slab_fits_whole<WIDTH, IN_JB, NHM>;
@@ -1410,46 +1427,34 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
                         for (int jb = 0; jb < NIB; jb++) gw_out[jb] = mfma(yT[g], aT[jb][g], gw_out[jb]);
                 }
                 float16_t acc[NIB];
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++) acc[ib] = mfma(img_out[ib * 64], dy, zero16());
+                dgrad_out<WIDTH>(img_out, dy, acc);
                 half8_t dz[NKB];
                 activation_transfer<WIDTH, RELU>(act, acc, a_top, dz);
                 transpose_hidden<WIDTH>(dz, sel, zT);
                 transpose_hidden<WIDTH>(a_below, sel, aT);
-#pragma unroll
-                for (int g = 0; g < 2; g++)
-#pragma unroll
-                    for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                        for (int jb = 0; jb < NIB; jb++) gw_top[ib][jb] = mfma(zT[ib][g], aT[jb][g], gw_top[ib][jb]);
+                wgrad_blocks(zT, aT, gw_top);
             }
             end_of_round(base);
         }
+        auto each = [&](const auto& sink) {
+#pragma unroll
+            for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                for (int jb = 0; jb < NIB; jb++) sink.put(gw_top[ib][jb], base_top, WIDTH, ib, jb, WIDTH, WIDTH);
+#pragma unroll
+            for (int jb = 0; jb < NIB; jb++) sink.put(gw_out[jb], base_out, WIDTH, 0, jb, 16, WIDTH);
+        };
         if (slab_staged_paired<WIDTH, IN_JB, NHM> && !serial_flush) {
-            pass(part_a, [&](const SlabCopy& c) {
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                    for (int jb = 0; jb < NIB; jb++) c.put(gw_top[ib][jb], base_top, WIDTH, ib, jb, WIDTH, WIDTH);
-#pragma unroll
-                for (int jb = 0; jb < NIB; jb++) c.put(gw_out[jb], base_out, WIDTH, 0, jb, 16, WIDTH);
-            });
+            pass(part_a, each);
             if constexpr (!whole) pass(part_b, [](const SlabCopy&) {});
             return;
         }
         // the reference form (NGP_FF_SERIAL_FLUSH):
-        begin_reduction();
+        slab_serial_begin<FP_THREADS>(red, n_params);
         // the waves of a role add into the same entries, one after the other (a fixed order: deterministic); the two roles own disjoint
         // parts of the slab and take their turns at the same time
         for (int turn = 0; turn < FP_PAIRS; turn++) {
-            if (pair == turn) {
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                    for (int jb = 0; jb < NIB; jb++) flush(gw_top[ib][jb], base_top, WIDTH, ib, jb, WIDTH, WIDTH);
-#pragma unroll
-                for (int jb = 0; jb < NIB; jb++) flush(gw_out[jb], base_out, WIDTH, 0, jb, 16, WIDTH);
-            }
+            if (pair == turn) each(serial);
             __syncthreads();
         }
     } else {
@@ -1492,32 +1497,21 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
                     for (int kb = 0; kb < NKB; kb++) a_prev[kb] = afrag[(NHM * NKB + kb) * 64];
                 }
                 float16_t acc[NIB];
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++) acc[ib] = mfma(img_out[ib * 64], dy, zero16());
+                dgrad_out<WIDTH>(img_out, dy, acc);
                 half8_t dz[NKB];
                 half8_t aT[NIB][2], zT[NIB][2];
                 // top hidden matmul: dgrad only (its dW belongs to role 0)
                 activation_transfer<WIDTH, RELU>(act, acc, a_prev, dz);
 #pragma unroll
                 for (int kb = 0; kb < NKB; kb++) a_prev[kb] = afrag[((NHM - 1) * NKB + kb) * 64];
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++) {
-                    acc[ib] = zero16();
-#pragma unroll
-                    for (int kb = 0; kb < NKB; kb++) acc[ib] = mfma(img_hid[(ib * NKB + kb) * 64], dz[kb], acc[ib]);
-                }
+                dgrad_hidden<WIDTH>(img_hid, dz, acc);
                 if constexpr (NHM == 2) {  // lower hidden matmul: dW and dgrad
                     activation_transfer<WIDTH, RELU>(act, acc, a_prev, dz);
 #pragma unroll
                     for (int kb = 0; kb < NKB; kb++) a_prev[kb] = afrag[kb * 64];
                     transpose_hidden<WIDTH>(dz, sel, zT);
                     transpose_hidden<WIDTH>(a_prev, sel, aT);
-#pragma unroll
-                    for (int g = 0; g < 2; g++)
-#pragma unroll
-                        for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                            for (int jb = 0; jb < NIB; jb++) gw_low[ib][jb] = mfma(zT[ib][g], aT[jb][g], gw_low[ib][jb]);
+                    wgrad_blocks(zT, aT, gw_low);
                     const half8_t* wl = img_hid + (size_t)NIB * NKB * 64;
 #pragma unroll
                     for (int ib = 0; ib < NIB; ib++) {
@@ -1573,74 +1567,43 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
                         *reinterpret_cast<half4_t*>(grow + 8) = b;
                     }
                 } else if (with_dx) {
-#pragma unroll
-                    for (int ib = 0; ib < IN_JB; ib++) {
-                        float16_t dx = zero16();
-#pragma unroll
-                        for (int kb = 0; kb < NKB; kb++) dx = mfma(img_in[(ib * NKB + kb) * 64], dz[kb], dx);
-                        const size_t srow = (size_t)tile * FF_TILE + n;
-                        half_t* grow = grad_inputs + srow * in_dim;
-#pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            const uint32_t f0 = 32 * ib + 8 * q + 4 * h;
-                            if (f0 < in_dim) {
-                                if (dx_planar) {
-                                    const half2_t lo = {(half_t)dx[4 * q], (half_t)dx[4 * q + 1]}, hi = {(half_t)dx[4 * q + 2], (half_t)dx[4 * q + 3]};
-                                    *reinterpret_cast<half2_t*>(grad_inputs + ((size_t)(f0 / 2) * rows + srow) * 2) = lo;
-                                    *reinterpret_cast<half2_t*>(grad_inputs + ((size_t)(f0 / 2 + 1) * rows + srow) * 2) = hi;
-                                } else {
-                                    half4_t v = {(half_t)dx[4 * q], (half_t)dx[4 * q + 1], (half_t)dx[4 * q + 2], (half_t)dx[4 * q + 3]};
-                                    *reinterpret_cast<half4_t*>(grow + f0) = v;
-                                }
-                            }
-                        }
-                    }
+                    store_dx<WIDTH, IN_JB>(img_in, dz, grad_inputs, tile, n, h, in_dim, rows, dx_planar);
                 }
             }
             end_of_round(base);
         }
-        if (slab_staged_paired<WIDTH, IN_JB, NHM> && !serial_flush) {
-            auto put_in = [&](const SlabCopy& c) {
+        auto each_in = [&](const auto& sink) {
+#pragma unroll
+            for (int ib = 0; ib < NIB; ib++)
+#pragma unroll
+                for (int jb = 0; jb < IN_JB; jb++) sink.put(gw_in[ib][jb], lay.in(), in_dim, ib, jb, WIDTH, in_dim);
+        };
+        auto each_low = [&](const auto& sink) {
+            if constexpr (NHM == 2) {
 #pragma unroll
                 for (int ib = 0; ib < NIB; ib++)
 #pragma unroll
-                    for (int jb = 0; jb < IN_JB; jb++) c.put(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
-            };
+                    for (int jb = 0; jb < NIB; jb++) sink.put(gw_low[ib][jb], base_low, WIDTH, ib, jb, WIDTH, WIDTH);
+            }
+        };
+        if (slab_staged_paired<WIDTH, IN_JB, NHM> && !serial_flush) {
             pass(part_a, [&](const SlabCopy& c) {
-                if constexpr (whole) put_in(c);
-                if constexpr (NHM == 2) {
-#pragma unroll
-                    for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                        for (int jb = 0; jb < NIB; jb++) c.put(gw_low[ib][jb], base_low, WIDTH, ib, jb, WIDTH, WIDTH);
-                }
+                if constexpr (whole) each_in(c);
+                each_low(c);
             });
-            if constexpr (!whole) pass(part_b, put_in);
+            if constexpr (!whole) pass(part_b, each_in);
             return;
         }
-        begin_reduction();
+        slab_serial_begin<FP_THREADS>(red, n_params);
         for (int turn = 0; turn < FP_PAIRS; turn++) {
             if (pair == turn) {
-#pragma unroll
-                for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                    for (int jb = 0; jb < IN_JB; jb++) flush(gw_in[ib][jb], 0, in_dim, ib, jb, WIDTH, in_dim);
-                if constexpr (NHM == 2) {
-#pragma unroll
-                    for (int ib = 0; ib < NIB; ib++)
-#pragma unroll
-                        for (int jb = 0; jb < NIB; jb++) flush(gw_low[ib][jb], base_low, WIDTH, ib, jb, WIDTH, WIDTH);
-                }
+                each_in(serial);
+                each_low(serial);
             }
             __syncthreads();
         }
     }
-    if (grad_weights_direct) {
-        for (uint32_t i = threadIdx.x; i < n_params; i += FP_THREADS) grad_weights_direct[i] = (half_t)red[i];
-    } else {
-        float* slab = slabs + (size_t)blockIdx.x * n_params;
-        for (uint32_t i = threadIdx.x; i < n_params; i += FP_THREADS) slab[i] = red[i];
-    }
+    slab_serial_store<FP_THREADS>(red, n_params, slabs, grad_weights_direct);
 }
 
 
@@ -1654,7 +1617,7 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
 // layer, exactly what the reference keeps there).  A wave re-reads only fragments it wrote itself, a __threadfence() between passes
 // orders them.  The weight gradients are their own kernel (k_ffmlp_wgrad): one workgroup per (matmul, 32-row block, 8 column
 // blocks, sample chunk), operands transposed on the matrix core as in the fast kernel, per-chunk fp32 slabs in a caller-provided
-// workspace summed in a fixed order (k_ffmlp_reduce_slabs) -- or, without a workspace, one chunk and a direct store.  Deterministic.
+// workspace summed in a fixed order (reduce_slabs) -- or, without a workspace, one chunk and a direct store.  Deterministic.
 // ------------------------------------------------------------------------------------------------
 template <int WIDTH>
 __device__ __forceinline__ void fwd_matmul_range(uint32_t m, uint32_t in_dim, uint32_t num_layers, uint32_t& first, uint32_t& count) {
@@ -1920,30 +1883,11 @@ __global__ __launch_bounds__(FF_THREADS) void k_ffmlp_wgrad(const half_t* __rest
     }
 }
 
-// sum the per-workgroup slabs in a fixed order and round once to fp16.
-// One workgroup = 64 consecutive parameters x 16 slab groups: thread (g, i) adds slabs g, g+16, g+32, ... of parameter i
-// (coalesced 256-byte rows), the 16 partial sums are combined in LDS in ascending g -- a fixed summation tree, so the
-// result is bit-reproducible -- and rounded once.
-__global__ __launch_bounds__(RS_PARAMS * RS_GROUPS) void k_ffmlp_reduce_slabs(const float* __restrict__ slabs, uint32_t n_slabs,
-                                                                               uint32_t n_params, half_t* __restrict__ grad_weights) {
-    __shared__ float part[RS_GROUPS][RS_PARAMS];
-    const uint32_t li = threadIdx.x & (RS_PARAMS - 1), g = threadIdx.x / RS_PARAMS;
-    const uint32_t i = blockIdx.x * RS_PARAMS + li;
-    float s = 0.0f;
-    if (i < n_params)
-        for (uint32_t k = g; k < n_slabs; k += RS_GROUPS) s += slabs[(size_t)k * n_params + i];
-    part[g][li] = s;
-    __syncthreads();
-    if (g == 0 && i < n_params) {
-        float t = 0.0f;
-#pragma unroll
-        for (int q = 0; q < RS_GROUPS; q++) t += part[q][li];
-        grad_weights[i] = (half_t)t;
-    }
-}
-
-// the same for TWO slab sets in one launch (the two MLPs of the fused network): workgroups [0, blocks_a) take set a, the rest set b
-// (common.h: slab_reduce_block -- shared with the grid encoder's slice accumulate, which can carry these blocks in its own grid)
+// Sum the per-workgroup slabs in a fixed order and round once to fp16 (common.h: slab_reduce_block -- shared with the grid encoder's slice
+// accumulate, which can carry these blocks in its own grid).  One workgroup = 64 consecutive parameters x 16 slab groups: thread (g, i) adds
+// slabs g, g+16, g+32, ... of parameter i (coalesced 256-byte rows), the 16 partial sums are combined in LDS in ascending g -- a fixed
+// summation tree, so the result is bit-reproducible -- and rounded once.  Up to TWO slab sets per launch (the two MLPs of the fused network):
+// workgroups [0, blocks_a) take set a, the rest set b.
 __global__ __launch_bounds__(RS_PARAMS * RS_GROUPS) void k_ffmlp_reduce_slabs_pair(SlabSets sets, float* __restrict__ found_inf) {
     __shared__ float part[RS_GROUPS][RS_PARAMS];
     slab_reduce_block(sets, blockIdx.x, part, found_inf);
@@ -1991,10 +1935,17 @@ static int raise_lds(const void* kern, size_t lds, const char* what) {
     return NGP_OK;
 }
 
+// one backward's own reduction: its n_slabs slabs as a one-set launch of the pair kernel, no found_inf sweep
+static int reduce_slabs(const void* slabs, uint32_t n_slabs, uint32_t n_params, void* grad_weights, hipStream_t st, const char* what) {
+    SlabSets sets = {};
+    const uint32_t blocks = slab_set(sets, 0, slabs, n_slabs, n_params, grad_weights, false);
+    hipLaunchKernelGGL(k_ffmlp_reduce_slabs_pair, dim3(blocks), dim3(RS_PARAMS * RS_GROUPS), 0, st, sets, (float*)nullptr);
+    return check_launch(what);
+}
+
 template <int WIDTH>
 static size_t forward_image_bytes(uint32_t in_dim, uint32_t num_layers) {
-    constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
-    return (size_t)(NIB * (in_dim / 16) + (num_layers - 1) * NIB * NKB + NKB) * 1024;
+    return (size_t)fwd_frag_count<WIDTH>(in_dim, num_layers) * 1024;
 }
 
 // layered forward: one matmul image at a time (any width / depth whose single largest matmul fits the LDS)
@@ -2112,15 +2063,22 @@ static int launch_backward_layered(const void* grad, const void* inputs, const v
                        direct ? (half_t*)grad_weights : (half_t*)nullptr);
     rc = check_launch("ffmlp_backward(wgrad)");
     if (rc || direct) return rc;
-    hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st, (const float*)workspace, chunks,
-                       n_params, (half_t*)grad_weights);
-    return check_launch("ffmlp_backward(reduce)");
+    return reduce_slabs(workspace, chunks, n_params, grad_weights, st, "ffmlp_backward(reduce)");
+}
+
+// the shapes the register-resident backward kernels serve (everything else: the layered kernels), and those among them whose backward can leave
+// slabs for a deferred reduction (the paired kernel: 2 or 3 layers)
+static bool ff_register_resident(uint32_t in_dim, uint32_t hidden, uint32_t num_layers) {
+    return (hidden == 32 || hidden == 64) && num_layers <= 4 && in_dim <= 64;
+}
+static bool ff_leaves_slabs(uint32_t in_dim, uint32_t hidden, uint32_t num_layers) {
+    return ff_register_resident(in_dim, hidden, num_layers) && num_layers >= 2 && num_layers <= 3;
 }
 
 // workgroups of the register-resident backward = fp32 weight-gradient slabs it leaves in backward_buffer ([num_layers, B, hidden] fp16)
 template <int WIDTH>
 static uint32_t backward_slab_count(uint32_t B, uint32_t in_dim, uint32_t num_layers) {
-    const uint32_t n_params = ff_param_count(in_dim, WIDTH, num_layers);
+    const uint32_t n_params = SlabLayout{WIDTH, in_dim, num_layers}.n_params();
     const size_t buf_bytes = (size_t)num_layers * B * WIDTH * sizeof(half_t);
     uint32_t blocks = (uint32_t)device_info().cus;
     const uint32_t need = cdiv(B / FF_TILE, FF_WAVES);
@@ -2130,61 +2088,85 @@ static uint32_t backward_slab_count(uint32_t B, uint32_t in_dim, uint32_t num_la
     return blocks;
 }
 
+// The LDS of a register-resident backward launch: the weight image(s), the tile buffers behind it, and -- in the same bytes, once the tile
+// loop is over -- the epilogue's copies of the slab (slab_sum_pass: four of the slab or of its largest part; the serial form: one).
+struct BackwardLds {
+    size_t image, tile;   // bytes of the weight image (recompute: backward + forward image) and of one tile buffer
+    uint32_t pf_depth;    // tile buffers per wave (per pair)
+    size_t stage, total;
+};
+template <int WIDTH, int IN_JB, int NHM>
+static BackwardLds backward_lds_plan(uint32_t in_dim, uint32_t num_layers, bool with_dx, uint32_t flags, bool recompute) {
+    constexpr int NKB = Shape<WIDTH>::NKB;
+    static_assert(FF_WAVES == FP_PAIRS, "one tile stream per wave or per pair: the same number of tile buffers");
+    const SlabLayout lay{WIDTH, in_dim, num_layers};
+    BackwardLds p;
+    const uint32_t nfrag = bwd_frag_count<WIDTH>(in_dim, num_layers, with_dx);
+    size_t scratch = 0;
+    if (recompute) {
+        // the forward image without its output layer behind the backward image; tiles carry dY and X only (3 KiB: three deep); role 1 parks
+        // the recomputed activations in a scratch of its own
+        p.image = (size_t)(nfrag + fwd_frag_count<WIDTH>(in_dim, num_layers) - NKB) * 1024;
+        p.tile = (size_t)(1 + in_dim / 16) * 1024;
+        p.pf_depth = 3;
+        scratch = (size_t)FP_PAIRS * NHM * NKB * 1024;
+    } else {
+        // double-buffered when both fit the 160 KiB LDS of a CU
+        // (three tile buffers for the two-layer networks, which would fit: measured SLOWER, sigma-net backward 32.6 -> 34.1 us; the kernel's wait
+        // counts cover the shapes should that change)
+        p.image = (size_t)nfrag * 1024;
+        p.tile = (size_t)(1 + num_layers * NKB + in_dim / 16) * 1024;
+        p.pf_depth = p.image + 2 * FF_WAVES * p.tile > 160 * 1024 ? 1 : 2;
+    }
+    const bool paired = (NHM == 1 || NHM == 2) && !(flags & NGP_FF_SINGLE_WAVE);
+    const bool staged = !(flags & NGP_FF_SERIAL_FLUSH) && (paired ? slab_staged_paired<WIDTH, IN_JB, NHM> : slab_staged_single<WIDTH, IN_JB, NHM>);
+    p.stage = staged ? slab_stage_bytes(slab_fits_whole<WIDTH, IN_JB, NHM>, lay) : 0;
+    p.total = p.image + (size_t)p.pf_depth * FF_WAVES * p.tile + scratch;
+    if (p.total < (size_t)lay.n_params() * 4) p.total = (size_t)lay.n_params() * 4;
+    if (p.total < p.stage) p.total = p.stage;
+    return p;
+}
+
+// One launch of a register-resident backward kernel and what follows it.  launch(grid, slabs, direct) starts `kern`: one workgroup stores the
+// fp16 gradients itself (slabs NULL), several leave one fp32 slab each in the caller's backward_buffer ([num_layers, B, hidden] fp16) -- summed
+// here, or by the caller when deferred (ngp_ffmlp_reduce_slabs_pair, or carried by the grid backward).
+template <typename Launch>
+static int launch_and_reduce(const void* kern, size_t lds, uint32_t blocks, bool defer, void* backward_buffer, void* grad_weights, uint32_t n_params,
+                             hipStream_t st, Launch&& launch) {
+    int rc = raise_lds(kern, lds, "ffmlp_backward");
+    if (rc) return rc;
+    const bool direct = blocks <= 1;
+    launch(dim3(direct ? 1 : blocks), direct ? (float*)nullptr : (float*)backward_buffer, direct ? (half_t*)grad_weights : (half_t*)nullptr);
+    rc = check_launch("ffmlp_backward");
+    if (rc || direct || defer) return rc;
+    return reduce_slabs(backward_buffer, blocks, n_params, grad_weights, st, "ffmlp_backward(reduce)");
+}
+
 template <int WIDTH, int IN_JB, int NHM, bool RELU>
 static int launch_backward_t(const void* grad, const void* inputs, const void* weights, const void* fwd, uint32_t B, uint32_t in_dim,
                            uint32_t num_layers, uint32_t act, bool with_dx, void* backward_buffer, void* grad_inputs,
                            void* grad_weights, uint32_t flags, hipStream_t st, const MidEpilogue* mid_in) {
     const bool in_planar = (flags & NGP_FF_INPUT_PLANAR) != 0, dx_planar = (flags & NGP_FF_DX_PLANAR) != 0;
-    const bool defer = (flags & NGP_FF_DEFER_REDUCE) != 0;
+    const bool defer = (flags & NGP_FF_DEFER_REDUCE) != 0, serial = (flags & NGP_FF_SERIAL_FLUSH) != 0;
     const MidEpilogue mid = mid_in ? *mid_in : MidEpilogue{nullptr, nullptr, nullptr, 0.0f};
-    constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     const uint32_t n_tiles = B / FF_TILE;
-    const uint32_t nfrag = NIB + (num_layers - 1) * NIB * NKB + (with_dx ? ((in_dim + 31) / 32) * NKB : 0);
-    const uint32_t n_params = ff_param_count(in_dim, WIDTH, num_layers);
-    // weight image + per-wave tile buffers (double-buffered when both fit the 160 KiB LDS of a CU)
-    const size_t tile_bytes = (size_t)(1 + num_layers * NKB + in_dim / 16) * 1024;
-    uint32_t pf_depth = 2;
-    if ((size_t)nfrag * 1024 + 2 * FF_WAVES * tile_bytes > 160 * 1024) pf_depth = 1;
-    // (three tile buffers for the two-layer networks, which would fit: measured SLOWER, sigma-net backward 32.6 -> 34.1 us; the kernel's wait
-    // counts cover the shapes should that change -- the recomputing variant, whose tiles are 3 KiB, does run three deep)
-    size_t lds = (size_t)nfrag * 1024 + (size_t)pf_depth * FF_WAVES * tile_bytes;
-    if (lds < (size_t)n_params * 4) lds = (size_t)n_params * 4;
-    // the epilogue stages the waves' accumulators in the same LDS (slab_sum_pass): four copies of the slab, or of its largest part
-    const bool serial = (flags & NGP_FF_SERIAL_FLUSH) != 0;
-    const bool paired = (NHM == 1 || NHM == 2) && !(flags & NGP_FF_SINGLE_WAVE);
-    constexpr bool whole = slab_fits_whole<WIDTH, IN_JB, NHM>;
-    const bool staged = !serial && (paired ? slab_staged_paired<WIDTH, IN_JB, NHM> : slab_staged_single<WIDTH, IN_JB, NHM>);
-    const size_t stage = staged ? slab_stage_bytes(whole, n_params, WIDTH * in_dim) : 0;
-    if (lds < stage) lds = stage;
-    NGP_REQUIRE(lds <= 160 * 1024, NGP_ERR_INVALID, "ffmlp_backward: LDS need (%zu B) exceeds 160 KiB", lds);
-    // one fp32 slab per workgroup lives in the caller's backward_buffer ([num_layers, B, hidden] fp16)
+    const uint32_t n_params = SlabLayout{WIDTH, in_dim, num_layers}.n_params();
+    const BackwardLds lds = backward_lds_plan<WIDTH, IN_JB, NHM>(in_dim, num_layers, with_dx, flags, false);
+    NGP_REQUIRE(lds.total <= 160 * 1024, NGP_ERR_INVALID, "ffmlp_backward: LDS need (%zu B) exceeds 160 KiB", lds.total);
     const uint32_t blocks = backward_slab_count<WIDTH>(B, in_dim, num_layers);
+    const half_t *g = (const half_t*)grad, *x = (const half_t*)inputs, *w = (const half_t*)weights;
     if (flags & NGP_FF_RECOMPUTE) {
         // no stored activations: the paired kernel recomputes them from the inputs (64-wide ReLU networks with 32 inputs, 2 or 3 layers)
         if constexpr (WIDTH == 64 && IN_JB == 1 && RELU && (NHM == 1 || NHM == 2)) {
             NGP_REQUIRE(in_dim == 32 && !(flags & NGP_FF_SINGLE_WAVE), NGP_ERR_INVALID, "ffmlp_backward: NGP_FF_RECOMPUTE needs input_dim 32 and the paired kernel");
-            const uint32_t ffrag = NIB * (in_dim / 16) + (num_layers - 1) * NIB * NKB;
-            const size_t tile_b = (size_t)(1 + in_dim / 16) * 1024;
-            const uint32_t depth = 3;
-            size_t lds_r = (size_t)(nfrag + ffrag) * 1024 + (size_t)depth * FP_PAIRS * tile_b + (size_t)FP_PAIRS * NHM * NKB * 1024;
-            if (lds_r < (size_t)n_params * 4) lds_r = (size_t)n_params * 4;
-            if (lds_r < stage) lds_r = stage;
-            NGP_REQUIRE(lds_r <= 160 * 1024, NGP_ERR_INVALID, "ffmlp_backward: LDS need (%zu B) exceeds 160 KiB", lds_r);
+            const BackwardLds lds_r = backward_lds_plan<WIDTH, IN_JB, NHM>(in_dim, num_layers, with_dx, flags, true);
+            NGP_REQUIRE(lds_r.total <= 160 * 1024, NGP_ERR_INVALID, "ffmlp_backward: LDS need (%zu B) exceeds 160 KiB", lds_r.total);
             auto pk = k_ffmlp_backward_paired<WIDTH, IN_JB, NHM, RELU, true>;
-            if (lds_r > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-                NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp_backward: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-            }
-            const bool direct = blocks <= 1;
-            hipLaunchKernelGGL(pk, dim3(direct ? 1 : blocks), dim3(FP_THREADS), lds_r, st, (const half_t*)grad, (const half_t*)inputs,
-                               (const half_t*)weights, (const half_t*)nullptr, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs,
-                               direct ? (float*)nullptr : (float*)backward_buffer, direct ? (half_t*)grad_weights : (half_t*)nullptr, in_planar,
-                               dx_planar, depth, mid, (uint32_t)lds_r, serial);
-            int rc = check_launch("ffmlp_backward");
-            if (rc || direct || defer) return rc;
-            hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st,
-                               (const float*)backward_buffer, blocks, n_params, (half_t*)grad_weights);
-            return check_launch("ffmlp_backward(reduce)");
+            return launch_and_reduce(reinterpret_cast<const void*>(pk), lds_r.total, blocks, defer, backward_buffer, grad_weights, n_params, st,
+                                     [&](dim3 grid, float* slabs, half_t* direct) {
+                hipLaunchKernelGGL(pk, grid, dim3(FP_THREADS), lds_r.total, st, g, x, w, (const half_t*)nullptr, n_tiles, in_dim, num_layers, act, with_dx,
+                                   (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds_r.pf_depth, mid, (uint32_t)lds_r.total, serial);
+            });
         } else {
             NGP_REQUIRE(false, NGP_ERR_INVALID, "ffmlp_backward: NGP_FF_RECOMPUTE serves 64-wide ReLU networks with 32 inputs and 2 or 3 layers");
         }
@@ -2193,42 +2175,20 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
         // 2- and 3-layer networks: two sibling waves per tile stream split the weight-gradient accumulators (see the kernel)
         if (!(flags & NGP_FF_SINGLE_WAVE)) {
             auto pk = k_ffmlp_backward_paired<WIDTH, IN_JB, NHM, RELU>;
-            if (lds > 64 * 1024) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp_backward: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-            }
-            const bool direct = blocks <= 1;
-            hipLaunchKernelGGL(pk, dim3(direct ? 1 : blocks), dim3(FP_THREADS), lds, st, (const half_t*)grad, (const half_t*)inputs,
-                               (const half_t*)weights, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs,
-                               direct ? (float*)nullptr : (float*)backward_buffer, direct ? (half_t*)grad_weights : (half_t*)nullptr, in_planar,
-                               dx_planar, pf_depth, mid, (uint32_t)lds, serial);
-            int rc = check_launch("ffmlp_backward");
-            if (rc || direct || defer) return rc;  // deferred: the caller sums the slabs (ngp_ffmlp_reduce_slabs_pair)
-            hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st,
-                               (const float*)backward_buffer, blocks, n_params, (half_t*)grad_weights);
-            return check_launch("ffmlp_backward(reduce)");
+            return launch_and_reduce(reinterpret_cast<const void*>(pk), lds.total, blocks, defer, backward_buffer, grad_weights, n_params, st,
+                                     [&](dim3 grid, float* slabs, half_t* direct) {
+                hipLaunchKernelGGL(pk, grid, dim3(FP_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
+                                   (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds.pf_depth, mid, (uint32_t)lds.total, serial);
+            });
         }
     }
     NGP_REQUIRE(!mid.grad_sigma && !defer, NGP_ERR_INVALID, "ffmlp_backward: this extension needs the paired kernel (2 or 3 layers)");
     auto kern = k_ffmlp_backward<WIDTH, IN_JB, NHM, RELU>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp_backward: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
-    }
-    if (blocks <= 1) {
-        hipLaunchKernelGGL(kern, dim3(1), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)inputs, (const half_t*)weights,
-                           (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs, (float*)nullptr,
-                           (half_t*)grad_weights, in_planar, dx_planar, pf_depth, (uint32_t)lds, serial);
-        return check_launch("ffmlp_backward");
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)inputs, (const half_t*)weights,
-                       (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs, (float*)backward_buffer,
-                       (half_t*)nullptr, in_planar, dx_planar, pf_depth, (uint32_t)lds, serial);
-    int rc = check_launch("ffmlp_backward");
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st, (const float*)backward_buffer, blocks, n_params,
-                       (half_t*)grad_weights);
-    return check_launch("ffmlp_backward(reduce)");
+    return launch_and_reduce(reinterpret_cast<const void*>(kern), lds.total, blocks, false, backward_buffer, grad_weights, n_params, st,
+                             [&](dim3 grid, float* slabs, half_t* direct) {
+        hipLaunchKernelGGL(kern, grid, dim3(FF_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
+                           (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds.pf_depth, (uint32_t)lds.total, serial);
+    });
 }
 
 template <int WIDTH, int IN_JB, int NHM>
@@ -2284,9 +2244,8 @@ extern "C" int ngp_ffmlp_inference_ex(const void* inputs, const void* weights, u
 }
 
 extern "C" size_t ngp_ffmlp_backward_workspace_bytes(uint32_t B, uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    const bool fast = (hidden_dim == 32 || hidden_dim == 64) && num_layers <= 4 && input_dim <= 64;
-    if (fast || B == 0) return 0;
-    return (size_t)WG_MAX_CHUNKS * ff_param_count(input_dim, hidden_dim, num_layers) * sizeof(float);
+    if (ff_register_resident(input_dim, hidden_dim, num_layers) || B == 0) return 0;
+    return (size_t)WG_MAX_CHUNKS * SlabLayout{hidden_dim, input_dim, num_layers}.n_params() * sizeof(float);
 }
 
 extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, uint32_t B,
@@ -2311,7 +2270,7 @@ extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const
     NGP_REQUIRE(!calc_grad_inputs || grad_inputs, NGP_ERR_INVALID, "ffmlp_backward: grad_inputs is NULL but calc_grad_inputs is set");
     hipStream_t st = as_stream(stream);
     const bool dx = calc_grad_inputs != 0;
-    const bool fast = (hidden_dim == 32 || hidden_dim == 64) && num_layers <= 4 && input_dim <= 64 && !(flags & NGP_FF_LAYERED);
+    const bool fast = ff_register_resident(input_dim, hidden_dim, num_layers) && !(flags & NGP_FF_LAYERED);
     NGP_REQUIRE(fast || !(flags & NGP_FF_RECOMPUTE), NGP_ERR_INVALID, "ffmlp_backward: NGP_FF_RECOMPUTE serves 64-wide ReLU networks with 32 inputs and 2 or 3 layers");
     NGP_REQUIRE(fast || !(flags & NGP_FF_DEFER_REDUCE), NGP_ERR_INVALID, "ffmlp_backward: NGP_FF_DEFER_REDUCE needs a 2- or 3-layer network of width 32 / 64");
     if (!fast) {
@@ -2348,7 +2307,7 @@ extern "C" int ngp_ffmlp_backward_ex(const void* grad, const void* inputs, const
 
 
 extern "C" uint32_t ngp_ffmlp_backward_slab_count(uint32_t B, uint32_t input_dim, uint32_t hidden_dim, uint32_t num_layers) {
-    if ((hidden_dim != 32 && hidden_dim != 64) || num_layers < 2 || num_layers > 3 || input_dim > 64 || B == 0) return 0;
+    if (!ff_leaves_slabs(input_dim, hidden_dim, num_layers) || B == 0) return 0;
     const uint32_t blocks = hidden_dim == 64 ? backward_slab_count<64>(B, input_dim, num_layers) : backward_slab_count<32>(B, input_dim, num_layers);
     return blocks <= 1 ? 0u : blocks;  // one workgroup stores the gradients directly: nothing left to sum
 }
@@ -2356,16 +2315,12 @@ extern "C" uint32_t ngp_ffmlp_backward_slab_count(uint32_t B, uint32_t input_dim
 extern "C" int ngp_ffmlp_reduce_slabs_pair(const void* slabs_a, uint32_t n_slabs_a, uint32_t n_params_a, void* grad_weights_a,
                                            const void* slabs_b, uint32_t n_slabs_b, uint32_t n_params_b, void* grad_weights_b,
                                            float* found_inf, ngp_stream_t stream) {
-    // a set without slabs (its backward stored the gradients directly) still gets workgroups when found_inf asks for the sweep
-    const uint32_t blocks_a = (n_slabs_a || found_inf) && n_params_a ? cdiv(n_params_a, RS_PARAMS) : 0u;
-    const uint32_t blocks_b = (n_slabs_b || found_inf) && n_params_b ? cdiv(n_params_b, RS_PARAMS) : 0u;
+    SlabSets sets = {};
+    const uint32_t blocks_a = slab_set(sets, 0, slabs_a, n_slabs_a, n_params_a, grad_weights_a, found_inf != nullptr);
+    const uint32_t blocks_b = slab_set(sets, 1, slabs_b, n_slabs_b, n_params_b, grad_weights_b, found_inf != nullptr);
     if (blocks_a + blocks_b == 0) return NGP_OK;
     NGP_REQUIRE((!blocks_a || ((slabs_a || !n_slabs_a) && grad_weights_a)) && (!blocks_b || ((slabs_b || !n_slabs_b) && grad_weights_b)),
                 NGP_ERR_INVALID, "ffmlp_reduce_slabs_pair: NULL tensor");
-    SlabSets sets;
-    sets.slabs[0] = (const float*)slabs_a; sets.n_slabs[0] = n_slabs_a; sets.n_params[0] = n_params_a; sets.grad_weights[0] = (half_t*)grad_weights_a;
-    sets.slabs[1] = (const float*)slabs_b; sets.n_slabs[1] = n_slabs_b; sets.n_params[1] = n_params_b; sets.grad_weights[1] = (half_t*)grad_weights_b;
-    sets.blocks[0] = blocks_a; sets.blocks[1] = blocks_b;
     hipLaunchKernelGGL(k_ffmlp_reduce_slabs_pair, dim3(blocks_a + blocks_b), dim3(RS_PARAMS * RS_GROUPS), 0, as_stream(stream), sets, found_inf);
     return check_launch("ffmlp_reduce_slabs_pair");
 }

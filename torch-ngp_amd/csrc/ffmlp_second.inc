@@ -320,9 +320,7 @@ static int launch_backward_backward(const void* grad, const void* inputs, const 
         if ((rc = check_launch("ffmlp_backward_backward(wgrad, implicit)"))) return rc;
         n_slabs = 2 * chunks;
     }
-    hipLaunchKernelGGL(k_ffmlp_reduce_slabs, dim3(cdiv(n_params, RS_PARAMS)), dim3(RS_PARAMS * RS_GROUPS), 0, st, (const float*)slabs, n_slabs, n_params,
-                       (half_t*)grad_weights2);
-    return check_launch("ffmlp_backward_backward(reduce)");
+    return reduce_slabs(slabs, n_slabs, n_params, grad_weights2, st, "ffmlp_backward_backward(reduce)");
 }
 
 }  // namespace ngp

@@ -2238,17 +2238,12 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
     // are launched on their own -- the caller gets the reduced gradients and the loss either way
     SlabSets carried = {};
     if (slab_sets) {
-        // same rule as ngp_ffmlp_reduce_slabs_pair: a set without slabs (gradients stored directly) still gets blocks when found_inf asks for the sweep
-        const uint32_t ba = (slab_sets->n_slabs_a || found_inf) && slab_sets->n_params_a ? cdiv(slab_sets->n_params_a, (uint32_t)RS_PARAMS) : 0u;
-        const uint32_t bb = (slab_sets->n_slabs_b || found_inf) && slab_sets->n_params_b ? cdiv(slab_sets->n_params_b, (uint32_t)RS_PARAMS) : 0u;
+        const uint32_t ba = slab_set(carried, 0, slab_sets->slabs_a, slab_sets->n_slabs_a, slab_sets->n_params_a, slab_sets->grad_weights_a, found_inf != nullptr);
+        const uint32_t bb = slab_set(carried, 1, slab_sets->slabs_b, slab_sets->n_slabs_b, slab_sets->n_params_b, slab_sets->grad_weights_b, found_inf != nullptr);
         NGP_REQUIRE((!ba || ((slab_sets->slabs_a || !slab_sets->n_slabs_a) && slab_sets->grad_weights_a)) &&
                         (!bb || ((slab_sets->slabs_b || !slab_sets->n_slabs_b) && slab_sets->grad_weights_b)),
                     NGP_ERR_INVALID, "grid_encode_backward: NULL tensor in the slab sets");
         NGP_REQUIRE(!slab_sets->loss || (slab_sets->ray_err && slab_sets->n_rays > 0), NGP_ERR_INVALID, "grid_encode_backward: loss sum without per-ray errors");
-        carried.slabs[0] = (const float*)slab_sets->slabs_a; carried.n_slabs[0] = slab_sets->n_slabs_a; carried.n_params[0] = slab_sets->n_params_a;
-        carried.grad_weights[0] = (half_t*)slab_sets->grad_weights_a; carried.blocks[0] = ba;
-        carried.slabs[1] = (const float*)slab_sets->slabs_b; carried.n_slabs[1] = slab_sets->n_slabs_b; carried.n_params[1] = slab_sets->n_params_b;
-        carried.grad_weights[1] = (half_t*)slab_sets->grad_weights_b; carried.blocks[1] = bb;
         carried.ray_err = slab_sets->ray_err; carried.n_rays = slab_sets->n_rays; carried.loss = slab_sets->loss;
     }
     auto reduce_alone = [&]() -> int {
