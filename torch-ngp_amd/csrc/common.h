@@ -125,21 +125,22 @@ __device__ __forceinline__ void loss_sum_block(const float* err, uint32_t N, flo
 // ---- Adam + loss-scale arithmetic shared by optim.hip (k_adam, k_adam_small_commit) and the slice accumulate of the grid backward that
 // carries the table's Adam sweep in its flush (gridencoder.hip): ONE statement of the update, so the fused and the separate form produce the
 // same bits (the library is built with -ffp-contract=off).
-// state[0] = loss scale, [1] = growth tracker, [2] = found_inf, [3] = Adam step count t, [4] = lr multiplier, [5] = table parity (0 / 1: which of
-// the two buffer sets of a speculatively updated table is current, ngp_table_adam_t)
+// The optimizer's eight state words by name (the layout and what each word means: include/ngp_hip.h, ngp_optim_adam_step).
+enum OptState { OPT_SCALE, OPT_GROWTH_TRACKER, OPT_FOUND_INF, OPT_STEP_COUNT, OPT_LR_MULT, OPT_TABLE_PARITY, OPT_TICKET, OPT_SCALE_DEAD, OPT_STATE_WORDS };
+static_assert(OPT_STATE_WORDS == 8, "include/ngp_hip.h: state = device float[8]");
 struct AdamConsts {
     float inv_scale, bc1, bc2_sqrt, lr_mult;
     bool skip;  // found_inf already raised, or the loss scale is unusable (underflowed to 0 / denormal: GradScaler's 1 / scale = inf)
 };
 __device__ __forceinline__ AdamConsts adam_consts(const float* state, float beta1, float beta2, float grad_mult) {
     AdamConsts a;
-    const bool scale_dead = !__builtin_isfinite(1.0f / state[0]);
-    a.skip = state[2] != 0.0f || scale_dead;
-    a.inv_scale = scale_dead ? 0.0f : grad_mult / state[0];
-    const float t = state[3] + 1.0f;  // this step's count (the commit stores it)
+    const bool scale_dead = !__builtin_isfinite(1.0f / state[OPT_SCALE]);
+    a.skip = state[OPT_FOUND_INF] != 0.0f || scale_dead;
+    a.inv_scale = scale_dead ? 0.0f : grad_mult / state[OPT_SCALE];
+    const float t = state[OPT_STEP_COUNT] + 1.0f;  // this step's count (the commit stores it)
     a.bc1 = 1.0f - powf(beta1, t);
     a.bc2_sqrt = sqrtf(1.0f - powf(beta2, t));
-    a.lr_mult = state[4];
+    a.lr_mult = state[OPT_LR_MULT];
     return a;
 }
 // one element: g = the (already unscaled) gradient; PyTorch's Adam (amsgrad = False, weight_decay = 0)
@@ -158,6 +159,17 @@ struct TableAdam {
     const float* state;
     float lr, beta1, beta2, eps;
 };
+// host side: the caller's ngp_table_adam_t as the kernels take it.  Returns the first buffer set with a NULL buffer, -1 when both are whole.
+inline int table_adam_from(TableAdam& ta, const ngp_table_adam_t& t) {
+    for (int k = 0; k < 2; k++) {
+        if (!(t.param[k] && t.exp_avg[k] && t.exp_avg_sq[k] && t.param_fp16[k])) return k;
+        ta.p[k] = t.param[k]; ta.m[k] = t.exp_avg[k]; ta.v[k] = t.exp_avg_sq[k];
+        ta.p16[k] = reinterpret_cast<_Float16*>(t.param_fp16[k]);
+    }
+    ta.state = t.state;
+    ta.lr = t.lr; ta.beta1 = t.beta1; ta.beta2 = t.beta2; ta.eps = t.eps;
+    return -1;
+}
 // which copy of a double-buffered fp16 table a reader takes (device-side copy of the (embeddings_alt, parity) pair of the *_sel entry points)
 struct TableSel {
     const _Float16* alt;

@@ -1341,8 +1341,8 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
 // ADAM (round 6): the flush of a slice is also the table's Adam sweep for that slice (ngp_table_adam_t, include/ngp_hip.h): the final
 // gradient of 4096 entries sits in LDS, most of the chip is waiting on record walks, and the separate 28 B/parameter sweep over the whole
 // table that used to follow (k_adam: 61 us, HBM-bound) is exactly the kind of stream that fits under a latency-bound kernel.  The update is
-// speculative -- parameters / moments of buffer set state[5] are read, the OTHER set is written; the commit flips the parity only when no
-// gradient of the step was non-finite -- and uses the fp16-rounded gradient, i.e. the bits k_adam would have read from the stored table.
+// speculative -- parameters / moments of the buffer set the parity word (OPT_TABLE_PARITY) names are read, the OTHER set is written; the
+// commit flips the parity only when no gradient of the step was non-finite -- and uses the fp16-rounded gradient, i.e. the bits k_adam would have read from the stored table.
 template <int D, bool ADAM>
 __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_grid_backward_accumulate(const int32_t* __restrict__ offsets, half_t* __restrict__ grad_grid,
                                                                           BinPlan plan, const uint32_t* __restrict__ descriptors,
@@ -1397,7 +1397,7 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
         if (adam_here) {
             const uint32_t level_ = plan.level(li);
             const uint32_t off0_ = (uint32_t)offsets[level_], size_ = (uint32_t)offsets[level_ + 1] - off0_;
-            const uint32_t src = ta.state[5] != 0.0f ? 1u : 0u;
+            const uint32_t src = ta.state[OPT_TABLE_PARITY] != 0.0f ? 1u : 0u;
             const float* __restrict__ p_in = ta.p[src] + (size_t)off0_ * 2;
             const float* __restrict__ m_in = ta.m[src] + (size_t)off0_ * 2;
             const float* __restrict__ v_in = ta.v[src] + (size_t)off0_ * 2;
@@ -2195,15 +2195,24 @@ extern "C" size_t ngp_grid_backward_workspace_bytes(const int32_t* offsets_host,
     return plan_for_query(plan, offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) ? plan.workspace_bytes() : 0;
 }
 
+// The dense levels' round-robin bins leave their entries to ngp_optim_adam_small_commit: those levels must form a prefix of the binned levels.
+// true: k = the number of leading interleaved levels; false: k = the first binned level that breaks the rule (a dense level behind a hashed one)
+static bool dense_level_prefix(const BackwardPlan& plan, uint32_t& k) {
+    uint32_t lead = 0;
+    while (lead < plan.n_binned && plan.bins.interleaved(lead)) lead++;
+    for (k = lead; k < plan.n_binned; k++)
+        if (plan.bins.interleaved(k)) return false;
+    k = lead;
+    return true;
+}
+
 extern "C" uint32_t ngp_grid_table_adam_prefix(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                                                uint32_t gridtype, int align_corners, int dtype) {
     BackwardPlan plan;
     if (!plan_for_query(plan, offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype)) return 0xffffffffu;
     if (plan.n_atomic != 0 || plan.n_binned != L || dtype != NGP_F16 || C != 2) return 0xffffffffu;
-    uint32_t k = 0;
-    while (k < L && plan.bins.interleaved(k)) k++;
-    for (uint32_t j = k; j < L; j++)
-        if (plan.bins.interleaved(j)) return 0xffffffffu;
+    uint32_t k;
+    if (!dense_level_prefix(plan, k)) return 0xffffffffu;
     return (uint32_t)offsets_host[k];   // (binned levels are listed in level order when every level is binned: index == level)
 }
 
@@ -2280,25 +2289,15 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
                     "grid_encode_backward: table_adam needs overwrite_table and every level on the record-sort path (fp16, C = 2, >= %u samples, "
                     "a workspace and the host offsets)", BIN_MIN_SAMPLES);
         NGP_REQUIRE(tadam->state, NGP_ERR_INVALID, "grid_encode_backward: table_adam without the optimizer's state");
-        {   // the dense levels' round-robin bins leave their entries to ngp_optim_adam_small_commit: they must form a prefix of the table
-            // (ngp_grid_table_adam_prefix tells the caller how long it is), and their gradient has to be stored for it
-            uint32_t k = 0;
-            while (k < plan.n_binned && plan.bins.interleaved(k)) k++;
-            for (uint32_t j = k; j < plan.n_binned; j++)
-                NGP_REQUIRE(!plan.bins.interleaved(j), NGP_ERR_INVALID, "grid_encode_backward: table_adam: a dense level behind a hashed one (level %u)",
-                            plan.bins.level(j));
-            NGP_REQUIRE(k == 0 || grad_embeddings, NGP_ERR_INVALID, "grid_encode_backward: table_adam: the dense levels' gradient needs grad_embeddings");
-        }
-        for (int k = 0; k < 2; k++)
-            NGP_REQUIRE(tadam->param[k] && tadam->exp_avg[k] && tadam->exp_avg_sq[k] && tadam->param_fp16[k], NGP_ERR_INVALID,
-                        "grid_encode_backward: table_adam: NULL buffer in set %d", k);
+        // the dense levels' entries are left to ngp_optim_adam_small_commit (ngp_grid_table_adam_prefix tells the caller how many there are),
+        // and their gradient has to be stored for it
+        uint32_t k;
+        const bool prefix_ok = dense_level_prefix(plan, k);
+        NGP_REQUIRE(prefix_ok, NGP_ERR_INVALID, "grid_encode_backward: table_adam: a dense level behind a hashed one (level %u)", plan.bins.level(k));
+        NGP_REQUIRE(k == 0 || grad_embeddings, NGP_ERR_INVALID, "grid_encode_backward: table_adam: the dense levels' gradient needs grad_embeddings");
+        const int null_set = table_adam_from(plan.table_adam, *tadam);
+        NGP_REQUIRE(null_set < 0, NGP_ERR_INVALID, "grid_encode_backward: table_adam: NULL buffer in set %d", null_set);
         plan.adam = true;
-        for (int k = 0; k < 2; k++) {
-            plan.table_adam.p[k] = tadam->param[k]; plan.table_adam.m[k] = tadam->exp_avg[k]; plan.table_adam.v[k] = tadam->exp_avg_sq[k];
-            plan.table_adam.p16[k] = reinterpret_cast<_Float16*>(tadam->param_fp16[k]);
-        }
-        plan.table_adam.state = tadam->state;
-        plan.table_adam.lr = tadam->lr; plan.table_adam.beta1 = tadam->beta1; plan.table_adam.beta2 = tadam->beta2; plan.table_adam.eps = tadam->eps;
     }
     if (slab_sets && slab_sets->overwrite_table) {
         // every entry comes out of the accumulate only when every level is sorted; otherwise: zero the table, then add as usual

@@ -457,7 +457,7 @@ def fused_train_iteration(model, rays_o, rays_d, target, box, counter, capacity,
     Trainer's loss (nerf/utils.py:516,557) and its scaled gradient in one kernel, then the backward launches, depositing the gradients
     into the optimizer's fp16 buffers (optim.NGPAdam with deposit=True must manage the three parameter tensors).  28 launches instead
     of 45: autograd's bookkeeping kernels (ones/zeros fills, the loss-scale multiplies, the mse forward/backward/mean kernels) vanish.
-    rays_o/rays_d [N,3] fp32, target [N,3] fp32, loss_scale: device scalar (NGPAdam.scalars[0:1]) or None.  noise_seed: optional
+    rays_o/rays_d [N,3] fp32, target [N,3] fp32, loss_scale: device scalar (the SCALE word of NGPAdam.scalars) or None.  noise_seed: optional
     4-byte device word that changes from step to step (NGPAdam's step count); with perturb=True the marcher then draws the per-ray start
     offsets itself (NGP_MARCH_NOISE_FROM_SEED) instead of reading a torch.rand tensor.
     overwrite_table: the table's deposit buffer RECEIVES this iteration's gradient (every entry written, nothing added, nothing read) and

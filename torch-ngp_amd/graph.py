@@ -350,15 +350,16 @@ class GraphedTrainStep:
         lookahead (its own counter row and noise seed), else of the single set (seeded by the optimizer's step count).
         checked: the producers flag non-finite gradients themselves -- and carry the table's Adam sweep when the graphs were captured for it
         (table_fused; the optimizer is then handed over as `table_adam`, else its separate sweep runs)"""
+        from optim import FOUND_INF, SCALE, STEP_COUNT
         m, kw, opt = self.model, self.render_kwargs, self.optimizer
         bg = kw.get('bg_color', None)
         if p is None:
-            batch, counter, seed = (self.rays_o, self.rays_d, self.target), self.counter[0], opt.scalars[3:4]
+            batch, counter, seed = (self.rays_o, self.rays_d, self.target), self.counter[0], opt.scalars.narrow(0, STEP_COUNT, 1)
         else:
             batch, counter, seed = (self.la_rays_o[p], self.la_rays_d[p], self.la_target[p]), self.counter[p], self.la_seed[p:p + 1]
-        args = (m, *batch, m.aabb_train, counter, self.captured_capacity, opt.scalars[0:1], 1 if bg is None else bg, kw.get('perturb', False),
+        args = (m, *batch, m.aabb_train, counter, self.captured_capacity, opt.scalars.narrow(0, SCALE, 1), 1 if bg is None else bg, kw.get('perturb', False),
                 kw.get('dt_gamma', 0), kw.get('max_steps', 1024), kw.get('T_thresh', 1e-4))
-        return args, dict(noise_seed=seed, found_inf=opt.scalars[2:3] if checked else None, overwrite_table=self._overwrites_table(),
+        return args, dict(noise_seed=seed, found_inf=opt.scalars.narrow(0, FOUND_INF, 1) if checked else None, overwrite_table=self._overwrites_table(),
                           table_adam=opt if checked and self.table_fused else None, geo_loss=getattr(self, 'geo_loss', None))
 
     def _iteration_front(self):

@@ -28,7 +28,7 @@ Multi-GPU (one process per GPU, torch.distributed; 'nccl' is RCCL over xGMI), tw
     on a side stream, which the next iteration's parameter-independent ray marching overlaps.  Same bytes on the wire as the ring
     all-reduce (which is a reduce-scatter + all-gather), 1/world of the optimizer traffic, and the gather leaves the critical path.
     The "step skipped as a whole" rule needs a global verdict: every rank sweeps its LOCAL gradient before the exchange into found_inf
-    (scalars[2]); `poison_shards()` then writes NaN into the first element of every shard when that flag is set, the reduce-scatter carries
+    (the FOUND_INF word of `scalars`); `poison_shards()` then writes NaN into the first element of every shard when that flag is set, the reduce-scatter carries
     the NaN to every owner, and `apply()` reads the global verdict off its own shard (`verdict='poison'`, the default: no collective besides
     the reduce-scatter on the critical path).  `verdict='allreduce'` keeps round 3's extra 4-byte all_reduce(MAX) next to the reduce-scatter.
     `shard='force'` runs this path on ONE rank as well (a 1-rank process group: every collective executes, the exchange is the identity) --
@@ -57,6 +57,7 @@ was issued": buffer set B may be the current one) and cleared by `materialize()`
 whoever REPLAYS a captured fused-table step states it after every replay (`replayed_fused_table_step()`): `materialize()` then reads the
 parity word again (tests/test_gpu_table_adam.py: every reader and writer outside the graphs at odd and even replay counts).
 """
+import collections
 import ctypes
 
 import torch
@@ -65,6 +66,28 @@ import torch.distributed as dist
 import _ngp_capi as capi
 
 _MAX = 8
+
+# the eight device-resident state words of an optimizer (`NGPAdam.scalars`; layout and meaning: include/ngp_hip.h, ngp_optim_adam_step);
+# `scalars.narrow(0, WORD, 1)` is the one-element view that kernels and in-place writes take
+SCALE, GROWTH_TRACKER, FOUND_INF, STEP_COUNT, LR_MULT, TABLE_PARITY, TICKET, SCALE_DEAD = range(8)
+
+
+# one tensor of a launch: flat tensors (param / moments / shadows may be None), grad_is_half bits (1: fp16 gradient, 2: kept, not zeroed)
+Entry = collections.namedtuple('Entry', 'n param exp_avg exp_avg_sq grad fp16 is_half lr ema')
+
+
+def _entry_arrays(entries, ema, keep):
+    """up to 8 `Entry`s as nine void* in the order of the fields (ctypes arrays, appended to `keep`: alive until the caller drops them); the
+    EMA shadows only with `ema` (else None); all None for a launch without entries"""
+    k, vp = len(entries), ctypes.c_void_p
+    if not k:
+        return [None] * 9
+    ptrs = lambda tensors: (vp * k)(*[(t.data_ptr() if t is not None else None) for t in tensors])
+    col = Entry(*zip(*entries))   # one tuple per field
+    arrs = ((ctypes.c_uint64 * k)(*map(int, col.n)), ptrs(col.param), ptrs(col.exp_avg), ptrs(col.exp_avg_sq), ptrs(col.grad), ptrs(col.fp16),
+            (ctypes.c_int * k)(*map(int, col.is_half)), (ctypes.c_float * k)(*map(float, col.lr)), ptrs(col.ema) if ema else None)
+    keep.append((arrs, entries))
+    return [ctypes.cast(a, vp) if a is not None else None for a in arrs]
 
 
 def announce_overwrite(p, table_adam_prefix=None):
@@ -203,9 +226,9 @@ class NGPAdam:
                 st['grad16'] = self.flat_grad16[off:off + n].view_as(p)
                 p._ngp_fp16, p._ngp_grad16, p._ngp_version = st['fp16'], st['grad16'], p._version
             self.state[p] = st
-        # device-resident scalars: loss scale, growth tracker, found_inf, Adam step count, lr multiplier (schedulers write this one)
-        self.scalars = torch.tensor([init_scale, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
-        self._scale_view = self.scalars[0]
+        # the device-resident state words (SCALE ... SCALE_DEAD above; schedulers write LR_MULT)
+        self.scalars = torch.tensor([{SCALE: init_scale, LR_MULT: 1.0}.get(i, 0.0) for i in range(8)], dtype=torch.float32, device=dev)
+        self._scale_view = self.scalars[SCALE]
         self._keep = []   # ctypes argument arrays of the launches of the current step (kept alive until the next step / building block)
         self._comm_stream = None
         self._shadows_ready = None
@@ -217,7 +240,7 @@ class NGPAdam:
     def enable_table_fusion(self, param):
         """`param` (the hash table: a deposit-managed parameter of this optimizer) gets a SECOND set of master weights, moments and fp16
         shadow.  A training iteration that passes `table_adam()` to the grid backward (fused.fused_train_iteration(table_adam=...)) has the
-        slice accumulate apply Adam to the table in its flush -- reading the set the device-side parity word `scalars[5]` names, writing the
+        slice accumulate apply Adam to the table in its flush -- reading the set the device-side parity word (TABLE_PARITY) names, writing the
         other -- and `step()` then runs one small launch (Adam on the remaining tensors, loss-scale commit, parity flip when the step
         stands).  GradScaler's skip-the-whole-step rule holds exactly: a skipped step never flips, the current set is never written.
         Outside a stretch of fused steps set A (the torch Parameter, `state[p]`) is the current one: `materialize()` restores that.
@@ -236,9 +259,9 @@ class NGPAdam:
         for t in self._table_alt.values():
             t.zero_()
         self.fused_table = param
-        self.scalars[5:6].zero_()
+        self.scalars.narrow(0, TABLE_PARITY, 1).zero_()
         # readers of the fp16 table (fused.py: ngp_grid_encode_forward_sel) find the second copy and the parity word on the shadow tensor itself
-        st['fp16']._ngp_sel = (self._table_alt['p16'], self.scalars[5:6])
+        st['fp16']._ngp_sel = (self._table_alt['p16'], self.scalars.narrow(0, TABLE_PARITY, 1))
         param._ngp_materialize = self.materialize
 
     def table_adam(self):
@@ -274,12 +297,12 @@ class NGPAdam:
             raise RuntimeError('NGPAdam.materialize: called inside a stream capture (it reads the parity word on the host)')
         p = self.fused_table
         st, alt = self.state[p], self._table_alt
-        if float(self.scalars[5].item()) != 0.0:
+        if float(self.scalars[TABLE_PARITY].item()) != 0.0:
             p.data.copy_(alt['p'])        # (.data: no autograd version bump -- the shadow is copied right here)
             st['exp_avg'].copy_(alt['m'])
             st['exp_avg_sq'].copy_(alt['v'])
             st['fp16'].copy_(alt['p16'])
-            self.scalars[5:6].zero_()
+            self.scalars.narrow(0, TABLE_PARITY, 1).zero_()
         self._maybe_flipped = False
 
     # -- GradScaler-like surface -------------------------------------------------------------------
@@ -287,16 +310,16 @@ class NGPAdam:
         return loss * self._scale_view
 
     def get_scale(self):
-        return float(self.scalars[0].item())
+        return float(self.scalars[SCALE].item())
 
     def scale_is_dead(self):
         """True once the loss scale has underflowed (a long run of overflowing steps halved it to 0 / a denormal): from then on every step is
-        skipped -- as with GradScaler, which has no lower bound either -- and nothing else would say so (one host read of scalars[7])"""
-        return bool(self.scalars[7].item() != 0.0)
+        skipped -- as with GradScaler, which has no lower bound either -- and nothing else would say so (one host read of the SCALE_DEAD word)"""
+        return bool(self.scalars[SCALE_DEAD].item() != 0.0)
 
     def set_lr_scale(self, factor):
         """multiplies every group's lr (what the reference's LambdaLR does, main_nerf.py:137); a device write, valid under graph replay"""
-        self.scalars[4:5].fill_(float(factor))
+        self.scalars.narrow(0, LR_MULT, 1).fill_(float(factor))
 
     def set_lr_lambda(self, fn):
         """`fn(step) -> factor`: the reference's LambdaLR rule (main_nerf.py:137: 0.1 ** min(step / iters, 1)); `schedule_step(step)`
@@ -374,10 +397,10 @@ class NGPAdam:
     # ---- sharded mode: pre_reduce_check (capturable) -> reduce_gradients (collectives) -> apply (capturable) -> gather_shadows (async) ----
     @torch.no_grad()
     def pre_reduce_check(self):
-        """sweep the LOCAL flat gradient for non-finite values into found_inf (scalars[2]); capturable.  First building block of a
+        """sweep the LOCAL flat gradient for non-finite values into the FOUND_INF word; capturable.  First building block of a
         sharded step: starts a fresh list of kept-alive launch arguments."""
         self._keep = []
-        self._launch([(self.total, None, None, None, self.flat_grad16, None, 1, 0.0, None)], capi.NGP_OPT_PHASE_CHECK, 0.0)
+        self._launch([Entry(self.total, None, None, None, self.flat_grad16, None, 1, 0.0, None)], capi.NGP_OPT_PHASE_CHECK, 0.0)
 
     @torch.no_grad()
     def poison_shards(self):
@@ -422,18 +445,18 @@ class NGPAdam:
             dist.all_reduce(self.flat_grad16, op=dist.ReduceOp.SUM, group=self.group)
             self.shard_grad.copy_(view[self.rank])
         if self.verdict != 'poison':
-            dist.all_reduce(self.scalars[2:3], op=dist.ReduceOp.MAX, group=self.group)
+            dist.all_reduce(self.scalars.narrow(0, FOUND_INF, 1), op=dist.ReduceOp.MAX, group=self.group)
 
     def _shard_entries(self):
-        """the pieces of parameters inside my shard, as kernel entries (n, p, m, v, g, p16, is_half, lr, ema)"""
+        """the pieces of parameters inside my shard, as kernel entries"""
         lo, hi = self.shard_range
         out = []
         lr_of = {id(p): g['lr'] for g in self.param_groups for p in g['params']}
         for p, off in zip(self.flat_params, self.offsets):
             a, b = max(off, lo), min(off + p.numel(), hi)
             if a < b:
-                out.append((b - a, self.flat_master[a:b], self.exp_avg[a - lo:b - lo], self.exp_avg_sq[a - lo:b - lo], self.shard_grad[a - lo:b - lo],
-                            self.flat_p16[a:b], 1, lr_of[id(p)], None))
+                out.append(Entry(b - a, self.flat_master[a:b], self.exp_avg[a - lo:b - lo], self.exp_avg_sq[a - lo:b - lo], self.shard_grad[a - lo:b - lo],
+                                 self.flat_p16[a:b], 1, lr_of[id(p)], None))
         return out
 
     @torch.no_grad()
@@ -499,9 +522,9 @@ class NGPAdam:
             self._all_gather(self.flat_master, self.flat_master[lo:hi])
 
     # -- the step ----------------------------------------------------------------------------------
-    def _entries(self):
-        """(param, state, gradient tensor, is_half, lr) of every parameter that received a gradient this iteration.  A parameter with
-        neither a `.grad` nor a deposit buffer is left alone, as torch.optim.Adam skips `grad is None` parameters."""
+    def _entries(self, update_ema=None):
+        """the `Entry` of every parameter that received a gradient this iteration (with its shadow in `update_ema`, if given).  A parameter
+        with neither a `.grad` nor a deposit buffer is left alone, as torch.optim.Adam skips `grad is None` parameters."""
         entries = []
         for g in self.param_groups:
             for p in g['params']:
@@ -522,7 +545,8 @@ class NGPAdam:
                         _consumed(p, kept=True)
                 else:
                     continue
-                entries.append((p, st, grad, is_half, g['lr']))
+                entries.append(Entry(p.numel(), p, st['exp_avg'], st['exp_avg_sq'], grad, st.get('fp16'), is_half, g['lr'],
+                                     update_ema.shadow_of(p) if update_ema is not None else None))
         return entries
 
     clean_deposits = staticmethod(clean_deposits)   # (`optimizer.clean_deposits(params)`: the spelling of graph.py and the tests)
@@ -533,44 +557,27 @@ class NGPAdam:
             return False
         return bool(st['grad16'].ne(0).any().item())
 
-    def _entry_arrays(self, entries, ema):
-        """the per-entry arguments of a launch as nine void* (ctypes arrays, kept alive until the next step): n, param, exp_avg, exp_avg_sq,
-        grad, fp16 shadow, grad_is_half, lr and -- `ema` -- the EMA shadow (else None); all None for a launch without entries.
-        entries: up to 8 tuples in that order, of flat tensors (param / moments / shadows may be None)"""
-        k = len(entries)
-        if not k:
-            return [None] * 9
-        vp = ctypes.c_void_p
-
-        def ptrs(i):
-            return (vp * k)(*[(e[i].data_ptr() if e[i] is not None else None) for e in entries])
-        arrs = ((ctypes.c_uint64 * k)(*[int(e[0]) for e in entries]), ptrs(1), ptrs(2), ptrs(3), ptrs(4), ptrs(5),
-                (ctypes.c_int * k)(*[int(e[6]) for e in entries]), (ctypes.c_float * k)(*[float(e[7]) for e in entries]), ptrs(8) if ema else None)
-        self._keep.append((arrs, entries))
-        return [ctypes.cast(a, vp) if a is not None else None for a in arrs]
+    def _leading_args(self, entries, cast):
+        """the arguments both Adam entries start with: count, the first eight arrays of `cast` (_entry_arrays), betas, eps, grad_mult, growth, backoff, interval, state"""
+        return [len(entries), *cast[:8], self.betas[0], self.betas[1], self.eps, 1.0, self.growth_factor, self.backoff_factor, self.growth_interval, self.scalars.data_ptr()]
 
     def _launch(self, entries, phases, omd):
-        """one ngp_optim_adam_step_ex call over up to 8 entries (`_entry_arrays`; param / moments may be None for a CHECK-only call)"""
-        cast = self._entry_arrays(entries, ema=omd > 0.0)
-        capi.check(capi.lib.ngp_optim_adam_step_ex(len(entries), cast[0], cast[1], cast[2], cast[3], cast[4], cast[5], cast[6], cast[7], self.betas[0],
-                                                   self.betas[1], self.eps, 1.0, self.growth_factor, self.backoff_factor, self.growth_interval,
-                                                   self.scalars.data_ptr(), cast[8], float(omd), phases, capi.stream()))
+        """one ngp_optim_adam_step_ex call over up to 8 entries (param / moments may be None for a CHECK-only call)"""
+        cast = _entry_arrays(entries, omd > 0.0, self._keep)
+        capi.check(capi.lib.ngp_optim_adam_step_ex(*self._leading_args(entries, cast), cast[8], float(omd), phases, capi.stream()))
 
     def _launch_small_commit(self, entries, flip, table_prefix=0):
-        k, cast = len(entries), self._entry_arrays(entries, ema=False)
         ta = self._table_adam_struct() if table_prefix else None   # (copied by the C entry before it returns)
-        capi.check(capi.lib.ngp_optim_adam_small_commit(k, cast[0], cast[1], cast[2], cast[3], cast[4], cast[5], cast[6], cast[7], self.betas[0],
-                                                        self.betas[1], self.eps, 1.0, self.growth_factor, self.backoff_factor, self.growth_interval,
-                                                        self.scalars.data_ptr(), 1 if flip else 0,
+        capi.check(capi.lib.ngp_optim_adam_small_commit(*self._leading_args(entries, _entry_arrays(entries, False, self._keep)), 1 if flip else 0,
                                                         None if ta is None else ctypes.cast(ctypes.pointer(ta), ctypes.c_void_p),
-                                                        self.state[self.fused_table]['grad16'].data_ptr() if table_prefix else None,
-                                                        int(table_prefix), capi.stream()))
+                                                        self.state[self.fused_table]['grad16'].data_ptr() if table_prefix else None, int(table_prefix),
+                                                        capi.stream()))
 
     @torch.no_grad()
     def step(self, update_ema=None, gradients_checked=False):
         """one optimizer + loss-scaling step.  `update_ema`: an `NGPEma` whose moving average is advanced inside the same sweep (the
         Trainer does that once per epoch, nerf/utils.py:760-761,891-892; call it with the last step of the epoch).
-        gradients_checked: the kernels that deposited the fp16 gradients already set found_inf (scalars[2]) where a value came out
+        gradients_checked: the kernels that deposited the fp16 gradients already set the FOUND_INF word where a value came out
         non-finite (fused.fused_train_iteration(found_inf=...)), so the sweep of the CHECK phase is not launched; ignored (the sweep runs)
         when any parameter carries an autograd `.grad`.
         Sharded mode: the whole exchange-and-update sequence (pre_reduce_check -> reduce_gradients -> apply -> gather_shadows)."""
@@ -598,9 +605,8 @@ class NGPAdam:
             if update_ema is not None or not gradients_checked:
                 raise RuntimeError('NGPAdam.step: a fused-table step needs gradients_checked=True (the producers raise found_inf) and no fold-in EMA')
             self.clean_deposits([p for p in self.flat_params if p is not self.fused_table and not getattr(p, '_ngp_deposit_overwritten', False)])
-            entries = [(p.numel(), p, st['exp_avg'], st['exp_avg_sq'], grad, st.get('fp16'), is_half, lr, None)
-                       for p, st, grad, is_half, lr in self._entries() if p is not self.fused_table]
-            if len(entries) > _MAX or not all(e[6] & 1 for e in entries):
+            entries = [e for e in self._entries() if e.param is not self.fused_table]
+            if len(entries) > _MAX or not all(e.is_half & 1 for e in entries):
                 raise RuntimeError('NGPAdam.step: a fused-table step serves at most 8 remaining tensors, all with deposited fp16 gradients')
             # the dense levels at the start of the table (left out by the accumulate's flush) are swept here, contiguously
             prefix = int(getattr(self.fused_table, '_ngp_table_adam_prefix', 0)) * int(self.fused_table.shape[1])
@@ -610,10 +616,9 @@ class NGPAdam:
         # a deposit buffer that an overwriting producer left behind and nobody has overwritten since holds an OLD gradient
         self.clean_deposits([p for p in self.flat_params if not getattr(p, '_ngp_deposit_overwritten', False)])
         omd = update_ema.begin_update() if update_ema is not None else 0.0
-        entries = [(p.numel(), p, st['exp_avg'], st['exp_avg_sq'], grad, st.get('fp16'), is_half, lr,
-                    update_ema.shadow_of(p) if update_ema is not None else None) for p, st, grad, is_half, lr in self._entries()]
+        entries = self._entries(update_ema)
         chunks = [entries[i:i + _MAX] for i in range(0, len(entries), _MAX)]
-        checked = gradients_checked and all(e[6] & 1 for e in entries)   # every gradient is a deposited fp16 buffer
+        checked = gradients_checked and all(e.is_half & 1 for e in entries)   # every gradient is a deposited fp16 buffer
         if len(chunks) == 1:
             self._launch(chunks[0], (0 if checked else CHECK) | UPDATE | COMMIT, omd)
         else:
@@ -640,7 +645,7 @@ class NGPAdam:
                 continue
             self._set_moments(p, st['exp_avg'], st['exp_avg_sq'])
             step = max(step, float(st['step']))
-        self.scalars[3:4].fill_(step)
+        self.scalars.narrow(0, STEP_COUNT, 1).fill_(step)
         # learning rate: the group keeps the scheduler-free base rate, the scheduler's current factor (LambdaLR writes lr =
         # initial_lr * lambda(step), main_nerf.py:137) goes into the device-side multiplier -- a resumed run continues at the decayed rate
         factors = []
@@ -657,10 +662,9 @@ class NGPAdam:
             else:
                 self.set_lr_scale(factors[0])
         if scaler_sd:
-            self.scalars[0:1].fill_(float(scaler_sd.get('scale', self.get_scale())))
-            self.scalars[1:2].fill_(float(scaler_sd.get('_growth_tracker', 0)))
+            self.scalars.narrow(0, SCALE, 1).fill_(float(scaler_sd.get('scale', self.get_scale())))
+            self.scalars.narrow(0, GROWTH_TRACKER, 1).fill_(float(scaler_sd.get('_growth_tracker', 0)))
         self._sync_shadows(assume_complete=True)   # the caller loaded the full parameter set on every rank
-
 
     def _shard_piece(self, p):
         """(a, b, off): the packed range [a, b) of parameter p inside my shard (a >= b: nothing) and p's packed offset"""
@@ -706,7 +710,7 @@ class NGPAdam:
         flat = [p for g in self.param_groups for p in g['params']]
         self.materialize()
         self.scalars.copy_(sd['scalars'])
-        self.scalars[5:6].zero_()   # (the parity of a fused table is not part of a checkpoint: set A is what gets loaded)
+        self.scalars.narrow(0, TABLE_PARITY, 1).zero_()   # (the parity of a fused table is not part of a checkpoint: set A is what gets loaded)
         for p, m, v in zip(flat, sd['exp_avg'], sd['exp_avg_sq']):
             self._set_moments(p, m, v)
         for g, lr in zip(self.param_groups, sd['lr']):
@@ -761,18 +765,11 @@ class NGPEma:
     def update(self):
         self._complete_params()
         omd = self.begin_update()
-        stream = capi.stream()
-        keep = []
+        self._keep = []
         for i in range(0, len(self.params), _MAX):
-            ps, sh = self.params[i:i + _MAX], self.shadow_params[i:i + _MAX]
-            k = len(ps)
-            n = (ctypes.c_uint64 * k)(*[p.numel() for p in ps])
-            pp = (ctypes.c_void_p * k)(*[p.data_ptr() for p in ps])
-            ss = (ctypes.c_void_p * k)(*[t.data_ptr() for t in sh])
-            keep.append((n, pp, ss))
-            capi.check(capi.lib.ngp_optim_ema_update(k, ctypes.cast(n, ctypes.c_void_p), ctypes.cast(pp, ctypes.c_void_p),
-                                                     ctypes.cast(ss, ctypes.c_void_p), float(omd), stream))
-        self._keep = keep
+            entries = [Entry(p.numel(), p, None, None, None, None, 0, 0.0, t) for p, t in zip(self.params[i:i + _MAX], self.shadow_params[i:i + _MAX])]
+            cast = _entry_arrays(entries, True, self._keep)
+            capi.check(capi.lib.ngp_optim_ema_update(len(entries), cast[0], cast[1], cast[8], float(omd), capi.stream()))
 
     @torch.no_grad()
     def copy_to(self):
