@@ -24,6 +24,7 @@ with planted structure, each item an edge of the segmented wave scan of the atom
 `exactness` states, from the oracle alone, what every case must satisfy; tests/test_grid_lattice_cases.py asserts it for every case
 the GPU tests use, so a vacuous case fails instead of passing."""
 import collections
+import copy
 import functools
 import itertools
 
@@ -112,8 +113,8 @@ def _colliding_pair(case, rng, level):
 
 
 @functools.lru_cache(maxsize=None)
-def make(case):
-    """x [B, D] float32, g [L, B, C] float32, offsets int32 [L + 1], S = 0.0 (cached: treat the arrays as read-only)"""
+def _walk(case):
+    """the sample sequence of a case: x [B, D] float32, the gradient numerators J [B, C] and the generator behind them"""
     D, C, H, sub, jmax = case.D, case.C, case.H, case.sub, case.jmax
     rng = np.random.default_rng(1000 + case.seed)
     N = sub * (H - 1)
@@ -208,6 +209,22 @@ def make(case):
     sel = np.flatnonzero(OOB)
     axis = sel % D
     x[sel, axis] = np.where(OOB[sel] == OOB_HI, np.nextafter(np.float32(1.0), np.float32(2.0)), np.float32(-1e-7))
+    x.setflags(write=False)
+    return x, J, rng
+
+
+def points(case):
+    """x [B, D] float32, offsets int32 [L + 1], S = 0.0: the points of make(case) without its gradients (the forward's cases,
+    tests/grid_forward_cases.py)"""
+    return _walk(case)[0], _offsets(case), 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def make(case):
+    """x [B, D] float32, g [L, B, C] float32, offsets int32 [L + 1], S = 0.0 (cached: treat the arrays as read-only)"""
+    x, J, rng = _walk(case)
+    rng = copy.deepcopy(rng)
+    C, H = case.C, case.H
     L = len(case.level_sizes)
     g = np.empty((L, case.B, C), np.float32)
     g[0] = J * 2.0 ** -6
@@ -226,7 +243,7 @@ def make(case):
             assert l > 0 and window[l] > 256, 'level 0 carries the planted structure whole: shrink |j| or the stretch instead'
             window[l] //= 2
             g[l, window[l]:] = 0.0
-    for a in (x, g, offs):
+    for a in (g, offs):
         a.setflags(write=False)
     return x, g, offs, 0.0
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import oracle
+from grid_forward_cases import grid_reference as _grid_reference   # the float64 model of the forward: the fp16 / fp32 kernels are pinned to it too
 
 pytestmark = pytest.mark.gpu
 
@@ -49,58 +50,6 @@ def _table(n, C, rng):
     return 1.0 + rng.integers(0, 1 << 20, (n, C)).astype(np.float64) * 2.0 ** -40
 
 
-def _frac32(x, scale, align, interp):
-    """fractions and smoothstep derivative exactly as grid_index.h: locate() computes them (fp32, same operation order)"""
-    p = (x.astype(np.float64) * np.float64(scale) + (0.0 if align else 0.5)).astype(np.float32)   # fmaf: exact here, one rounding
-    f = (p - np.floor(p)).astype(np.float32)
-    one = np.float32(1)
-    if interp == 1:
-        deriv = (np.float32(6) * f) * (one - f)
-        f = (f * f) * (np.float32(3) - np.float32(2) * f)
-    else:
-        deriv = np.ones_like(f)
-    return f, deriv
-
-
-def _grid_reference(x, emb, offs, S, H, gridtype, align, interp):
-    """fp64 restatement: oracle corner indices, fp32 weights as the kernel forms them, fp64 products and sums.
-    -> outputs [L,B,C], dy_dx [B,L,D,C], per level (indices [B,2^D] global, weights [B,2^D] fp32, inside mask)"""
-    B, D = x.shape
-    C = emb.shape[1]
-    L = len(offs) - 1
-    idx = oracle.grid_corner_indices(x, offs, S, H, gridtype, align)
-    scale, _ = oracle.grid_level_table(L, S, H)
-    inside = np.all((x >= 0) & (x <= 1), axis=1)
-    out = np.zeros((L, B, C))
-    dydx = np.zeros((B, L, D, C))
-    levels = []
-    for l in range(L):
-        f, deriv = _frac32(x, scale[l], align, interp)
-        gidx = offs[l] + idx[l].astype(np.int64)
-        gidx[~inside] = 0
-        ws = np.zeros((B, 1 << D), np.float32)
-        for k in range(1 << D):
-            w = np.ones(B, np.float32)
-            for d in range(D):
-                w = w * (f[:, d] if (k >> d) & 1 else np.float32(1) - f[:, d])
-            ws[:, k] = w
-            out[l] += w.astype(np.float64)[:, None] * emb[gidx[:, k]]
-        for g in range(D):
-            for k in range(1 << D):
-                if (k >> g) & 1:
-                    continue
-                w = np.full(B, scale[l], np.float32)
-                for d in range(D):
-                    if d != g:
-                        w = w * (f[:, d] if (k >> d) & 1 else np.float32(1) - f[:, d])
-                wd = (w * deriv[:, g]).astype(np.float64)
-                dydx[:, l, g] += wd[:, None] * (emb[gidx[:, k | (1 << g)]] - emb[gidx[:, k]])
-        out[l][~inside] = 0
-        dydx[~inside, l] = 0
-        levels.append((gidx, ws, inside))
-    return out, dydx, levels
-
-
 def _close(got, want, rel=1e-12):
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape
@@ -125,7 +74,7 @@ def test_grid_forward_matches_fp64_restatement(D, C):
                 offs = _offsets(D, L, H, 2.0, 10, align)
                 emb = _table(int(offs[-1]), C, rng)
                 x = _dyadic_points(B, D, rng)
-                want_out, want_dy, _ = _grid_reference(x, emb, offs, S, H, gridtype, align, interp)
+                want_out, want_dy, _, _ = _grid_reference(x, emb, offs, S, H, gridtype, align, interp)
                 xt, et, ot = torch.from_numpy(x).cuda(), torch.from_numpy(emb).cuda(), torch.from_numpy(offs).cuda()
                 for with_dy in (True, False):
                     out = torch.empty(L, B, C, device='cuda', dtype=F64)
@@ -145,7 +94,7 @@ def test_grid_backward_matches_fp64_restatement(kind, D, C, gridtype, align, int
     emb = _table(int(offs[-1]), C, rng)
     x = _dyadic_points(B, D, rng)
     grad = rng.standard_normal((L, B, C))
-    _, want_dy, levels = _grid_reference(x, emb, offs, S, H, gridtype, align, interp)
+    _, want_dy, levels, _ = _grid_reference(x, emb, offs, S, H, gridtype, align, interp)
     want_ge = np.zeros_like(emb)
     for l, (gidx, ws, inside) in enumerate(levels):
         contrib = ws.astype(np.float64)[:, :, None] * grad[l][:, None, :]       # [B, 2^D, C]

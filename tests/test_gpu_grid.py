@@ -100,6 +100,8 @@ def test_forward_lego_config(dtype, tol):
     (5, 1, 0, False, 1, torch.float32), (2, 8, 1, True, 0, torch.float16), (3, 1, 0, False, 0, torch.float16),
 ])
 def test_forward_and_dydx_all_shapes(D, C, gridtype, align, interp, dtype):
+    """calc_grad=True: every shape here runs k_grid_forward<T, D, C, true>, the dy_dx kernel; the scheduled kernels (k_grid_forward_pair,
+    k_grid_forward_fast) are covered over the same shapes by tests/test_gpu_grid_forward.py"""
     rng = np.random.default_rng(2)
     offs, pls = oracle.grid_offsets(input_dim=D, num_levels=5, level_dim=C, per_level_scale=1.6, base_resolution=4,
                                     log2_hashmap_size=11, align_corners=align)
