@@ -374,7 +374,19 @@ int ngp_grid_encode_backward_ws(const void* grad, const float* inputs, const voi
  * `grid = max(grid * decay, tmp)` where both sides are >= 0 (one update per distinct cell), `mean(clamp(grid, 0))` (double, fixed order)
  * and packbits against min(density_thresh, mean) -- nothing read back.  cells [n] int64: cascade * H^3 + morton index of each queried
  * point; scratch [n_cells] fp32: -1 everywhere before the first call, left that way; workspace: ngp_density_grid_update_workspace_bytes,
- * zeroed before the first call. */
+ * zeroed before the first call.
+ * What tests/test_gpu_occupancy.py pins (model: tests/occupancy_cases.py density_update_model):
+ *   - n_cells >= 8 and a multiple of 8; density_grid and scratch 16-byte aligned (NGP_ERR_INVALID otherwise); n may be 0;
+ *   - an index >= n_cells is ignored (nothing is written for it); indices are not expected to be negative;
+ *   - with f = fl32(density_scale * sigma) the fresh value of a sampled cell and g its grid value: where g >= 0 and f >= 0 (-0.0 counts
+ *     as >= 0) the cell becomes max(fl32(g * decay), f) in fp32 (max(+0, -0) = +0), bit for bit; a NaN or negative f is NOT applied -- its
+ *     scratch entry is reset to -1 all the same --, a cell with g < 0 is left alone, a cell that was not sampled keeps its bits (no
+ *     decay).  Of several samples of one cell any one wins (as with index_put_);
+ *   - scratch is -1.0 everywhere after every call, the workspace is ready for the next call (no re-zeroing);
+ *   - mean_out[0] = the fp32 rounding of [sum of max(g, 0) over the updated grid, accumulated in double in a fixed order] / n_cells: the
+ *     same bits on every call with the same inputs, at most 1 fp32 ulp from the rounding of the exact mean (equal to it when the double
+ *     sum is exact in any order);
+ *   - bitfield = packbits(updated grid, fminf(density_thresh, mean_out[0])). */
 size_t ngp_density_grid_update_workspace_bytes(uint32_t n_cells);
 int ngp_density_grid_update(const float* sigmas, const int64_t* cells, uint32_t n, float density_scale, float decay, float* density_grid,
                             uint32_t n_cells, float* scratch, float density_thresh, float* mean_out, uint8_t* bitfield, void* workspace,
@@ -599,7 +611,12 @@ int ngp_render_iterations_dev(const ngp_render_loop_t* args, uint32_t n_iter, ui
  * alive).  ngp_coarse_occupancy: per cascade a (H/4)^3 byte grid (x fastest), 1 when any voxel of the cell's 4^3 block or of one of its 26
  * neighbouring blocks is occupied (ngp_coarse_occupancy_bytes(C, H) bytes).  ngp_cull_rays: rays_alive[n] = n, or -1 for a ray whose segment
  * [near, far] provably (conservatively: half-cell sampling of the dilated grid, every cascade the marcher could select) meets no occupied
- * voxel -- such a ray would emit no sample, so dropping it from the initial alive list (ngp_compact_rays) leaves the image bit-identical. */
+ * voxel -- such a ray would emit no sample, so dropping it from the initial alive list (ngp_compact_rays) leaves the image bit-identical.
+ * Verdicts that do not depend on the grid: near >= far (the ray misses the box; near or far NaN included) gives -1.  With near < far a
+ * DEGENERATE ray is KEPT, not judged: a zero direction, a direction with a NaN or infinite length, far = +inf, and a ray that is not through
+ * after 4096 samples (e.g. near = 0, far = 2000 in a bound-1 box of 16^3).  Entries of rays_alive behind N are not written.  The verdicts
+ * are pinned ray for ray by tests/test_gpu_occupancy.py against oracle/ngp_oracle.c orc_cull_rays, the coarse grid against
+ * tests/occupancy_cases.py coarse_model. */
 size_t ngp_coarse_occupancy_bytes(uint32_t C, uint32_t H);
 int ngp_coarse_occupancy(const uint8_t* grid, uint32_t C, uint32_t H, uint8_t* coarse, ngp_stream_t stream);
 int ngp_cull_rays(const float* rays_o, const float* rays_d, const float* nears, const float* fars, uint32_t N, float bound, uint32_t C,

@@ -247,6 +247,28 @@ def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, bitfi
     return xyzs, dirs, deltas
 
 
+def coarse_occupancy(bitfield, C, H):
+    """ngp_coarse_occupancy (include/ngp_hip.h) voxel by voxel -> uint8 [C * (H/4)^3], x fastest"""
+    bitfield = np.ascontiguousarray(bitfield, dtype=np.uint8)
+    assert bitfield.size == C * H ** 3 // 8
+    out = np.zeros(C * (H // 4) ** 3, np.uint8)
+    lib().orc_coarse_occupancy(_p(bitfield), u32(C), u32(H), _p(out))
+    return out
+
+
+def cull_rays(rays_o, rays_d, nears, fars, bound, C, H, coarse, variant=0):
+    """k_cull_rays (csrc/raymarching.hip) in fp32, statement by statement -> rays_alive [N] int32 (n kept, -1 culled).
+    variant 1..3: deliberately wrong versions (ngp_oracle.c), for the tests of the tests only."""
+    rays_o, rays_d = _f32(rays_o).reshape(-1, 3), _f32(rays_d).reshape(-1, 3)
+    N = rays_o.shape[0]
+    coarse = np.ascontiguousarray(coarse, dtype=np.uint8)
+    assert coarse.size >= C * (H // 4) ** 3
+    out = np.full(N, -7, np.int32)
+    lib().orc_cull_rays(_p(rays_o), _p(rays_d), _p(_f32(nears)), _p(_f32(fars)), u32(N), f32(bound), u32(C), u32(H), _p(coarse), _p(out),
+                        u32(variant))
+    return out
+
+
 def composite_rays_train_forward(sigmas, rgbs, deltas, rays, T_thresh=1e-4):
     sigmas, rgbs, deltas, rays = _f32(sigmas), _f32(rgbs), _f32(deltas), _i32(rays)
     M, N = sigmas.shape[0], rays.shape[0]

@@ -620,3 +620,86 @@ void orc_composite_rays(uint32_t n_alive, uint32_t n_step, float T_thresh, int32
         image[index * 3] = (float)r; image[index * 3 + 1] = (float)g; image[index * 3 + 2] = (float)b;
     }
 }
+
+/* =====================================================================================
+ *  empty-ray culling     (extension, include/ngp_hip.h "Empty-ray culling"; no reference counterpart)
+ * ===================================================================================== */
+/* ngp_coarse_occupancy from the header's statement, voxel by voxel: per cascade a (H/4)^3 byte grid, x fastest, 1 when any voxel of the
+ * cell's 4^3 block or of one of its 26 neighbouring blocks (those inside the grid) is occupied.  coarse: C * (H/4)^3 bytes. */
+void orc_coarse_occupancy(const uint8_t *grid, uint32_t C, uint32_t H, uint8_t *coarse) {
+    const uint32_t R = H / 4u;
+    const size_t cells = (size_t)R * R * R, H3 = (size_t)H * H * H;
+    uint8_t *any = (uint8_t *)calloc(cells ? cells : 1, 1);
+    for (uint32_t c = 0; c < C; c++) {
+        memset(any, 0, cells);
+        for (uint32_t z = 0; z < H; z++)
+            for (uint32_t y = 0; y < H; y++)
+                for (uint32_t x = 0; x < H; x++) {
+                    const size_t index = (size_t)c * H3 + orc_morton3D_1(x, y, z);
+                    if (grid[index / 8] & (1u << (index % 8))) any[((size_t)(z / 4u) * R + y / 4u) * R + x / 4u] = 1;
+                }
+        for (int z = 0; z < (int)R; z++)
+            for (int y = 0; y < (int)R; y++)
+                for (int x = 0; x < (int)R; x++) {
+                    uint8_t v = 0;
+                    for (int dz = -1; dz <= 1; dz++)
+                        for (int dy = -1; dy <= 1; dy++)
+                            for (int dx = -1; dx <= 1; dx++) {
+                                const int X = x + dx, Y = y + dy, Z = z + dz;
+                                if (X < 0 || Y < 0 || Z < 0 || X >= (int)R || Y >= (int)R || Z >= (int)R) continue;
+                                v |= any[((size_t)Z * R + (size_t)Y) * R + (size_t)X];
+                            }
+                    coarse[(size_t)c * cells + ((size_t)z * R + (size_t)y) * R + (size_t)x] = v;
+                }
+    }
+    free(any);
+}
+
+/* k_cull_rays (csrc/raymarching.hip) in its statement order, fp32: every multiply-add the kernel fuses is an fmaf() here, everything else
+ * one correctly rounded operation (sqrtf and the divisions are IEEE on both sides); the kernel's clamp_med3(x, lo, hi) is
+ * fminf(hi, fmaxf(lo, x)) for lo <= hi and a number x (orc_clampf), its mip_exponent is orc_mip_exponent.  rays_alive[n] = n for a kept
+ * ray, -1 for a culled one.
+ * variant 0 is the kernel's algorithm.  1..3 are DELIBERATELY WRONG versions that tests/occupancy_cases.py must tell from it:
+ *   1  a step of 1.8 coarse cells instead of 0.9;  2  the cascade lookup starts at lp instead of lp - 1;  3  only the finest cascade of
+ *   the lookup is read. */
+void orc_cull_rays(const float *rays_o, const float *rays_d, const float *nears, const float *fars, uint32_t N, float bound,
+                   uint32_t C, uint32_t H, const uint8_t *coarse, int32_t *rays_alive, uint32_t variant) {
+    const uint32_t R = H / 4u, cells = R * R * R;
+    const float Rf = (float)R;
+    const float stride = variant == 1 ? 1.8f : 0.9f;
+    for (uint32_t n = 0; n < N; n++) {
+        const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
+        const float dx = rays_d[n * 3], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
+        const float near = nears[n], far = fars[n];
+        const float dlen = sqrtf(dx * dx + dy * dy + dz * dz);
+        const float rdlen = 1.0f / dlen, rbound = 1.0f / bound;
+        const int regular = dlen > 0.0f && isfinite(far) && isfinite(dlen);
+        int keep = (near < far) && !regular;
+        if (near < far && regular) {
+            float t = near;
+            for (uint32_t it = 0; it < 4096u && !keep; it++) {
+                const float tc = fminf(t, far);
+                const float x = orc_clampf(fmaf(tc, dx, ox), -bound, bound);
+                const float y = orc_clampf(fmaf(tc, dy, oy), -bound, bound);
+                const float z = orc_clampf(fmaf(tc, dz, oz), -bound, bound);
+                int lp = 0;
+                if (C > 1u) lp = orc_mip_exponent(fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z))), C);
+                int c0 = lp > 0 ? lp - 1 : 0;
+                if (variant == 2) c0 = lp;
+                for (int c = c0; c < (int)C && !keep; c++) {
+                    const float pw = scalbnf(1.0f, c);
+                    const float rmb = pw < bound ? scalbnf(1.0f, -c) : rbound;
+                    const int ix = (int)orc_clampf((0.5f * fmaf(x, rmb, 1.0f)) * Rf, 0.0f, Rf - 1.0f);
+                    const int iy = (int)orc_clampf((0.5f * fmaf(y, rmb, 1.0f)) * Rf, 0.0f, Rf - 1.0f);
+                    const int iz = (int)orc_clampf((0.5f * fmaf(z, rmb, 1.0f)) * Rf, 0.0f, Rf - 1.0f);
+                    keep = coarse[(size_t)c * cells + ((uint32_t)iz * R + (uint32_t)iy) * R + (uint32_t)ix] != 0u;
+                    if (variant == 3) break;
+                }
+                if (!(t < far)) break;
+                t += stride * (2.0f * fminf(scalbnf(1.0f, lp), bound) / Rf) * rdlen;
+                if (it == 4095u) keep = 1;
+            }
+        }
+        rays_alive[n] = keep ? (int32_t)n : -1;
+    }
+}

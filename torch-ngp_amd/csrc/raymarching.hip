@@ -167,7 +167,9 @@ __global__ __launch_bounds__(DM_THREADS) void k_density_apply_mean(float* __rest
 #pragma unroll 2
     for (int k = 0; k < DM_PER_THREAD / 4; k++) {
         const uint32_t i = base + (uint32_t)(k * DM_THREADS + threadIdx.x) * 4u;
-        if (i + 3u < n_cells) {
+        // (i is a multiple of 4 and n_cells one of 8 -- ngp_density_grid_update requires it --, so a group that starts inside the grid lies
+        // inside it entirely: there is no partial group, only whole groups past the end, which are skipped)
+        if (i < n_cells) {
             float4_t g = *reinterpret_cast<const float4_t*>(grid + i);
             const float4_t f = *reinterpret_cast<const float4_t*>(scratch + i);
             bool t0, t1, t2, t3;
@@ -175,12 +177,6 @@ __global__ __launch_bounds__(DM_THREADS) void k_density_apply_mean(float* __rest
             if (t0 || t1 || t2 || t3) {
                 *reinterpret_cast<float4_t*>(grid + i) = g;
                 *reinterpret_cast<float4_t*>(scratch + i) = float4_t{-1.0f, -1.0f, -1.0f, -1.0f};
-            }
-        } else {
-            for (uint32_t j = i; j < n_cells; j++) {
-                bool t;
-                const float g = one(grid[j], scratch[j], t);
-                if (t) { grid[j] = g; scratch[j] = -1.0f; }
             }
         }
     }
