@@ -584,6 +584,29 @@ int ngp_composite_rays_dev(const int32_t* state, uint32_t alive_bound, uint32_t 
 int ngp_compact_rays_dev(const int32_t* state, uint32_t alive_bound, uint32_t n_total, uint32_t n_step_cap, uint32_t max_steps, const int32_t* rays_alive,
                          int32_t* out_alive, int32_t* out_state, void* workspace, ngp_stream_t stream);
 
+/* EXTENSION (not in the reference): caller-defined per-sample channels in the inference loop -- the non-mutating companion of
+ * ngp_composite_rays / ngp_composite_rays_dev.  Call it BEFORE that entry, on the same sample rows, alive list and stream: it reads the
+ * weights_sum the compositor is about to advance and, for list entry n (index = rays_alive[n], rows s = n * n_step + step), runs the
+ * compositor's own statements
+ *   ws = weights_sum[index];  per step:  d0 = deltas[s,0], d0 == 0 ends the ray BEFORE anything of the row is read;
+ *   alpha = 1 - exp(-sigmas[s] d0), T = 1 - ws, w = alpha T, ws += w;  out[index, c] += w feats[s, c]  (c = 0 .. C-1);  T < T_thresh ends the
+ *   ray BEHIND the accumulation
+ * in fp32 with an unfused multiply and add, in step order, starting from the out the caller passes: the result does not depend on how a
+ * ray's samples are chunked into calls; with feats = rgbs (and out = image) it has the bits of the compositor's image, with a channel of
+ * ones (out = weights_sum) those of its weights_sum.  Only out [N,C] fp32 is written -- rays_alive, weights_sum and the sample rows are
+ * read, rows at or behind a ray's end are not.  feats [>= n_alive * n_step, C] of feat_dtype (NGP_F32 or NGP_F16; fp16 is converted at the
+ * load: the bits of the fp32 call on the up-cast values), 1 <= C <= 256.  Deterministic: list entries are distinct rays, nothing crosses
+ * lanes.  _dev: n_alive and n_step = max(min(n_total / n_alive, cap), 1) come from `state` as in ngp_composite_rays_dev (same n_total and
+ * n_step_cap as the other calls of the iteration); entries beyond the device-side count do nothing.
+ * C outside 1 .. 256, an unknown feat_dtype, n_step_cap > 1024 or a NULL tensor: NGP_ERR_INVALID.  n_alive == 0 / alive_bound == 0: nothing
+ * is launched. */
+int ngp_composite_rays_features(uint32_t n_alive, uint32_t n_step, float T_thresh, const int32_t* rays_alive, const float* sigmas,
+                                const void* feats, const float* deltas, const float* weights_sum, uint32_t C, int feat_dtype,
+                                float* out, ngp_stream_t stream);
+int ngp_composite_rays_features_dev(const int32_t* state, uint32_t alive_bound, uint32_t n_total, uint32_t n_step_cap, float T_thresh,
+                                    const int32_t* rays_alive, const float* sigmas, const void* feats, const float* deltas,
+                                    const float* weights_sum, uint32_t C, int feat_dtype, float* out, ngp_stream_t stream);
+
 /* n iterations of the eval loop (renderer.py:341-367: march_rays -> network -> composite_rays -> compaction of the alive list) issued by ONE
  * call -- EXTENSION: ngp_march_rays_dev -> ngp_grid_encode_forward_sched -> ngp_network_forward (inference, density scale
  * folded) -> ngp_composite_rays_dev -> ngp_compact_rays_dev per iteration, on the ping-pong alive lists / device state of the *_dev entry

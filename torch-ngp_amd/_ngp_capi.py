@@ -118,6 +118,8 @@ _SIGNATURES = {
     'ngp_composite_rays_train_features_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _i32, _vp, _vp, _vp],
     'ngp_composite_rays_train_features_forward_f64': [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp],
     'ngp_composite_rays_train_features_backward_f64': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp],
+    'ngp_composite_rays_features': [_u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _vp],
+    'ngp_composite_rays_features_dev': [_vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _u32, _i32, _vp, _vp],
     'ngp_composite_train_loss_backward': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _sz, _vp],
     # ... + (lambda_distortion, lambda_depth, target_depth, depth_weight) after target, (depth_raw, distortion) after depth_out

@@ -1369,6 +1369,93 @@ __global__ __launch_bounds__(RM_THREADS) void k_composite_rays(uint32_t n_alive,
     image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
 }
 
+// Per-sample feature channels in the inference loop (extension): out[index, c] += sum over the samples k_composite_rays
+// composites in this call of w * feats[s, c], 1 <= C <= 256, with that kernel's statements for the weight (d0 == 0 breaks before the row is
+// read, T = 1 - ws, w = alpha * T, ws += w, `T < T_thresh` breaks behind the accumulation) and its unfused multiply and add -- so with
+// feats = rgbs the result has the bits of `image`, with a channel of ones those of `weights_sum`.  Launched BEFORE k_composite_rays on the same
+// rows: it reads the weights_sum that kernel is about to advance, and writes nothing but `out`.
+// Lanes: 1 << lp = min(C, 64) rounded up to a power of two lanes per group, lane = (group t >> lp, channel t & (P - 1)); C > 64 walks NB
+// channel blocks of 64 with one accumulator each.  A group works on CRF_RAYS list entries side by side (template parameter): the entries' chains
+// (delta -> sigma and features -> weight) are independent, so each of a step's two load rounds has CRF_RAYS rows in flight per lane instead of
+// one.  Every lane runs the scalar recurrence of its entries (the sigma / delta loads are one address per group), so nothing crosses lanes:
+// no LDS, no atomics, a fixed order.  The busy lanes of a group read C consecutive elements per entry and step, a ray's steps and a wave's
+// entries follow each other in memory -- where one lane per ray would stride by n_step * C.
+// CRF_RAYS per channel count (ngp_composite_rays_features' launch; measured): 1 below 16 channels, where the kernel is bound by
+// its instructions and a second chain only adds exec-mask regions; 2 from 16; 4 at 64, where a step's rows are whole 256-byte wave loads; above 64
+// the channel blocks already put NB loads per entry in flight: NB x CRF_RAYS stays 4 (2 x 2, 4 x 1; not measured separately).
+template <typename F, int NB, int CRF_RAYS>
+__global__ __launch_bounds__(RM_THREADS) void k_composite_rays_feat(uint32_t n_alive, uint32_t n_step, float T_thresh, const int32_t* __restrict__ rays_alive,
+                                                                    const float* __restrict__ sigmas, const F* __restrict__ feats,
+                                                                    const float* __restrict__ deltas, const float* __restrict__ weights_sum, uint32_t C,
+                                                                    uint32_t lp, float* out, const int32_t* __restrict__ dev_state, uint32_t n_total,
+                                                                    uint32_t n_step_cap) {
+    const uint32_t t = blockIdx.x * RM_THREADS + threadIdx.x;
+    if (dev_state) {
+        n_alive = (uint32_t)dev_state[0];
+        n_step = loop_n_step(n_total, n_alive, n_step_cap);
+    }
+    // a workgroup's groups take its entries in CRF_RAYS rounds: entry = (block * CRF_RAYS + k) * groups per block + group -- the groups of a
+    // wave hold neighbouring entries in every round, so a load instruction covers the addresses it covers with one entry per group
+    const uint32_t per_block = RM_THREADS >> lp;
+    const uint32_t first = blockIdx.x * CRF_RAYS * per_block + (threadIdx.x >> lp), c = t & ((1u << lp) - 1u);
+    if (first >= n_alive || c >= C) return;
+    const float* sg[CRF_RAYS];
+    const float* de[CRF_RAYS];
+    const F* ft[CRF_RAYS];
+    float* o[CRF_RAYS];
+    float ws[CRF_RAYS], acc[CRF_RAYS][NB];
+    bool listed[CRF_RAYS], live[CRF_RAYS];
+#pragma unroll
+    for (int k = 0; k < CRF_RAYS; k++) {
+        const uint32_t n = first + k * per_block;
+        listed[k] = live[k] = n < n_alive;
+        const uint32_t index = listed[k] ? (uint32_t)rays_alive[n] : 0u;
+        sg[k] = sigmas + (size_t)n * n_step;
+        de[k] = deltas + (size_t)n * n_step * 2;
+        ft[k] = feats + (size_t)n * n_step * C + c;
+        o[k] = out + (size_t)index * C + c;
+        ws[k] = listed[k] ? weights_sum[index] : 0.0f;
+#pragma unroll
+        for (int b = 0; b < NB; b++) acc[k][b] = (listed[k] && (NB == 1 || b * 64u + c < C)) ? o[k][b * 64] : 0.0f;
+    }
+    // per step two load rounds, each for all entries at once: the deltas; then, for the entries whose d0 is not 0, sigma and the feature row
+    // (a row at or behind an entry's break is never read: `live` goes false at the break and guards every load)
+    for (uint32_t step = 0; step < n_step; step++) {
+        float d0[CRF_RAYS], s[CRF_RAYS], f[CRF_RAYS][NB];
+#pragma unroll
+        for (int k = 0; k < CRF_RAYS; k++) d0[k] = live[k] ? de[k][step * 2] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < CRF_RAYS; k++) live[k] = live[k] && !(d0[k] == 0.0f);
+#pragma unroll
+        for (int k = 0; k < CRF_RAYS; k++) {
+            s[k] = live[k] ? sg[k][step] : 0.0f;
+#pragma unroll
+            for (int b = 0; b < NB; b++) f[k][b] = (live[k] && (NB == 1 || b * 64u + c < C)) ? (float)ft[k][(size_t)step * C + b * 64] : 0.0f;
+        }
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < CRF_RAYS; k++) {
+            if (live[k]) {
+                const float alpha = 1.0f - __expf(-s[k] * d0[k]);
+                const float T = 1.0f - ws[k];
+                const float w = alpha * T;
+                ws[k] += w;
+#pragma unroll
+                for (int b = 0; b < NB; b++)
+                    if (NB == 1 || b * 64u + c < C) acc[k][b] = __fadd_rn(acc[k][b], __fmul_rn(w, f[k][b]));
+                if (T < T_thresh) live[k] = false;
+            }
+            any = any || live[k];
+        }
+        if (!any) break;
+    }
+#pragma unroll
+    for (int k = 0; k < CRF_RAYS; k++)
+#pragma unroll
+        for (int b = 0; b < NB; b++)
+            if (listed[k] && (NB == 1 || b * 64u + c < C)) o[k][b * 64] = acc[k][b];
+}
+
 // ---------------------------------------------------------------------------------------------
 // order-preserving compaction of the alive list (extension; replaces a host-side boolean index)
 // workspace (uint32): per-block survivor counts
@@ -2197,6 +2284,50 @@ extern "C" int ngp_composite_rays_dev(const int32_t* state, uint32_t alive_bound
     RM_LAUNCH_1D(k_composite_rays, alive_bound, as_stream(stream), alive_bound, 1u, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas,
                  weights_sum, depth, image, state, n_total, n_step_cap);
     return check_launch("composite_rays_dev");
+}
+
+// the launch of k_composite_rays_feat behind both entries (dev_state == NULL: the host's n_alive / n_step)
+static int launch_composite_rays_feat(const char* fn, uint32_t lanes, uint32_t n_step, float T_thresh, const int32_t* rays_alive, const float* sigmas,
+                                      const void* feats, const float* deltas, const float* weights_sum, uint32_t C, int feat_dtype, float* out,
+                                      const int32_t* dev_state, uint32_t n_total, uint32_t n_step_cap, ngp_stream_t stream) {
+    const uint32_t lp = C >= 64u ? 6u : feat_log2_segment(C);
+    NGP_REQUIRE(((uint64_t)lanes << lp) <= 0xffffffffull - RM_THREADS, NGP_ERR_INVALID, "%s: %u list entries of %u lanes each do not fit one launch", fn,
+                lanes, 1u << lp);
+#define NGP_RAYS_FEAT(F, NB, K)                                                                                                                  \
+    RM_LAUNCH_1D((k_composite_rays_feat<F, NB, K>), cdiv(lanes, (uint32_t)K) << lp, as_stream(stream), lanes, n_step, T_thresh, rays_alive, sigmas, \
+                 static_cast<const F*>(feats), deltas, weights_sum, C, lp, out, dev_state, n_total, n_step_cap)
+#define NGP_RAYS_FEAT_NB(F)                                                                                                                      \
+    do {                                                                                                                                         \
+        if (C < 16u) NGP_RAYS_FEAT(F, 1, 1); else if (C < 64u) NGP_RAYS_FEAT(F, 1, 2); else if (C == 64u) NGP_RAYS_FEAT(F, 1, 4);                \
+        else if (C <= 128u) NGP_RAYS_FEAT(F, 2, 2); else NGP_RAYS_FEAT(F, 4, 1);                                                                 \
+    } while (0)
+    if (feat_dtype == NGP_F16) NGP_RAYS_FEAT_NB(_Float16); else NGP_RAYS_FEAT_NB(float);
+#undef NGP_RAYS_FEAT_NB
+#undef NGP_RAYS_FEAT
+    return check_launch(fn);
+}
+
+extern "C" int ngp_composite_rays_features(uint32_t n_alive, uint32_t n_step, float T_thresh, const int32_t* rays_alive, const float* sigmas,
+                                           const void* feats, const float* deltas, const float* weights_sum, uint32_t C, int feat_dtype,
+                                           float* out, ngp_stream_t stream) {
+    const int rc = feat_args_ok("composite_rays_features", C, feat_dtype);
+    if (rc != NGP_OK) return rc;
+    if (n_alive == 0) return NGP_OK;
+    NGP_REQUIRE(rays_alive && sigmas && feats && deltas && weights_sum && out, NGP_ERR_INVALID, "composite_rays_features: NULL tensor");
+    return launch_composite_rays_feat("composite_rays_features", n_alive, n_step, T_thresh, rays_alive, sigmas, feats, deltas, weights_sum, C,
+                                      feat_dtype, out, nullptr, 0u, 0u, stream);
+}
+
+extern "C" int ngp_composite_rays_features_dev(const int32_t* state, uint32_t alive_bound, uint32_t n_total, uint32_t n_step_cap, float T_thresh,
+                                               const int32_t* rays_alive, const float* sigmas, const void* feats, const float* deltas,
+                                               const float* weights_sum, uint32_t C, int feat_dtype, float* out, ngp_stream_t stream) {
+    const int rc = feat_args_ok("composite_rays_features_dev", C, feat_dtype);
+    if (rc != NGP_OK) return rc;
+    NGP_REQUIRE(n_step_cap <= 1024u, NGP_ERR_INVALID, "composite_rays_features_dev: n_step_cap must be in [0, 1024] (0 = the reference's 8)");
+    if (alive_bound == 0) return NGP_OK;
+    NGP_REQUIRE(state && rays_alive && sigmas && feats && deltas && weights_sum && out, NGP_ERR_INVALID, "composite_rays_features_dev: NULL tensor");
+    return launch_composite_rays_feat("composite_rays_features_dev", alive_bound, 1u, T_thresh, rays_alive, sigmas, feats, deltas, weights_sum, C,
+                                      feat_dtype, out, state, n_total, n_step_cap, stream);
 }
 
 /* compaction + loop bookkeeping: out_alive / out_state {n_alive, steps marched} describe the next iteration; the count becomes 0 once

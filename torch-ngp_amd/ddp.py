@@ -107,6 +107,9 @@ def render_sharded(model, rays_o, rays_d, rank=None, world=None, group=None, **k
     with dt_gamma = 0 can need more than max_steps) is cut off at a different sample when the frame is sharded."""
     if kwargs.get('aux') is not None:
         raise NotImplementedError("render_sharded(aux=...): the sharded frame gathers image and depth only; the 'aux' channels are a training output")
+    if kwargs.get('aux_infer') is not None:
+        raise NotImplementedError("render_sharded(aux_infer=...): the sharded frame gathers image and depth only (a rank without rays would "
+                                  "not know the channel count of 'aux'); render the frame on one rank")
     rank = dist.get_rank(group) if rank is None else rank
     world = dist.get_world_size(group) if world is None else world
     n = rays_o.shape[-2]

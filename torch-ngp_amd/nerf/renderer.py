@@ -179,7 +179,7 @@ class NeRFRenderer(nn.Module):
         return bool(probe(dummy, dummy)) and torch.is_grad_enabled()
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
-                 T_thresh=1e-4, geo=False, aux=None, **kwargs):
+                 T_thresh=1e-4, geo=False, aux=None, aux_infer=None, **kwargs):
         # rays_o, rays_d [B, N, 3] (B == 1) -> {'image' [B,N,3], 'depth' [B,N], ('weights_sum' when training)}
         # geo (extension, training only): composite with raymarching.composite_rays_train_geo -- 'depth' becomes differentiable
         # and the results gain 'depth_raw' [N] (the compositor's un-normalised depth) and 'distortion' [N] (EffDistLoss per ray / (far - near))
@@ -187,7 +187,16 @@ class NeRFRenderer(nn.Module):
         # results gain 'aux' [N,C], its raw composite under the rays' weights (raymarching.composite_rays_train_features, no background blend)
         if aux is not None and not self.training:
             raise NotImplementedError("render(aux=...): the 'aux' channels are composited by the training compositor only (model.train()); the "
-                                      "inference loop has no feature compositor")
+                                      "inference loop has no feature compositor for this contract -- an eval frame takes aux_infer=fn "
+                                      "(called once per loop iteration, no gradient graph)")
+        # aux_infer (extension, eval only): a callable (xyzs [R,3], dirs [R,3], sigmas [R] fp32 density-scaled, rgbs [R,3] fp32)
+        # -> [R,C] fp32 or fp16, 1 <= C <= 256, called once per loop iteration on the iteration's padded row buffers (rows behind the marched
+        # ones hold zero deltas and arbitrary values; their outputs are never read); the results gain 'aux' [*lead, C] fp32, its raw composite
+        # under the frame's weights (raymarching.composite_rays_features, no background blend).  A new keyword, not aux=: that one keeps
+        # raising in eval, and its callable is called once on all samples with a gradient graph.
+        if aux_infer is not None and self.training:
+            raise ValueError("render(aux_infer=...): aux_infer is the eval frame's keyword (model.eval()); a training render composites the "
+                             "caller's channels with aux=fn")
         lead = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -254,11 +263,12 @@ class NeRFRenderer(nn.Module):
             depth = torch.zeros(n_rays, dtype=torch.float32, device=dev)
             image = torch.zeros(n_rays, 3, dtype=torch.float32, device=dev)
             rays_t = nears.clone()
+            aux_frame = {'out': None} if aux_infer is not None else None   # 'out' [N,C]: zeros at the callable's first call of the frame
             from fused import pinned_half_weights
             with pinned_half_weights(self):  # one fp16 cast of the parameters per frame instead of one per loop iteration
                 if getattr(self, 'device_loop', True):
                     self._render_loop_on_device(rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image, perturb, dt_gamma, max_steps,
-                                                T_thresh)
+                                                T_thresh, aux_infer=aux_infer, aux_frame=aux_frame)
                 else:  # the reference's host-driven loop (renderer.py:341-367): one device->host read-back per iteration
                     rays_alive = torch.arange(n_rays, dtype=torch.int32, device=dev)
                     step = 0
@@ -272,18 +282,45 @@ class NeRFRenderer(nn.Module):
                             self.grid_size, nears, fars, 128, perturb if step == 0 else False, dt_gamma, max_steps)
                         sigmas, rgbs = self(xyzs, dirs)
                         sigmas = self.density_scale * sigmas
+                        if aux_infer is not None:   # the fp32 tensors composite_rays' cast would make: both ops read the same values
+                            sigmas, rgbs = sigmas.float().contiguous(), rgbs.float().contiguous()
+                            feats = self._aux_infer_feats(aux_infer, aux_frame, xyzs, dirs, sigmas, rgbs, n_rays)
+                            raymarching.composite_rays_features(n_alive, n_step, rays_alive, sigmas, feats, deltas, weights_sum, aux_frame['out'],
+                                                                T_thresh)
                         raymarching.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image,
                                                    T_thresh)
                         rays_alive = rays_alive[rays_alive >= 0]
                         step += n_step
             image, depth = self._finish(image, depth, weights_sum, bg_color, nears, fars, lead)
+            if aux_infer is not None:
+                out = aux_frame['out']   # (None: a frame without a loop iteration, i.e. without rays -- no call, no channel count)
+                results['aux'] = torch.zeros(*lead, 0, dtype=torch.float32, device=dev) if out is None else out.view(*lead, out.shape[1])
 
         results['depth'] = depth
         results['image'] = image
         return results
 
+    @staticmethod
+    def _aux_infer_feats(fn, frame, xyzs, dirs, sigmas, rgbs, n_rays):
+        """one call of an eval frame's aux_infer callable on an iteration's row buffers -> feats [R,C] (detached, contiguous, fp32 or fp16);
+        the first call of the frame fixes C and the dtype and allocates frame['out'] [n_rays,C] as zeros"""
+        with torch.no_grad():
+            feats = fn(xyzs, dirs, sigmas, rgbs)
+        if not torch.is_tensor(feats) or feats.dim() != 2 or feats.shape[0] != xyzs.shape[0] or not 1 <= feats.shape[1] <= 256:
+            raise ValueError(f"render(aux_infer=...): the callable must return a [{xyzs.shape[0]}, C] tensor with 1 <= C <= 256 (got "
+                             f"{tuple(feats.shape) if torch.is_tensor(feats) else type(feats).__name__})")
+        if feats.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"render(aux_infer=...): the callable must return float32 or float16 (got {feats.dtype})")
+        if frame['out'] is None:
+            frame['out'] = torch.zeros(n_rays, feats.shape[1], dtype=torch.float32, device=xyzs.device)
+            frame['dtype'] = feats.dtype
+        elif feats.shape[1] != frame['out'].shape[1] or feats.dtype != frame['dtype']:
+            raise ValueError(f"render(aux_infer=...): every call of a frame must return the same C and dtype (first call: C = "
+                             f"{frame['out'].shape[1]}, {frame['dtype']}; this call: C = {feats.shape[1]}, {feats.dtype})")
+        return feats.detach().contiguous()
+
     def _render_loop_on_device(self, rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image, perturb, dt_gamma, max_steps, T_thresh,
-                               sync_every=8):
+                               sync_every=8, aux_infer=None, aux_frame=None):
         """the eval loop of run_cuda (renderer.py:341-367) with its state on the device (extension): the alive count,
         the per-iteration n_step = max(min(N // n_alive, 8), 1) and the marched-step total live in a device word pair that the march /
         composite / compaction kernels read, so the host issues `sync_every` iterations back to back and reads the count back once per
@@ -301,8 +338,12 @@ class NeRFRenderer(nn.Module):
         800x800, transparent / opaque frame): host-driven loop 26.0 / 2.2 ms, device state with the reference's n_step rule 21.3 / 1.93 ms,
         + graphs 21.3 / 2.0 ms (the frame is bound by its kernels, not by launches: graphs are off by default), device state with the adaptive
         row budget below (`adaptive_n_step`, default) 17.3 / 1.95 ms.  `_loop_debug = []` collects (iterations done, alive bound, boost,
-        survival per iteration) at every read-back (tools/render_loop_trace.py)."""
+        survival per iteration) at every read-back (tools/render_loop_trace.py).
+        aux_infer / aux_frame (run_cuda): the caller's channels, composited into aux_frame['out'] by
+        composite_rays_features_dev in front of every composite_rays_dev.  A Python callable cannot be issued from C or captured: the native
+        pair call and graph_loop are declined for such a frame; culling, the adaptive row budget and the tail cap stay."""
         from raymarching.raymarching import _backend as rb   # compiled binding when built, else ctypes (same C ABI)
+        from raymarching import backend as rf                # (the feature compositor's entries are ctypes-only)
         import _ngp_capi as capi
         n_rays, dev = rays_o.shape[0], rays_o.device
         key = (n_rays, str(dev), float(dt_gamma), int(max_steps), float(T_thresh), float(self.density_scale), self.density_bitfield.data_ptr(),
@@ -318,7 +359,7 @@ class NeRFRenderer(nn.Module):
             self._loop_cache = cache
         # static buffers (the graphs hold their addresses): this frame's inputs and accumulators are copied in, the results copied out --
         # only with graph_loop; the eager loop works on the caller's tensors (eleven 4-us copy launches per frame less)
-        static = bool(getattr(self, 'graph_loop', False)) and not cache['failed']
+        static = bool(getattr(self, 'graph_loop', False)) and not cache['failed'] and aux_infer is None
         frame = tuple(t.contiguous() for t in (rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image))
         static = static or any(a is not b for a, b in zip(frame[5:], (weights_sum, depth, image)))   # (accumulators must be updated in place)
         if static:
@@ -380,6 +421,10 @@ class NeRFRenderer(nn.Module):
             else:
                 sigmas, rgbs = stage('network (encoder + MLPs + glue)', lambda: self(xyzs, dirs))
                 sigmas, rgbs32 = stage('casts (density_scale, fp32 copies)', lambda: ((self.density_scale * sigmas).float().contiguous(), rgbs.float().contiguous()))
+            if aux_infer is not None:   # before composite_rays_dev: the feature kernel reads the weights_sum that call advances
+                feats = stage('aux_infer (the caller\'s channels)', lambda: self._aux_infer_feats(aux_infer, aux_frame, xyzs, dirs, sigmas, rgbs32, n_rays))
+                stage('composite_rays_features', lambda: rf.composite_rays_features_dev(state[cur], lanes, n_total, cap, T_thresh, alive[cur], sigmas, feats,
+                                                                                        deltas, s_ws, aux_frame['out']))
             stage('composite_rays', lambda: rb.composite_rays_dev(state[cur], lanes, n_total, cap, T_thresh, alive[cur], s_t, sigmas, rgbs32, deltas, s_ws,
                                                                   s_depth, s_image))
             stage('compact_rays', lambda: rb.compact_rays_dev(state[cur], lanes, n_total, cap, max_steps, alive[cur], alive[1 - cur], state[1 - cur], ws))
@@ -393,7 +438,7 @@ class NeRFRenderer(nn.Module):
         # (tests/test_gpu_pipeline.py).  Taken when the network call would run the fused inference path on pinned fp16 weights and nobody is
         # probing the stages; `native_loop = False` keeps the per-stage calls.
         native = None
-        if (getattr(self, 'native_loop', True) and getattr(self, '_loop_probe', None) is None and getattr(self, '_loop_iter_hook', None) is None
+        if (getattr(self, 'native_loop', True) and aux_infer is None and getattr(self, '_loop_probe', None) is None and getattr(self, '_loop_iter_hook', None) is None
                 and hasattr(self, 'forward_scaled') and hasattr(capi.lib, 'ngp_render_iterations_dev')):
             import ctypes
             import fused
@@ -456,7 +501,7 @@ class NeRFRenderer(nn.Module):
         noises = torch.rand(n_rays, dtype=torch.float32, device=dev) if perturb else None
         pair(n_rays, full, noises, ib * n_rays)
         done = 2
-        use_graphs = getattr(self, 'graph_loop', False) and not cache['failed']
+        use_graphs = getattr(self, 'graph_loop', False) and not cache['failed'] and aux_infer is None
         adaptive = getattr(self, 'adaptive_n_step', True) and not use_graphs
         batch = 2
         bound_alive = int(state[0, 0].item())
@@ -707,6 +752,9 @@ class NeRFRenderer(nn.Module):
         if kwargs.get('aux') is not None and (staged or not self.cuda_ray):
             raise NotImplementedError("render(aux=...): the 'aux' channels need the cuda_ray training render; the staged / non-cuda_ray path "
                                       "does not composite them")
+        if kwargs.get('aux_infer') is not None and not self.cuda_ray:
+            raise NotImplementedError("render(aux_infer=...): the 'aux' channels of an eval frame are composited by the cuda_ray inference loop; "
+                                      "the non-cuda_ray path does not composite them")
         if self.cuda_ray:
             return self.run_cuda(rays_o, rays_d, **kwargs)
         if not staged:

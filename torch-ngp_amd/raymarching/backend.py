@@ -272,6 +272,29 @@ def composite_rays_dev(state, alive_bound, n_total, n_step_cap, T_thresh, rays_a
                                                capi.ptr(image), capi.stream()))
 
 
+def composite_rays_features(n_alive, n_step, T_thresh, rays_alive, sigmas, feats, deltas, weights_sum, out):
+    """extension (include/ngp_hip.h, ngp_composite_rays_features): out [N,C] += the composite of feats [>= n_alive * n_step, C] (float32 or
+    float16, converted at the load) over the samples composite_rays is about to composite -- called BEFORE it on the same rows.  ctypes-only,
+    like the training feature entries."""
+    for t, n in ((sigmas, 'sigmas'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (out, 'out')):
+        _f32(t, n)
+    _i32(rays_alive, 'rays_alive')
+    capi.check(capi.lib.ngp_composite_rays_features(n_alive, n_step, float(T_thresh), capi.ptr(rays_alive), capi.ptr(sigmas),
+                                                    capi.ptr(capi.dense(feats, 'feats')), capi.ptr(deltas), capi.ptr(weights_sum), out.shape[-1],
+                                                    _feat_code(feats, 'feats'), capi.ptr(out), capi.stream()))
+
+
+def composite_rays_features_dev(state, alive_bound, n_total, n_step_cap, T_thresh, rays_alive, sigmas, feats, deltas, weights_sum, out):
+    """extension (ngp_composite_rays_features_dev): composite_rays_features with the alive count / n_step taken from the device `state`"""
+    for t, n in ((sigmas, 'sigmas'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (out, 'out')):
+        _f32(t, n)
+    _i32(rays_alive, 'rays_alive'); _i32(state, 'state')
+    capi.check(capi.lib.ngp_composite_rays_features_dev(capi.ptr(state), alive_bound, n_total, n_step_cap, float(T_thresh), capi.ptr(rays_alive),
+                                                        capi.ptr(sigmas), capi.ptr(capi.dense(feats, 'feats')), capi.ptr(deltas),
+                                                        capi.ptr(weights_sum), out.shape[-1], _feat_code(feats, 'feats'), capi.ptr(out),
+                                                        capi.stream()))
+
+
 def compact_rays_dev(state, alive_bound, n_total, n_step_cap, max_steps, rays_alive, out_alive, out_state, workspace):
     _i32(rays_alive, 'rays_alive'); _i32(out_alive, 'out_alive'); _i32(out_state, 'out_state'); _i32(state, 'state')
     capi.check(capi.lib.ngp_compact_rays_dev(capi.ptr(state), alive_bound, n_total, n_step_cap, max_steps, capi.ptr(rays_alive), capi.ptr(out_alive),

@@ -22,7 +22,7 @@ except ImportError:
 from . import backend as _geo  # the geometry compositor's entries are ctypes-only: the compiled module's table is the reference's
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'packbits_capped', 'march_rays_train',
-           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'march_rays', 'composite_rays', 'compact_rays', 'update_density_grid', 'density_grid_state']
+           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'march_rays', 'composite_rays', 'composite_rays_features', 'compact_rays', 'update_density_grid', 'density_grid_state']
 
 _f32_fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 
@@ -350,6 +350,31 @@ class _composite_rays(Function):
 
 
 composite_rays = _composite_rays.apply
+
+
+def composite_rays_features(n_alive, n_step, rays_alive, sigmas, feats, deltas, weights_sum, out, T_thresh=1e-2):
+    """Extension (not in the reference): the caller's per-sample channels in the inference loop.  out [N,C] float32 is updated
+    in place, out[rays_alive[n], c] += sum of w * feats[n * n_step + step, c] over the samples composite_rays composites for list entry n,
+    with that op's weights (the same statements: with feats = rgbs the bits of its image, with a channel of ones those of weights_sum).
+    CALL ORDER: before composite_rays of the same rows -- it reads the weights_sum that call advances, and changes nothing but `out`
+    (rays_alive, rays_t, weights_sum stay as they are).  No background is blended in.
+    feats [>= n_alive * n_step, C], contiguous, float32 or float16, 1 <= C <= 256: float16 stays float16 (also under autocast; converted at the
+    load, accumulated in float32).  sigmas / deltas / weights_sum are taken as float32.  float64 is not provided.  No autograd: feats is
+    detached.  Rows at or behind a ray's end (deltas == 0, or behind the sample that crosses T_thresh) are not read."""
+    for t, name in ((sigmas, 'sigmas'), (feats, 'feats'), (deltas, 'deltas'), (weights_sum, 'weights_sum'), (out, 'out')):
+        if t.dtype == torch.float64:
+            raise TypeError(f"composite_rays_features: {name} is float64; the inference feature compositor takes float32 (feats: float32 or float16)")
+    feats = feats.detach()
+    if feats.dtype != torch.float16:  # no custom_fwd cast: it would up-cast float16 features
+        feats = feats.float()
+    if feats.dim() != 2 or out.dim() != 2 or feats.shape[1] != out.shape[1] or feats.shape[0] < n_alive * n_step:
+        raise RuntimeError(f"composite_rays_features: feats must be [>= {n_alive * n_step}, C] and out [N, C] (got {tuple(feats.shape)}, "
+                           f"{tuple(out.shape)})")
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise RuntimeError("composite_rays_features: out must be a contiguous float32 tensor (it is updated in place)")
+    _geo.composite_rays_features(n_alive, n_step, T_thresh, rays_alive, sigmas.detach().float().contiguous(), feats.contiguous(),
+                                 deltas.detach().float().contiguous(), weights_sum.detach().float().contiguous(), out)
+    return out
 
 
 def compact_rays(rays_alive, n_alive=None):
