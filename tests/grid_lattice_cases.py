@@ -427,3 +427,92 @@ def ray_case(D, C, dtype, gridtype, align, interp, log2_size):
     for a in (x, g, offs, ref, A, hits):
         a.setflags(write=False)
     return dict(x=x, g=g, offs=offs, S=S, H=H, ref=ref, A=A, hits=hits, zeroed=zeroed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# (f) exact sums at ONE level of a table whose scales are no powers of two (tests/test_gpu_grid_backward_paths.py: the level that takes
+# the atomics in a launch of the record sort)
+# ---------------------------------------------------------------------------------------------------------------------
+def half_lattice_coordinates(scale):
+    """the float32 coordinates x in [0, 1] whose position fma(x, scale, 0.5) at a level of (float32) scale `scale` is EXACTLY a multiple of
+    1/2.  x = m / (2 scale) is not representable in general; the fma's single rounding snaps most of them onto the half lattice, and the ones
+    it does not are left out.  (x * scale + 0.5 is exact in float64 for a float32 x and scale: its rounding to float32 is the fma's result.)"""
+    scale = np.float32(scale)
+    m = np.arange(0, int(np.floor(2.0 * float(scale))) + 1)
+    x = (m / (2.0 * float(scale))).astype(np.float32)
+    pos = (x.astype(np.float64) * float(scale) + 0.5).astype(np.float32).astype(np.float64)
+    keep = (x <= 1.0) & (pos * 2.0 == np.rint(pos * 2.0))
+    return x[keep]
+
+
+@functools.lru_cache(maxsize=None)
+def level_lattice(B, D, scale, seed):
+    """x [B, D] float32 on the half lattice of the level with this scale (every corner weight there is a multiple of 2^-D) and gradient
+    numerators J [B, 2] (the gradient is J * 2^-6): a walk over the lattice as in _walk (stay / step / jump), a stretch of 130 identical
+    points starting at 5 mod 64, runs of 8, 9, 16, 17 and 32 samples on one point, 5 % exactly-zero gradients, one point outside the unit cube.
+    Every contribution at that level is a multiple of level_lattice_unit(D): sums in any order are exact in fp16 while they stay below the
+    cap -- level_lattice_exact says whether they do."""
+    rng = np.random.default_rng(7000 + seed)
+    coord = half_lattice_coordinates(scale)
+    n = len(coord)
+    assert n >= 8
+    K, J = [], []
+    pos = rng.integers(0, n, D)
+
+    def step():
+        nonlocal pos
+        u = rng.random()
+        if u >= 0.95:
+            pos = rng.integers(0, n, D)
+        elif u >= 0.55:
+            pos = pos.copy()
+            d = rng.integers(D)
+            pos[d] = min(n - 1, max(0, pos[d] + (1 if rng.random() < 0.5 else -1)))
+        j = rng.integers(-2, 3, 2)
+        if not j.any():
+            j[rng.integers(2)] = rng.choice([-1, 1])
+        K.append(pos)
+        J.append(j if rng.random() >= 0.05 else np.zeros(2, np.int64))
+
+    for _ in range(69):
+        step()
+    here = rng.integers(0, n, D)
+    for _ in range(130):
+        K.append(here)
+        J.append(rng.choice([-1, 1], 2))
+    for length in (8, 9, 16, 17, 32):
+        while len(K) % 8 != 7:
+            step()
+        here = rng.integers(0, n, D)
+        for _ in range(length):
+            j = rng.integers(-2, 3, 2)
+            K.append(here)
+            J.append(np.where(j == 0, 1, j))
+    while len(K) < B:
+        step()
+    x = coord[np.array(K[:B])]
+    x[40, 0] = np.nextafter(np.float32(1.0), np.float32(2.0))   # outside: no contribution anywhere
+    J = np.array(J[:B], np.int64)
+    x.setflags(write=False)
+    J.setflags(write=False)
+    return x, J
+
+
+def level_lattice_unit(D):
+    return 2.0 ** -6 / 2 ** D
+
+
+def level_lattice_exact(x, g_level, offs, level, S, H, gridtype=0):
+    """from the oracle alone: at `level` every sum is an integer multiple of the unit, and sum|contribution| stays below 3/4 of the fp16 cap
+    (2^11 units) in every entry -- then any order of fp16 additions, merged into runs or not, gives the same bits.  Returns the largest
+    sum|contribution| in units."""
+    L, D = len(offs) - 1, x.shape[1]
+    g = np.zeros((L,) + g_level.shape, np.float32)
+    g[level] = g_level
+    n = int(offs[-1])
+    ref, _ = oracle.grid_backward(g, x, offs, n, 2, S, H, gridtype=gridtype)
+    A, _ = oracle.grid_backward(np.abs(g), x, offs, n, 2, S, H, gridtype=gridtype)
+    unit = level_lattice_unit(D)
+    assert np.array_equal(ref / unit, np.rint(ref / unit)), 'a contribution off the lattice'
+    assert A.max() / unit < 0.75 * 2 ** 11, 'sums leave the range in which fp16 holds every multiple of the unit'
+    return A.max() / unit

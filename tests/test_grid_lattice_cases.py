@@ -95,3 +95,26 @@ def test_ray_cases_have_long_hit_lists_and_normal_fp16_contributions(D, C, dtype
         assert 0 < rc['zeroed'] <= 0.01 * 3 * 4096
         assert A.max() < 65504 / 4
     assert {c[5] for c in glc.RAY_CASES} == {0, 1} and {c[3] for c in glc.RAY_CASES} == {0, 1} and {c[4] for c in glc.RAY_CASES} == {False, True}
+
+
+@pytest.mark.parametrize('name,level', [('T3', 1), ('T1', 0)])
+def test_level_lattice_inputs_are_exact_at_their_level(name, level):
+    """the inputs of tests/test_gpu_grid_backward_paths.py for calls with an atomic level: positions exactly on the half lattice of that level
+    (whose scale is no power of two), sums there in multiples of the unit and below the fp16 cap, runs longer than a DPP row"""
+    import grid_backward_path_cases as pc
+    tab = pc.table(name)
+    scale = np.float32(pc.level_scale(tab, level))
+    for B in pc.BATCHES:
+        x, g = pc.lattice_inputs(name, B, level)          # (asserts level_lattice_exact)
+        inside = np.all((x >= 0) & (x <= 1), axis=1)
+        pos = (x[inside].astype(np.float64) * float(scale) + 0.5).astype(np.float32).astype(np.float64)
+        assert np.array_equal(pos * 2, np.rint(pos * 2)) and (~inside).sum() == 1
+        units = g[level] / 2.0 ** -6
+        assert np.array_equal(units, np.rint(units)) and np.abs(units).max() == 2 and (units == 0).all(axis=1).mean() > 0.02
+        same = np.all(x[1:] == x[:-1], axis=1)
+        run = best = 0
+        for s in same:
+            run = run + 1 if s else 0
+            best = max(best, run)
+        assert best >= 129
+        assert glc.level_lattice_exact(x, g[level], tab['offs'], level, tab['S'], tab['H']) > 64   # entries that many contributions meet in

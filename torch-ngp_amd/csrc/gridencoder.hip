@@ -510,9 +510,12 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_corner_indices(const float
 // backward (scatter-add into grad_embeddings)
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void atomic_add_feat(float* p, float v) { unsafeAtomicAdd(p, v); }
-__device__ __forceinline__ void atomic_add_pk(half_t* p, float a, float b) {
-    half2_t v = {(half_t)a, (half_t)b};
-    (void)__builtin_amdgcn_flat_atomic_fadd_v2f16(reinterpret_cast<half2_t*>(p), v);  // global_atomic_pk_add_f16
+__device__ __forceinline__ uint32_t pack_half2(float a, float b) {
+    const half2_t h = {(half_t)a, (half_t)b};
+    return __builtin_bit_cast(uint32_t, h);
+}
+__device__ __forceinline__ void atomic_add_packed(half_t* p, uint32_t packed) {  // global_atomic_pk_add_f16
+    (void)__builtin_amdgcn_flat_atomic_fadd_v2f16(reinterpret_cast<half2_t*>(p), __builtin_bit_cast(half2_t, packed));
 }
 // fp16 table with odd C (C == 1): emulate with a 32-bit CAS on the containing word (the reference
 // routes this case to a slow scalar half atomicAdd; under autocast the wrapper never produces it).
@@ -553,7 +556,7 @@ __device__ __forceinline__ void scatter_add(T* dst, const float (&g)[C], float w
     if constexpr (sizeof(T) == 2) {
         if constexpr (C % 2 == 0) {
 #pragma unroll
-            for (int c = 0; c < C; c += 2) atomic_add_pk(reinterpret_cast<half_t*>(dst) + c, w * g[c], w * g[c + 1]);
+            for (int c = 0; c < C; c += 2) atomic_add_packed(reinterpret_cast<half_t*>(dst) + c, pack_half2(w * g[c], w * g[c + 1]));
         } else {
 #pragma unroll
             for (int c = 0; c < C; c++) atomic_add_half1(reinterpret_cast<half_t*>(dst) + c, w * g[c]);
@@ -631,28 +634,34 @@ struct BwdSample {
     }
 };
 
-// DPP row shifts (VALU, no LDS traffic): lane i of each 16-lane row reads lane i -/+ N of the SAME row; a lane without a source reads 0
+// DPP primitives of the backward (VALU, no LDS traffic; profiles/r01_dpp_probe.txt).  Row shift: lane i of each 16-lane row reads lane i - N of
+// the SAME row; a lane without a source reads 0.  wave_shr1 / wave_shl1: lane i reads lane i -/+ 1 across the whole wave; lane 0 / 63 reads 0.
 template <int N>
-__device__ __forceinline__ uint32_t row_shr(uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x110 + N, 0xF, 0xF, true);
-}
+__device__ __forceinline__ uint32_t row_shr(uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x110 + N, 0xF, 0xF, true); }
 template <int N>
-__device__ __forceinline__ uint32_t row_shl(uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x100 + N, 0xF, 0xF, true);
+__device__ __forceinline__ float row_shr_f(float src) { return __builtin_bit_cast(float, row_shr<N>(__builtin_bit_cast(uint32_t, src))); }
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x138, 0xF, 0xF, false); }
+__device__ __forceinline__ uint32_t wave_shl1(uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x130, 0xF, 0xF, false); }
+// Carries between the rows: row_bcast:15 hands lane 15 of a row to every lane of the NEXT row, row_bcast:31 hands lane 31 to every lane of rows
+// 2 and 3; the row mask keeps the other rows at `old` = 0.  row_bcast:15 comes in two forms: row mask 0xE (rows 1..3 read the row below; row 0
+// unused) for the run merge, which chains the rows one carry round at a time, and row mask 0xA (rows 1 and 3 only) for the scans below, where
+// row_bcast:31 then brings rows 2 and 3 the total of rows 0..1.
+__device__ __forceinline__ uint32_t row_bcast15(uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x142, 0xE, 0xF, false); }
+__device__ __forceinline__ uint32_t bcast15_rows13(uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x142, 0xA, 0xF, false); }
+__device__ __forceinline__ uint32_t bcast31_rows23(uint32_t src) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x143, 0xC, 0xF, false); }
+// Inclusive scan over the 64 lanes of a wave (Hillis-Steele: four row shifts, two broadcast carries); 0 is the identity of both operations
+template <typename Op>
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, Op op) {
+    v = op(v, row_shr<1>(v));
+    v = op(v, row_shr<2>(v));
+    v = op(v, row_shr<4>(v));
+    v = op(v, row_shr<8>(v));
+    v = op(v, bcast15_rows13(v));
+    return op(v, bcast31_rows23(v));
 }
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t src) {  // lane i reads lane i-1 across the whole wave; lane 0 reads 0
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t wave_shl1(uint32_t src) {  // lane i reads lane i+1; lane 63 reads 0
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x130, 0xF, 0xF, false);
-}
-__device__ __forceinline__ uint32_t row_bcast15(uint32_t src) {  // every lane of rows 1..3 reads lane 15 of the row below (row 0: unused)
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x142, 0xE, 0xF, false);
-}
-template <int N>
-__device__ __forceinline__ float row_shr_f(float src) {
-    return __builtin_bit_cast(float, row_shr<N>(__builtin_bit_cast(uint32_t, src)));
-}
+__device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t v) { return wave_incl_scan(v, [](uint32_t a, uint32_t b) { return a + b; }); }
+__device__ __forceinline__ uint32_t wave_incl_max_u32(uint32_t v) { return wave_incl_scan(v, [](uint32_t a, uint32_t b) { return max(a, b); }); }
+__device__ __forceinline__ uint32_t wave_last_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)v, 63); }
 
 // MERGE: how runs of equal table address over the whole wave are summed.  3 = two lanes per sample (BwdLanes::LPP == 2: fp16 tables with
 // C <= 2, fp32 with C = 1): DPP only, pure VALU; 1 = every other lane layout: cross-lane reads through ds_bpermute (~15 clk of the CU's
@@ -865,38 +874,40 @@ constexpr int BIN_RESIDENT = NGP_BIN_RESIDENT;                 // persistent sor
 #ifndef NGP_ACC_THREADS
 #define NGP_ACC_THREADS 1024
 #endif
-#ifndef NGP_ACC_RUNS_AHEAD
-#define NGP_ACC_RUNS_AHEAD 4
-#endif
 constexpr int ACC_THREADS = NGP_ACC_THREADS;
 // Dense levels: samples cluster where the scene is, so contiguous slices would be very unevenly loaded (and a 4913-entry level would
 // have two of them).  Their entries are dealt round-robin to BIN_DENSE_BINS workgroups instead: bin = index mod 128, slot = index / 128.
 constexpr int BIN_DENSE_BITS = 7;
 constexpr int BIN_DENSE_BINS = 1 << BIN_DENSE_BITS;
 
+// The words of a binned level's plan entry, BinPlan::lc[li] (words 6 and 11 are unused).  THE layout: written by plan_level_words, read by
+// the item decode of k_grid_backward_bin (the sort) and the accessors below (the accumulate).
 constexpr int BIN_LC_WORDS = 12;
+enum BinWord : uint32_t {
+    LC_LEVEL = 0,      // the level of the table
+    LC_N_BINS = 1,     // bins = workgroups of the accumulate: 128 round-robin bins, or slices of 4096 entries
+    LC_FLAGS = 2,      // BinFlag bits
+    LC_SIZE = 3,       // table entries of the level, by the HOST copy of the offsets
+    LC_SCALE = 4,      // scale of the level (float bits)
+    LC_MASK = 5,       // entries - 1 if a power of two, else 0
+    LC_DESC_BASE = 7,  // first descriptor of the level ([bin][chunk])
+    LC_STRIDE = 8,     // ..10: dense strides of the first three dimensions
+};
+// LC_FLAGS: interleaved bins (bin = index & 127, slot = index >> 7: dense levels, see above; else bin = index >> 12: contiguous slices),
+// LevelIndexer::hashed, LevelIndexer::need_mod
+enum BinFlag : uint32_t { LC_INTERLEAVED = 1u, LC_HASHED = 4u, LC_NEED_MOD = 8u };
 struct BinPlan {
     // per binned level li (blockIdx.y of the accumulate, item index of the sort): constants in 32-bit words, so that a wave-uniform index
     // becomes a few scalar loads from the kernel-argument segment.  Made from the caller's HOST copy of the offsets.
-    //   [0] level  [1] n_bins  [2] flags (1: interleaved bins, 4: hashed, 8: index needs the modulo)  [3] table entries  [4] scale (float bits)
-    //   [5] mask (entries - 1 if a power of two, else 0)  [7] first descriptor of the level ([bin][chunk])  [8..10] dense strides
     uint32_t lc[NGP_MAX_LEVELS][BIN_LC_WORDS];
     uint32_t n_chunks;                   // chunks (BIN_PPB samples) per level
     uint32_t n_levels;                   // binned levels
-    // interleaved = 0: bin = index >> 12 (contiguous slices); 1: bin = index & 127 (dense levels, see above)
-    __host__ __device__ __forceinline__ uint32_t level(uint32_t li) const { return lc[li][0]; }
-    __host__ __device__ __forceinline__ uint32_t n_bins(uint32_t li) const { return lc[li][1]; }
-    __host__ __device__ __forceinline__ bool interleaved(uint32_t li) const { return (lc[li][2] & 1u) != 0u; }
-    __host__ __device__ __forceinline__ uint32_t desc_base(uint32_t li) const { return lc[li][7]; }
+    __host__ __device__ __forceinline__ uint32_t level(uint32_t li) const { return lc[li][LC_LEVEL]; }
+    __host__ __device__ __forceinline__ uint32_t n_bins(uint32_t li) const { return lc[li][LC_N_BINS]; }
+    __host__ __device__ __forceinline__ bool interleaved(uint32_t li) const { return (lc[li][LC_FLAGS] & LC_INTERLEAVED) != 0u; }
+    __host__ __device__ __forceinline__ uint32_t size(uint32_t li) const { return lc[li][LC_SIZE]; }
+    __host__ __device__ __forceinline__ uint32_t desc_base(uint32_t li) const { return lc[li][LC_DESC_BASE]; }
 };
-
-__device__ __forceinline__ uint32_t pack_half2(float a, float b) {
-    const half2_t h = {(half_t)a, (half_t)b};
-    return __builtin_bit_cast(uint32_t, h);
-}
-__device__ __forceinline__ void atomic_add_packed(half_t* p, uint32_t packed) {
-    (void)__builtin_amdgcn_flat_atomic_fadd_v2f16(reinterpret_cast<half2_t*>(p), __builtin_bit_cast(half2_t, packed));
-}
 
 // Pass 1 and the atomic levels share ONE launch: the record sort is VALU-bound, the atomic levels wait on the LDS crossbar (run merge)
 // and on the fabric, so workgroups of the two kinds are interleaved (evenly, by a Bresenham split of the block index) and overlap on
@@ -907,15 +918,6 @@ struct AtomicPart {
     uint32_t blocks_per_level;  // = cdiv(B, points_per_block)
     uint32_t points_per_block;
 };
-
-// DPP carries between the 16-lane rows (profiles/r01_dpp_probe.txt): row_bcast:15 hands lane 15 of a row to every lane of the NEXT row,
-// row_bcast:31 hands lane 31 to every lane of rows 2 and 3; the row mask keeps the other rows at `old` = 0.
-__device__ __forceinline__ uint32_t bcast15_rows13(uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x142, 0xA, 0xF, false);
-}
-__device__ __forceinline__ uint32_t bcast31_rows23(uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src, 0x143, 0xC, 0xF, false);
-}
 
 // Record sort, round 4: ONE LANE PER SAMPLE, count pass + place pass.
 //
@@ -1000,7 +1002,6 @@ struct BinItem {  // wave-uniform description of one (chunk, level) item
     bool interleaved, plan_ok;
     half_t* gtable;
 };
-
 // LDS counters addressed by BYTE offset from the start of the dynamic LDS segment (one v_add less per counter than pointer arithmetic)
 __device__ __forceinline__ void lds_add_u32(uint32_t byte_addr) {
     __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(3))) uint32_t*>(byte_addr), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1151,7 +1152,7 @@ template <int BPL, int WAVES>
 __device__ __forceinline__ uint32_t bin_offsets(const uint32_t* __restrict__ hist, uint32_t* __restrict__ prow, int lane, int wid, const BinItem& it,
                                                 uint32_t n_chunks, uint32_t* __restrict__ descriptors, uint32_t staging_base) {
     constexpr int CAP = 64 * BPL;
-    uint32_t tot[BPL], mine[BPL], run = 0u;
+    uint32_t tot[BPL], mine[BPL];
 #pragma unroll
     for (int k = 0; k < BPL; k++) tot[k] = mine[k] = 0u;
 #pragma unroll BPL <= 2 ? WAVES : 1  // (8 x 8 loads in flight would cost the kernel its occupancy)
@@ -1170,16 +1171,9 @@ __device__ __forceinline__ uint32_t bin_offsets(const uint32_t* __restrict__ his
         uint32_t even[BPL], erun = 0u;
 #pragma unroll
         for (int k = 0; k < BPL; k++) { even[k] = (tot[k] + 1u) & ~1u; erun += even[k]; }
-        uint32_t incl = erun;
-        incl += row_shr<1>(incl);
-        incl += row_shr<2>(incl);
-        incl += row_shr<4>(incl);
-        incl += row_shr<8>(incl);
-        incl += bcast15_rows13(incl);
-        incl += bcast31_rows23(incl);
+        const uint32_t incl = wave_incl_sum_u32(erun);
         begin = incl - erun;
-        (void)run;
-        const uint32_t total_units = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63) >> 1;
+        const uint32_t total_units = wave_last_lane(incl) >> 1;
 #pragma unroll
         for (int k = 0; k < BPL; k++) {
             prow[lane * BPL + k] = begin + mine[k];
@@ -1252,8 +1246,8 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
     {
         bool differ = false;
         if ((uint32_t)lane < n_levels) {
-            const uint32_t level = plan.lc[lane][0];
-            differ = (uint32_t)offsets[level + 1] - (uint32_t)offsets[level] != plan.lc[lane][3];
+            const uint32_t level = plan.level(lane);
+            differ = (uint32_t)offsets[level + 1] - (uint32_t)offsets[level] != plan.size(lane);
         }
         levels_differ = __builtin_amdgcn_ballot_w64(differ);
     }
@@ -1263,7 +1257,7 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
     uint32_t g_cur = 0u, chunk_loaded = 0xffffffffu;
     auto fetch_g = [&](uint32_t chunk_x, uint32_t li) -> uint32_t {
         const uint32_t b = chunk_x * BIN_PPB + (uint32_t)tid;
-        return b < B ? *reinterpret_cast<const uint32_t*>(grad + ((size_t)plan.lc[li][0] * B + b) * C) : 0u;
+        return b < B ? *reinterpret_cast<const uint32_t*>(grad + ((size_t)plan.level(li) * B + b) * C) : 0u;
     };
     if (item < item_end) g_cur = fetch_g(it.chunk_x, it.li);
     __syncthreads();
@@ -1280,19 +1274,21 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
         uint32_t li_next = it.li + 1u, chunk_next = it.chunk_x;
         if (li_next == n_levels) { li_next = 0u; chunk_next++; }
         const uint32_t g_next = item + 1u < item_end ? fetch_g(chunk_next, li_next) : 0u;  // in flight during this item
+        // the item's constants and the indexer of its level, as planned.  (Written out: as a routine of its own -- by reference or returning the
+        // indexer -- the same statements cost every instantiation of this kernel an instruction and another scalar allocation, EXPERIMENTS.md.)
         const uint32_t* __restrict__ lc = plan.lc[it.li];
-        const uint32_t level = lc[0], flags = lc[2];
-        it.n_bins = lc[1];
-        it.scale = __builtin_bit_cast(float, lc[4]);
-        it.desc_base = lc[7];
-        it.interleaved = (flags & 1u) != 0u;
+        const uint32_t level = lc[LC_LEVEL], flags = lc[LC_FLAGS];
+        it.n_bins = lc[LC_N_BINS];
+        it.scale = __builtin_bit_cast(float, lc[LC_SCALE]);
+        it.desc_base = lc[LC_DESC_BASE];
+        it.interleaved = (flags & LC_INTERLEAVED) != 0u;
         LevelIndexer<D> indexer;
-        indexer.size = lc[3];
-        indexer.mask = lc[5];
-        indexer.hashed = (flags & 4u) != 0u;
-        indexer.need_mod = (flags & 8u) != 0u;
+        indexer.size = lc[LC_SIZE];
+        indexer.mask = lc[LC_MASK];
+        indexer.hashed = (flags & LC_HASHED) != 0u;
+        indexer.need_mod = (flags & LC_NEED_MOD) != 0u;
 #pragma unroll
-        for (int d = 0; d < D; d++) indexer.stride[d] = lc[8 + (d < 3 ? d : 2)];
+        for (int d = 0; d < D; d++) indexer.stride[d] = lc[LC_STRIDE + (d < 3 ? d : 2)];
         // the plan was made from the caller's HOST copy of the offsets; the device offsets are authoritative: where they describe another
         // level size (checked once per wave, above) index with them, and stay in bounds (records of a level that outgrew its bins take the atomic)
         it.plan_ok = true;
@@ -1331,6 +1327,46 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
     }
 }
 
+// The accumulator of one slice in LDS: per entry and channel an exact 64-bit fixed-point sum in units of 2^-24 and a poison bit for contributions
+// that are not finite.  Records go in through add_plain / add_general; what comes out is gradient(): the sum, to be rounded ONCE, or NaN.
+struct SliceSums {
+    unsigned long long* acc;  // [BIN_SLICE][2]
+    uint32_t* poison;         // [BIN_SLICE / 16], 2 bits per entry
+    // Exact fixed-point addend of a finite fp16 value v (11 significant bits), straight-line for BOTH magnitude ranges:
+    //   |v| <  128: v * 2^24 is an integer below 2^31                      -> q = (int32) (v * 2^24), addend = q
+    //   |v| >= 128: v is a multiple of 2^-3 (ulp of the binade of 128)     -> q = (int32) (v * 8) (<= 524032), addend = q << 21
+    // one multiply, one conversion, one 64-bit shift by a selected amount; both channels are added unconditionally (a zero addend is harmless).
+    static __device__ __forceinline__ unsigned long long fixed_addend(float v) {
+        const bool big = __builtin_fabsf(v) >= 128.0f;
+        const int32_t q = (int32_t)(v * (big ? 8.0f : 0x1p24f));
+        return (unsigned long long)(long long)q << (big ? 21 : 0);  // (shifted as unsigned: two's complement, exact mod 2^64)
+    }
+    static __device__ __forceinline__ uint32_t entry_of(uint32_t key) { return key & (BIN_SLICE - 1u); }  // (16-bit keys: the entry inside the slice, two scale flags)
+    static __device__ __forceinline__ bool special(uint32_t key, uint32_t val) {  // a record the straight-line addend does not cover
+        return (key & BIN_KEY_SCALED) != 0u || (val & 0x7c00u) == 0x7c00u || (val & 0x7c000000u) == 0x7c000000u;
+    }
+    __device__ __forceinline__ void add_plain(const uint32_t key, const uint32_t val) const {  // finite, unscaled
+        const uint32_t idx = entry_of(key);
+        NGP_BOUNDS(idx < (uint32_t)BIN_SLICE);
+        const half2_t hv = __builtin_bit_cast(half2_t, val);
+        __hip_atomic_fetch_add(&acc[2 * idx], fixed_addend((float)hv.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&acc[2 * idx + 1], fixed_addend((float)hv.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ void add_general(const uint32_t key, const uint32_t val) const {  // inf / NaN poison their channel; a scaled channel carries 1/64
+        const uint32_t idx = entry_of(key);
+        NGP_BOUNDS(idx < (uint32_t)BIN_SLICE);
+        const int up0 = (key & BIN_KEY_SCALED0) ? 6 : 0, up1 = (key & BIN_KEY_SCALED1) ? 6 : 0;
+        const half2_t hv = __builtin_bit_cast(half2_t, val);
+        const bool fin0 = (val & 0x7c00u) != 0x7c00u, fin1 = (val & 0x7c000000u) != 0x7c000000u;
+        __hip_atomic_fetch_add(&acc[2 * idx], fixed_addend(fin0 ? (float)hv.x : 0.0f) << up0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&acc[2 * idx + 1], fixed_addend(fin1 ? (float)hv.y : 0.0f) << up1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (!(fin0 && fin1)) atomicOr(&poison[idx >> 4], ((fin0 ? 0u : 1u) | (fin1 ? 0u : 2u)) << ((idx & 15u) * 2u));
+    }
+    // the gradient of a channel as it will be stored (before the one rounding to fp16): the sum (long long)acc[2 i + ch], or NaN when the channel's
+    // poison bit (poison[i >> 4] >> (2 (i & 15) + ch)) is set.  (The flushes read both themselves: accessors moved instructions, EXPERIMENTS.md.)
+    static __device__ __forceinline__ float gradient(long long sum, uint32_t poisoned) { return poisoned ? __builtin_nanf("") : (float)sum * 0x1p-24f; }
+};
+
 // Pass 2, round 4: DENSE lanes.  The kernel is bound by its instruction stream (34 M VALU per launch, PMC), and the round-3 walk -- a group
 // of 16 lanes per run, two records per lane, a second trip for the part of a run beyond 32 records -- kept about a third of the lanes
 // busy: runs are Poisson-distributed around 32 records, so most waves made the second trip for a handful of records.  Now a wave takes
@@ -1358,9 +1394,8 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
         carried_block(slabs, blockIdx.x, reinterpret_cast<float (*)[RS_PARAMS]>(acc_smem), found_inf);
         return;
     }
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(acc_smem);                                // [BIN_SLICE][2]
-    uint32_t* poison = reinterpret_cast<uint32_t*>(acc_smem + sizeof(unsigned long long) * 2 * BIN_SLICE);  // [BIN_SLICE / 16], 2 bits per entry
-    uint2* run_table = reinterpret_cast<uint2*>(poison + BIN_SLICE / 16);                                   // [WAVES][64] {first record, first pair | records << 18}
+    const SliceSums slice{reinterpret_cast<unsigned long long*>(acc_smem), reinterpret_cast<uint32_t*>(acc_smem + sizeof(unsigned long long) * 2 * BIN_SLICE)};
+    uint2* run_table = reinterpret_cast<uint2*>(slice.poison + BIN_SLICE / 16);                                   // [WAVES][64] {first record, first pair | records << 18}
     uint32_t* head_at = reinterpret_cast<uint32_t*>(run_table + WAVES * 64);                                // [WAVES][64] run (1-based) whose first pair sits at this lane of the window
     // levels in REVERSE order: the sort wrote the last level's records last, so they are the ones still in the memory-side cache
     // (same-box A/B: -4 us per iteration)
@@ -1372,8 +1407,8 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     const uint32_t li = plan.n_levels - 1u - (blockIdx.y - slab_row), bin = blockIdx.x;
     if (bin >= plan.n_bins(li)) return;
     const int tid = threadIdx.x, lane = tid & 63, wid = (int)__builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int i = tid; i < 2 * BIN_SLICE; i += ACC_THREADS) acc[i] = 0ull;
-    if (tid < BIN_SLICE / 16) poison[tid] = 0u;
+    for (int i = tid; i < 2 * BIN_SLICE; i += ACC_THREADS) slice.acc[i] = 0ull;
+    if (tid < BIN_SLICE / 16) slice.poison[tid] = 0u;
     __syncthreads();
     const uint32_t n_chunks = plan.n_chunks;
     const uint32_t* __restrict__ desc = descriptors + plan.desc_base(li) + (size_t)bin * n_chunks;
@@ -1423,37 +1458,6 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
             }
         }
     }
-    // Exact fixed-point addend of a finite fp16 value v (11 significant bits), straight-line for BOTH magnitude ranges:
-    //   |v| <  128: v * 2^24 is an integer below 2^31                      -> q = (int32) (v * 2^24), addend = q
-    //   |v| >= 128: v is a multiple of 2^-3 (ulp of the binade of 128)     -> q = (int32) (v * 8) (<= 524032), addend = q << 21
-    // one multiply, one conversion, one 64-bit shift by a selected amount; both channels are added unconditionally (a zero addend is
-    // harmless).
-    auto fixed_addend = [](float v) -> unsigned long long {
-        const bool big = __builtin_fabsf(v) >= 128.0f;
-        const int32_t q = (int32_t)(v * (big ? 8.0f : 0x1p24f));
-        return (unsigned long long)(long long)q << (big ? 21 : 0);  // (shifted as unsigned: two's complement, exact mod 2^64)
-    };
-    auto entry_of = [&](uint32_t key) { return key & (BIN_SLICE - 1u); };  // (16-bit keys: the entry inside the slice, two scale flags)
-    auto add_plain = [&](const uint32_t key, const uint32_t val) {  // finite, unscaled
-        const uint32_t idx = entry_of(key);
-        NGP_BOUNDS(idx < (uint32_t)BIN_SLICE);
-        const half2_t hv = __builtin_bit_cast(half2_t, val);
-        __hip_atomic_fetch_add(&acc[2 * idx], fixed_addend((float)hv.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&acc[2 * idx + 1], fixed_addend((float)hv.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-    auto add_general = [&](const uint32_t key, const uint32_t val) {  // inf / NaN poison their channel; a scaled channel carries 1/64
-        const uint32_t idx = entry_of(key);
-        NGP_BOUNDS(idx < (uint32_t)BIN_SLICE);
-        const int up0 = (key & BIN_KEY_SCALED0) ? 6 : 0, up1 = (key & BIN_KEY_SCALED1) ? 6 : 0;
-        const half2_t hv = __builtin_bit_cast(half2_t, val);
-        const bool fin0 = (val & 0x7c00u) != 0x7c00u, fin1 = (val & 0x7c000000u) != 0x7c000000u;
-        __hip_atomic_fetch_add(&acc[2 * idx], fixed_addend(fin0 ? (float)hv.x : 0.0f) << up0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&acc[2 * idx + 1], fixed_addend(fin1 ? (float)hv.y : 0.0f) << up1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (!(fin0 && fin1)) atomicOr(&poison[idx >> 4], ((fin0 ? 0u : 1u) | (fin1 ? 0u : 2u)) << ((idx & 15u) * 2u));
-    };
-    auto special = [](uint32_t key, uint32_t val) {  // a record the straight-line addend does not cover
-        return (key & BIN_KEY_SCALED) != 0u || (val & 0x7c00u) == 0x7c00u || (val & 0x7c000000u) == 0x7c000000u;
-    };
     // every workgroup of a level walks the same chunks: start each one somewhere else
     const uint32_t rot = (bin * 97u) % n_chunks;
     auto chunk_of = [&](uint32_t i) { const uint32_t k = i + rot; return k >= n_chunks ? k - n_chunks : k; };
@@ -1473,14 +1477,8 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
             first = k * (uint32_t)(2 * MAX_REC) + (d & 0xffffu) * 3u;  // WORD index of the run's first pair unit inside the level: < 2^31
         }
         const uint32_t pairs = (cnt + 1u) >> 1;  // 16-byte accesses: two records per lane (an odd run ends in a half-used pair)
-        uint32_t incl = pairs;
-        incl += row_shr<1>(incl);
-        incl += row_shr<2>(incl);
-        incl += row_shr<4>(incl);
-        incl += row_shr<8>(incl);
-        incl += bcast15_rows13(incl);
-        incl += bcast31_rows23(incl);
-        const uint32_t total_pairs = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t incl = wave_incl_sum_u32(pairs);
+        const uint32_t total_pairs = wave_last_lane(incl);
         const uint32_t start = incl - pairs;
         my_runs[2 * lane] = first;
         my_runs[2 * lane + 1] = start | (cnt << 18);  // (start < 64 * 2048 = 2^17, cnt <= 4096)
@@ -1490,15 +1488,8 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
         auto fetch = [&](uint32_t w0, uint4& q, uint32_t& valid) {
             my_heads[lane] = 0u;
             if (pairs != 0u && start - w0 < 64u) my_heads[start - w0] = (uint32_t)lane + 1u;  // (unsigned: start >= w0)
-            uint32_t r = my_heads[lane];
-            r = max(r, row_shr<1>(r));
-            r = max(r, row_shr<2>(r));
-            r = max(r, row_shr<4>(r));
-            r = max(r, row_shr<8>(r));
-            r = max(r, bcast15_rows13(r));
-            r = max(r, bcast31_rows23(r));
-            r = max(r, carry);
-            carry = (uint32_t)__builtin_amdgcn_readlane((int)r, 63);
+            const uint32_t r = max(wave_incl_max_u32(my_heads[lane]), carry);
+            carry = wave_last_lane(r);
             const uint32_t p = w0 + (uint32_t)lane;
             const bool have = p < total_pairs;  // (r >= 1 then: pair 0 is the head of the first non-empty run)
             const uint32_t ri = have ? r - 1u : 0u;
@@ -1527,12 +1518,12 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
             valid2 = 0u;
             if (w0 + 128u < total_pairs) fetch(w0 + 128u, q2, valid2);
             const bool have = (valid & 1u) != 0u, second = (valid & 2u) != 0u;
-            if (__builtin_amdgcn_ballot_w64((have && special(q.x, q.y)) || (second && special(q.z, q.w))) == 0ull) {
-                if (have) add_plain(q.x, q.y);
-                if (second) add_plain(q.z, q.w);
+            if (__builtin_amdgcn_ballot_w64((have && SliceSums::special(q.x, q.y)) || (second && SliceSums::special(q.z, q.w))) == 0ull) {
+                if (have) slice.add_plain(q.x, q.y);
+                if (second) slice.add_plain(q.z, q.w);
             } else {
-                if (have) add_general(q.x, q.y);
-                if (second) add_general(q.z, q.w);
+                if (have) slice.add_general(q.x, q.y);
+                if (second) slice.add_general(q.z, q.w);
             }
         }
     }
@@ -1572,15 +1563,14 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
                         pp[k].z = a.x; pp[k].w = a.y; pm[k].z = b.x; pm[k].w = b.y; pv[k].z = c.x; pv[k].w = c.y;
                     }
                 }
-                const float nan = __builtin_nanf("");
                 half4_t g16, h16;
 #pragma unroll
                 for (int c = 0; c < 4; c++) {
                     const uint32_t ii = i + (uint32_t)(c >> 1);
-                    const long long sum = (long long)acc[2 * ii + (c & 1)];
-                    const uint32_t bad = (poison[ii >> 4] >> ((ii & 15u) * 2u + (uint32_t)(c & 1))) & 1u;
+                    const long long sum = (long long)slice.acc[2 * ii + (c & 1)];
+                    const uint32_t bad = (slice.poison[ii >> 4] >> ((ii & 15u) * 2u + (uint32_t)(c & 1))) & 1u;
                     // the gradient as it would be stored: the exact sum rounded once to fp16 (0 + sum: what adding into a zeroed entry gives)
-                    g16[c] = (half_t)(0.0f + (bad ? nan : (float)sum * 0x1p-24f));
+                    g16[c] = (half_t)(0.0f + SliceSums::gradient(sum, bad));
                     const bool live = (c >> 1) ? ok1 : ok0;
                     nonfinite = nonfinite || (live && !__builtin_isfinite((float)g16[c]));
                     const float g = (float)g16[c] * inv_scale;
@@ -1628,9 +1618,9 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     for (int k = 0; k < PER_THREAD; k++) {
         const uint32_t i = (uint32_t)tid + (uint32_t)k * ACC_THREADS;
         ent[k] = interleaved ? (i << BIN_DENSE_BITS) + bin : bin * BIN_SLICE + i;
-        sum0[k] = (long long)acc[2 * i];
-        sum1[k] = (long long)acc[2 * i + 1];
-        badb[k] = (poison[i >> 4] >> ((i & 15u) * 2u)) & 3u;
+        sum0[k] = (long long)slice.acc[2 * i];
+        sum1[k] = (long long)slice.acc[2 * i + 1];
+        badb[k] = (slice.poison[i >> 4] >> ((i & 15u) * 2u)) & 3u;
         // overwrite: every entry of the slice is written (a zero sum stores +0: what adding it to a zeroed entry gives) and none is read
         touch[k] = ent[k] < hashmap_size && (overwrite || !(sum0[k] == 0 && sum1[k] == 0 && !badb[k]));
         oldv[k] = half2_t{(half_t)0.0f, (half_t)0.0f};
@@ -1643,10 +1633,9 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
 #pragma unroll
     for (int k = 0; k < PER_THREAD; k++) {
         if (!touch[k]) continue;
-        const float nan = __builtin_nanf("");
         half2_t nu;
-        nu.x = (half_t)((float)oldv[k].x + ((badb[k] & 1u) ? nan : (float)sum0[k] * 0x1p-24f));
-        nu.y = (half_t)((float)oldv[k].y + ((badb[k] & 2u) ? nan : (float)sum1[k] * 0x1p-24f));
+        nu.x = (half_t)((float)oldv[k].x + SliceSums::gradient(sum0[k], badb[k] & 1u));
+        nu.y = (half_t)((float)oldv[k].y + SliceSums::gradient(sum1[k], badb[k] & 2u));
         gtable[ent[k]] = nu;
         nonfinite = nonfinite || !__builtin_isfinite((float)nu.x) || !__builtin_isfinite((float)nu.y);
     }
@@ -1853,6 +1842,9 @@ struct BackwardPlan {
     bool adam = false;           // the accumulate's flush applies Adam to the table (needs overwrite; ngp_table_adam_t)
     TableAdam table_adam = {};
     mutable bool slabs_done = false;  // set by the launch that carried them
+    // every level of the L-level table is on the record-sort path: every entry of the table comes out of a flush (which implies what
+    // plan_backward asks of a binned level: fp16, C = 2, D = 2 or 3, a workspace, the host offsets, >= BIN_MIN_SAMPLES samples)
+    bool every_level_sorted(uint32_t L) const { return n_atomic == 0 && n_binned == L; }
     size_t desc_bytes() const { return ((size_t)total_desc * sizeof(uint32_t) + 255) & ~(size_t)255; }
     // (+64: the 16-byte load of a one-record run at the very end of the last chunk reads 8 bytes past it)
     size_t workspace_bytes() const { return n_binned ? desc_bytes() + (size_t)total_records * sizeof(uint2) + 64 : 0; }
@@ -1861,20 +1853,21 @@ struct BackwardPlan {
 constexpr uint32_t BIN_MIN_SAMPLES = 16384;       // below this the launch overheads of the two extra kernels win
 constexpr uint32_t BIN_MAX_SAMPLES = 1u << 24;
 
-static uint32_t float_bits(float v) {
-    uint32_t u;
-    memcpy(&u, &v, sizeof(u));
-    return u;
-}
-
-// the indexer's words of a binned level's plan entry (BinPlan::lc), from the indexer the kernels of the other paths build on the device
+// the words of a binned level's plan entry (BinWord); the indexer's part from the indexer the kernels of the other paths build on the device
 template <int D>
-static void plan_indexer_words(uint32_t* lc, uint32_t gridtype, bool align_corners, uint32_t size, uint32_t resolution) {
+static void plan_level_words(uint32_t* lc, uint32_t level, uint32_t n_bins, bool interleave, uint32_t size, float scale, uint32_t desc_base,
+                             uint32_t gridtype, bool align_corners, uint32_t resolution) {
     LevelIndexer<D> ix;
     ix.init(gridtype, align_corners, size, resolution);
-    lc[2] |= (ix.hashed ? 4u : 0u) | (ix.need_mod ? 8u : 0u);
-    lc[5] = ix.mask;
-    for (int d = 0; d < D; d++) lc[8 + d] = ix.stride[d];
+    for (int k = 0; k < BIN_LC_WORDS; k++) lc[k] = 0u;
+    lc[LC_LEVEL] = level;
+    lc[LC_N_BINS] = n_bins;
+    lc[LC_FLAGS] = (interleave ? LC_INTERLEAVED : 0u) | (ix.hashed ? LC_HASHED : 0u) | (ix.need_mod ? LC_NEED_MOD : 0u);
+    lc[LC_SIZE] = size;
+    memcpy(&lc[LC_SCALE], &scale, sizeof(scale));
+    lc[LC_MASK] = ix.mask;
+    lc[LC_DESC_BASE] = desc_base;
+    for (int d = 0; d < D; d++) lc[LC_STRIDE + d] = ix.stride[d];
 }
 
 // Every level of an eligible call is binned: hashed levels in contiguous slices, dense levels in round-robin bins.
@@ -1896,17 +1889,9 @@ static void plan_backward(BackwardPlan& p, const int32_t* offsets_host, const Gr
             p.atomic_levels.level[p.n_atomic++] = (uint8_t)l;
             continue;
         }
-        const uint32_t i = p.n_binned++;
-        uint32_t* lc = p.bins.lc[i];
-        for (int k = 0; k < BIN_LC_WORDS; k++) lc[k] = 0u;
-        lc[0] = l;
-        lc[1] = n_bins;
-        lc[2] = interleave ? 1u : 0u;
-        lc[3] = size;
-        lc[4] = float_bits(lv.scale[l]);
-        lc[7] = p.total_desc;
-        if (D == 2) plan_indexer_words<2>(lc, gridtype, align_corners, size, lv.res[l]);   // (eligible: D is 2 or 3)
-        else plan_indexer_words<3>(lc, gridtype, align_corners, size, lv.res[l]);
+        uint32_t* lc = p.bins.lc[p.n_binned++];
+        if (D == 2) plan_level_words<2>(lc, l, n_bins, interleave, size, lv.scale[l], p.total_desc, gridtype, align_corners, lv.res[l]);   // (eligible: D is 2 or 3)
+        else plan_level_words<3>(lc, l, n_bins, interleave, size, lv.scale[l], p.total_desc, gridtype, align_corners, lv.res[l]);
         p.total_desc += n_bins * p.bins.n_chunks;
         p.total_records += (uint64_t)p.bins.n_chunks * BIN_PPB * (1u << D);
         p.max_bins = n_bins > p.max_bins ? n_bins : p.max_bins;
@@ -1923,19 +1908,18 @@ static int launch_backward_bins(const void* grad, const float* inputs, const int
     const uint32_t bins_cap = p.max_bins <= 128u ? 128u : (uint32_t)BIN_MAX_BINS;
     constexpr size_t bin_smem_max = sizeof(uint2) * (BIN_PPB * (1 << D) + BIN_MAX_BINS) + sizeof(uint32_t) * 2 * (BIN_THREADS / 64) * BIN_MAX_BINS;
     const size_t bin_smem = sizeof(uint2) * (BIN_PPB * (1 << D) + bins_cap) + sizeof(uint32_t) * 2 * (BIN_THREADS / 64) * bins_cap;
+    const auto sort_kernel = bins_cap <= 128u ? k_grid_backward_bin<D, AMERGE, 2> : k_grid_backward_bin<D, AMERGE, BIN_MAX_BINS / 64>;
+    const auto acc_kernel = p.adam ? k_grid_backward_accumulate<D, true> : k_grid_backward_accumulate<D, false>;
     static bool configured = false;
     if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_backward_accumulate<D, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)acc_smem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_backward_accumulate<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)acc_smem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_backward_bin<D, AMERGE, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bin_smem_max) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_backward_bin<D, AMERGE, BIN_MAX_BINS / 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bin_smem_max) != hipSuccess) {
-            set_error("grid_encode_backward: hipFuncSetAttribute(LDS size) failed");
-            return NGP_ERR_LAUNCH;
-        }
+        const struct { const void* kernel; size_t lds; } need[] = {
+            {(const void*)k_grid_backward_accumulate<D, false>, acc_smem}, {(const void*)k_grid_backward_accumulate<D, true>, acc_smem},
+            {(const void*)k_grid_backward_bin<D, AMERGE, 2>, bin_smem_max}, {(const void*)k_grid_backward_bin<D, AMERGE, BIN_MAX_BINS / 64>, bin_smem_max}};
+        for (const auto& k : need)
+            if (hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) != hipSuccess) {
+                set_error("grid_encode_backward: hipFuncSetAttribute(LDS size) failed");
+                return NGP_ERR_LAUNCH;
+            }
         configured = true;
     }
     uint32_t* descriptors = reinterpret_cast<uint32_t*>(workspace);
@@ -1962,23 +1946,15 @@ static int launch_backward_bins(const void* grad, const float* inputs, const int
     const uint32_t blocks = persistent + ap.n_blocks;
     BinPlan bins = p.bins;
     bins.n_levels = p.n_binned;
-    if (bins_cap <= 128u)
-        hipLaunchKernelGGL((k_grid_backward_bin<D, AMERGE, 2>), dim3(blocks), dim3(BIN_THREADS), bin_smem, st, (const half_t*)grad, inputs, offsets,
-                           (half_t*)grad_emb, B, lv, gridtype, ac, interp, im, bins, descriptors, records, ap);
-    else
-        hipLaunchKernelGGL((k_grid_backward_bin<D, AMERGE, BIN_MAX_BINS / 64>), dim3(blocks), dim3(BIN_THREADS), bin_smem, st, (const half_t*)grad, inputs,
-                           offsets, (half_t*)grad_emb, B, lv, gridtype, ac, interp, im, bins, descriptors, records, ap);
+    hipLaunchKernelGGL(sort_kernel, dim3(blocks), dim3(BIN_THREADS), bin_smem, st, (const half_t*)grad, inputs, offsets, (half_t*)grad_emb, B, lv, gridtype,
+                       ac, interp, im, bins, descriptors, records, ap);
     int rc = check_launch("grid_encode_backward(bin)");
     if (rc) return rc;
     static_assert(ACC_THREADS == RS_PARAMS * RS_GROUPS, "the slab reduction's blocks have the accumulate's shape");
     const uint32_t slab_blocks = p.slabs.total_blocks();
     const dim3 acc_grid(std::max(p.max_bins, slab_blocks), p.n_binned + (slab_blocks ? 1u : 0u));
-    if (p.adam)
-        hipLaunchKernelGGL((k_grid_backward_accumulate<D, true>), acc_grid, dim3(ACC_THREADS), acc_smem, st, offsets, (half_t*)grad_emb, bins,
-                           (const uint32_t*)descriptors, (const uint2*)records, p.found_inf, p.slabs, p.overwrite, p.table_adam);
-    else
-        hipLaunchKernelGGL((k_grid_backward_accumulate<D, false>), acc_grid, dim3(ACC_THREADS), acc_smem, st, offsets, (half_t*)grad_emb, bins,
-                           (const uint32_t*)descriptors, (const uint2*)records, p.found_inf, p.slabs, p.overwrite, p.table_adam);
+    hipLaunchKernelGGL(acc_kernel, acc_grid, dim3(ACC_THREADS), acc_smem, st, offsets, (half_t*)grad_emb, bins, (const uint32_t*)descriptors,
+                       (const uint2*)records, p.found_inf, p.slabs, p.overwrite, p.table_adam);
     p.slabs_done = slab_blocks != 0;
     return check_launch("grid_encode_backward(accumulate)");
 }
@@ -2210,7 +2186,7 @@ extern "C" uint32_t ngp_grid_table_adam_prefix(const int32_t* offsets_host, uint
                                                uint32_t gridtype, int align_corners, int dtype) {
     BackwardPlan plan;
     if (!plan_for_query(plan, offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype)) return 0xffffffffu;
-    if (plan.n_atomic != 0 || plan.n_binned != L || dtype != NGP_F16 || C != 2) return 0xffffffffu;
+    if (!plan.every_level_sorted(L)) return 0xffffffffu;
     uint32_t k;
     if (!dense_level_prefix(plan, k)) return 0xffffffffu;
     return (uint32_t)offsets_host[k];   // (binned levels are listed in level order when every level is binned: index == level)
@@ -2236,6 +2212,63 @@ extern "C" int ngp_grid_encode_backward_checked(const void* grad, const float* i
                                                   stream);
 }
 
+// The steps of ngp_grid_encode_backward_checked_slabs, in the order it takes them.
+// The carried reductions (the two MLPs' weight-gradient slabs and the loss sum of the training step) ride in the accumulate launch when the
+// call has one; otherwise (few samples, no workspace, an empty batch) reduce_carried_alone launches them on their own -- the caller gets
+// the reduced gradients and the loss either way.
+static int carried_slab_sets(SlabSets& carried, const ngp_slab_sets_t* s, bool sweep) {
+    carried = {};
+    if (!s) return NGP_OK;
+    const uint32_t ba = slab_set(carried, 0, s->slabs_a, s->n_slabs_a, s->n_params_a, s->grad_weights_a, sweep);
+    const uint32_t bb = slab_set(carried, 1, s->slabs_b, s->n_slabs_b, s->n_params_b, s->grad_weights_b, sweep);
+    NGP_REQUIRE((!ba || ((s->slabs_a || !s->n_slabs_a) && s->grad_weights_a)) && (!bb || ((s->slabs_b || !s->n_slabs_b) && s->grad_weights_b)),
+                NGP_ERR_INVALID, "grid_encode_backward: NULL tensor in the slab sets");
+    NGP_REQUIRE(!s->loss || (s->ray_err && s->n_rays > 0), NGP_ERR_INVALID, "grid_encode_backward: loss sum without per-ray errors");
+    carried.ray_err = s->ray_err; carried.n_rays = s->n_rays; carried.loss = s->loss;
+    return NGP_OK;
+}
+
+static int reduce_carried_alone(const SlabSets& carried, float* found_inf, hipStream_t st) {
+    if (carried.total_blocks() == 0u) return NGP_OK;
+    hipLaunchKernelGGL(k_carried_reductions, dim3(carried.total_blocks()), dim3(RS_PARAMS * RS_GROUPS), 0, st, carried, found_inf);
+    return check_launch("grid_encode_backward(carried reductions)");
+}
+
+static int zero_table(void* grad_embeddings, const int32_t* offsets_host, uint32_t L, uint32_t C, int dtype, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(grad_embeddings, 0, (size_t)offsets_host[L] * C * (dtype == NGP_F16 ? 2 : 4), st);
+    NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "grid_encode_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
+    return NGP_OK;
+}
+
+// The table's Adam sweep rides in the accumulate's flush only when EVERY entry of the table comes out of a flush (all levels on the
+// record-sort path, overwrite mode) -- refused otherwise, before anything is launched (the caller falls back to ngp_optim_adam_step_ex).
+static int admit_table_adam(BackwardPlan& plan, const ngp_table_adam_t& tadam, bool overwrite_table, uint32_t L, const void* grad_embeddings) {
+    NGP_REQUIRE(overwrite_table && plan.every_level_sorted(L), NGP_ERR_INVALID,
+                "grid_encode_backward: table_adam needs overwrite_table and every level on the record-sort path (fp16, C = 2, >= %u samples, "
+                "a workspace and the host offsets)", BIN_MIN_SAMPLES);
+    NGP_REQUIRE(tadam.state, NGP_ERR_INVALID, "grid_encode_backward: table_adam without the optimizer's state");
+    // the dense levels' entries are left to ngp_optim_adam_small_commit (ngp_grid_table_adam_prefix tells the caller how many there are),
+    // and their gradient has to be stored for it
+    uint32_t k;
+    const bool prefix_ok = dense_level_prefix(plan, k);
+    NGP_REQUIRE(prefix_ok, NGP_ERR_INVALID, "grid_encode_backward: table_adam: a dense level behind a hashed one (level %u)", plan.bins.level(k));
+    NGP_REQUIRE(k == 0 || grad_embeddings, NGP_ERR_INVALID, "grid_encode_backward: table_adam: the dense levels' gradient needs grad_embeddings");
+    const int null_set = table_adam_from(plan.table_adam, tadam);
+    NGP_REQUIRE(null_set < 0, NGP_ERR_INVALID, "grid_encode_backward: table_adam: NULL buffer in set %d", null_set);
+    plan.adam = true;
+    return NGP_OK;
+}
+
+// found_inf over a table some of whose levels went through atomics (the record-sort path flags its own sums where it produces them)
+static int sweep_nonfinite(const void* grad_embeddings, uint64_t n, int dtype, float* found_inf, hipStream_t st) {
+    const uint32_t blocks = (uint32_t)(cdiv64(n, 256 * 8) > 2048 ? 2048 : cdiv64(n, 256 * 8));
+    if (dtype == NGP_F16)
+        hipLaunchKernelGGL(k_flag_nonfinite<half_t>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const half_t*)grad_embeddings, n, found_inf);
+    else
+        hipLaunchKernelGGL(k_flag_nonfinite<float>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const float*)grad_embeddings, n, found_inf);
+    return check_launch("grid_encode_backward(non-finite sweep)");
+}
+
 extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
                                                       void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                                       uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
@@ -2243,38 +2276,25 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
                                                       size_t workspace_bytes, float* found_inf, const ngp_slab_sets_t* slab_sets,
                                                       ngp_stream_t stream) {
     (void)embeddings;
-    // the carried reductions ride in the accumulate launch when this call has one; otherwise (few samples, no workspace, an empty batch) they
-    // are launched on their own -- the caller gets the reduced gradients and the loss either way
-    SlabSets carried = {};
-    if (slab_sets) {
-        const uint32_t ba = slab_set(carried, 0, slab_sets->slabs_a, slab_sets->n_slabs_a, slab_sets->n_params_a, slab_sets->grad_weights_a, found_inf != nullptr);
-        const uint32_t bb = slab_set(carried, 1, slab_sets->slabs_b, slab_sets->n_slabs_b, slab_sets->n_params_b, slab_sets->grad_weights_b, found_inf != nullptr);
-        NGP_REQUIRE((!ba || ((slab_sets->slabs_a || !slab_sets->n_slabs_a) && slab_sets->grad_weights_a)) &&
-                        (!bb || ((slab_sets->slabs_b || !slab_sets->n_slabs_b) && slab_sets->grad_weights_b)),
-                    NGP_ERR_INVALID, "grid_encode_backward: NULL tensor in the slab sets");
-        NGP_REQUIRE(!slab_sets->loss || (slab_sets->ray_err && slab_sets->n_rays > 0), NGP_ERR_INVALID, "grid_encode_backward: loss sum without per-ray errors");
-        carried.ray_err = slab_sets->ray_err; carried.n_rays = slab_sets->n_rays; carried.loss = slab_sets->loss;
-    }
-    auto reduce_alone = [&]() -> int {
-        if (carried.total_blocks() == 0u) return NGP_OK;
-        hipLaunchKernelGGL(k_carried_reductions, dim3(carried.total_blocks()), dim3(RS_PARAMS * RS_GROUPS), 0, as_stream(stream), carried, found_inf);
-        return check_launch("grid_encode_backward(carried reductions)");
-    };
+    hipStream_t st = as_stream(stream);
+    const bool overwrite_table = slab_sets && slab_sets->overwrite_table;
+    const ngp_table_adam_t* tadam = slab_sets ? slab_sets->table_adam : nullptr;
+    SlabSets carried;
+    int rc = carried_slab_sets(carried, slab_sets, found_inf != nullptr);
+    if (rc) return rc;
     NGP_REQUIRE(!(bound > 0.0f && dy_dx), NGP_ERR_INVALID, "grid_encode_backward: the fused input mapping does not provide grad_inputs");
     NGP_REQUIRE(!found_inf || offsets_host, NGP_ERR_INVALID, "grid_encode_backward: found_inf needs the host copy of the offsets");
-    const InputMap im = make_input_map(bound);
-    int rc = check_grid_args("grid_encode_backward", B, D, C, L, dtype);
+    rc = check_grid_args("grid_encode_backward", B, D, C, L, dtype);
     if (rc) return rc;
-    if (B == 0) {
-        NGP_REQUIRE(!(slab_sets && slab_sets->table_adam), NGP_ERR_INVALID, "grid_encode_backward: table_adam with an empty batch");
-        if (slab_sets && slab_sets->overwrite_table) {
+    if (B == 0) {   // nothing to add: the table is zeroed where the caller asked for an overwrite, the carried reductions still run
+        NGP_REQUIRE(!tadam, NGP_ERR_INVALID, "grid_encode_backward: table_adam with an empty batch");
+        if (overwrite_table) {
             NGP_REQUIRE(offsets_host && grad_embeddings, NGP_ERR_INVALID, "grid_encode_backward: overwrite_table needs the table and the host copy of the offsets");
-            hipError_t e = hipMemsetAsync(grad_embeddings, 0, (size_t)offsets_host[L] * C * (dtype == NGP_F16 ? 2 : 4), as_stream(stream));
-            NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "grid_encode_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
+            rc = zero_table(grad_embeddings, offsets_host, L, C, dtype, st);
+            if (rc) return rc;
         }
-        return reduce_alone();
+        return reduce_carried_alone(carried, found_inf, st);
     }
-    const ngp_table_adam_t* tadam = slab_sets ? slab_sets->table_adam : nullptr;
     NGP_REQUIRE(grad && inputs && offsets && (grad_embeddings || tadam), NGP_ERR_INVALID, "grid_encode_backward: NULL tensor");
     GridLevels lv;
     fill_levels(lv, L, S, H);
@@ -2283,52 +2303,30 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
     plan.found_inf = found_inf;
     plan.slabs = carried;
     if (tadam) {
-        // the table's Adam sweep rides in the accumulate's flush: only when EVERY entry of the table comes out of a flush (all levels on the
-        // record-sort path, overwrite mode) -- refused otherwise, before anything is launched (the caller falls back to ngp_optim_adam_step_ex)
-        NGP_REQUIRE(slab_sets->overwrite_table && plan.n_atomic == 0 && plan.n_binned == L && dtype == NGP_F16 && C == 2, NGP_ERR_INVALID,
-                    "grid_encode_backward: table_adam needs overwrite_table and every level on the record-sort path (fp16, C = 2, >= %u samples, "
-                    "a workspace and the host offsets)", BIN_MIN_SAMPLES);
-        NGP_REQUIRE(tadam->state, NGP_ERR_INVALID, "grid_encode_backward: table_adam without the optimizer's state");
-        // the dense levels' entries are left to ngp_optim_adam_small_commit (ngp_grid_table_adam_prefix tells the caller how many there are),
-        // and their gradient has to be stored for it
-        uint32_t k;
-        const bool prefix_ok = dense_level_prefix(plan, k);
-        NGP_REQUIRE(prefix_ok, NGP_ERR_INVALID, "grid_encode_backward: table_adam: a dense level behind a hashed one (level %u)", plan.bins.level(k));
-        NGP_REQUIRE(k == 0 || grad_embeddings, NGP_ERR_INVALID, "grid_encode_backward: table_adam: the dense levels' gradient needs grad_embeddings");
-        const int null_set = table_adam_from(plan.table_adam, *tadam);
-        NGP_REQUIRE(null_set < 0, NGP_ERR_INVALID, "grid_encode_backward: table_adam: NULL buffer in set %d", null_set);
-        plan.adam = true;
+        rc = admit_table_adam(plan, *tadam, overwrite_table, L, grad_embeddings);
+        if (rc) return rc;
     }
-    if (slab_sets && slab_sets->overwrite_table) {
+    if (overwrite_table) {
         // every entry comes out of the accumulate only when every level is sorted; otherwise: zero the table, then add as usual
-        if (plan.n_atomic == 0 && plan.n_binned == L && dtype == NGP_F16) {
-            plan.overwrite = true;
-        } else {
+        plan.overwrite = plan.every_level_sorted(L);
+        if (!plan.overwrite) {
             NGP_REQUIRE(offsets_host, NGP_ERR_INVALID, "grid_encode_backward: overwrite_table needs the host copy of the offsets");
-            const size_t bytes = (size_t)offsets_host[L] * C * (dtype == NGP_F16 ? 2 : 4);
-            hipError_t e = hipMemsetAsync(grad_embeddings, 0, bytes, as_stream(stream));
-            NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "grid_encode_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
+            rc = zero_table(grad_embeddings, offsets_host, L, C, dtype, st);
+            if (rc) return rc;
         }
     }
     NGP_REQUIRE(plan.workspace_bytes() <= workspace_bytes, NGP_ERR_INVALID,
                 "grid_encode_backward: workspace of %zu bytes, ngp_grid_backward_workspace_bytes() asks for %zu", workspace_bytes,
                 plan.workspace_bytes());
-    hipStream_t st = as_stream(stream);
+    const InputMap im = make_input_map(bound);
     const bool ac = align_corners != 0;
     rc = dtype == NGP_F16 ? dispatch_backward<half_t>(D, C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac,
                                                       interp, im, plan, workspace, st)
                           : dispatch_backward<float>(D, C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp,
                                                      im, plan, workspace, st);
-    if (!rc && slab_sets && !plan.slabs_done) rc = reduce_alone();
+    if (!rc && !plan.slabs_done) rc = reduce_carried_alone(carried, found_inf, st);
     if (rc || !found_inf || plan.n_atomic == 0) return rc;
-    // some levels went through atomics: their sums are swept here (the record-sort path flags its own)
-    const uint64_t n = (uint64_t)offsets_host[L] * C;
-    const uint32_t blocks = (uint32_t)(cdiv64(n, 256 * 8) > 2048 ? 2048 : cdiv64(n, 256 * 8));
-    if (dtype == NGP_F16)
-        hipLaunchKernelGGL(k_flag_nonfinite<half_t>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const half_t*)grad_embeddings, n, found_inf);
-    else
-        hipLaunchKernelGGL(k_flag_nonfinite<float>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const float*)grad_embeddings, n, found_inf);
-    return check_launch("grid_encode_backward(non-finite sweep)");
+    return sweep_nonfinite(grad_embeddings, (uint64_t)offsets_host[L] * C, dtype, found_inf, st);
 }
 
 extern "C" int ngp_grid_encode_backward_ws(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
