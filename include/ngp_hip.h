@@ -118,6 +118,43 @@ int ngp_grid_encode_backward_backward(const void* grad, const float* inputs, con
 /* scratch of ngp_grid_encode_backward_backward: 0 for F32 / F16; for F64 a function of B and D alone (offsets_host may be NULL) */
 size_t ngp_grid_backward_backward_workspace_bytes(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, int dtype);
 
+/* Ordered scatter (no reference counterpart): the table gradient of the first and of the second order for F32 and
+ * F16 tables WITHOUT float atomics, bit-reproducible.  Every D in {2,3,4,5} and C in {1,2,4,8}, F16 with odd C included (nothing is
+ * packed).  Opt-in: the entries above run exactly what they ran.
+ * Per level: one record per (point, corner), n = B * 2^D (key = the entry, level_size for a point outside [0,1]^D; value = the slot
+ * b << D | k), a stable 8-bit LSD radix sort on bit_length(level_size) bits, then the sum.  THE ORDER OF THE ADDITIONS is part of the
+ * contract and a function of the sorted array alone -- not of the launch geometry, the workspace or anything else two calls with equal
+ * inputs may differ in: the array is cut into tiles of 64 records; each tile's run of one entry (a fragment) is summed left to right
+ * in fp32 starting from its first contribution; a run inside one tile is added once, dst = T(float(dst) + sum); a fragment whose run
+ * crosses the tile's left (right) edge becomes the record (entry, partial sum) at slot 2t (2t + 1) of the next array, which is summed
+ * by the same rule, until an array fits one tile.  No lane performs more than 63 dependent additions per launch, however the points
+ * cluster; the launches and the array sizes follow from (B, D) alone, nothing is read back, the call can be captured in a graph.
+ * The contributions come from the atomic paths' code: w_k * grad (first order: the fp32 weight product), a_k * grad (second order: a_k
+ * from the fp32 phi, 1 - phi and phi' in double, rounded to fp32 once), one fp32 product each.
+ *
+ * ngp_grid_encode_backward_ordered: the arguments of ngp_grid_encode_backward_ws without offsets_host; grad_inputs has the bits of
+ * ngp_grid_encode_backward.  ngp_grid_encode_backward_backward_ordered: the arguments of ngp_grid_encode_backward_backward;
+ * grad_grad and grad_inputs2 have its bits.  grad_embeddings is accumulated (pre-zeroed by the caller).  Both need a 256-byte
+ * aligned workspace of ngp_grid_ordered_workspace_bytes(B, D, C, dtype) bytes and B * 2^D <= 2^31; both refuse NGP_F64 (the entries
+ * above are bit-reproducible for it).  Everything is checked before any launch; B == 0 is a no-op. */
+int ngp_grid_encode_backward_ordered(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                     void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                     const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                                     float bound, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+int ngp_grid_encode_backward_backward_ordered(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                              const void* grad_grad_inputs, void* grad_grad, void* grad_embeddings, void* grad_inputs2,
+                                              uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype,
+                                              int align_corners, uint32_t interp, int dtype, void* workspace, size_t workspace_bytes,
+                                              ngp_stream_t stream);
+/* scratch of the two ordered entries, a function of its arguments alone (0 for B == 0 and for arguments they refuse).  With n = B * 2^D
+ * and a256(x) = x rounded up to 256:  4 a256(4 n)  [keys and slots, twice]  +  a256(4 (256 * 1024 + 256))  [radix counts]
+ * + sum_i (a256(4 m_i) + a256(4 C m_i))  [partial sums: m_1 = 2 ceil(n / 64), m_{i+1} = 2 ceil(m_i / 64), while m_{i-1} > 64] */
+size_t ngp_grid_ordered_workspace_bytes(uint32_t B, uint32_t D, uint32_t C, int dtype);
+/* host only: 1 when ngp_grid_encode_backward_ws with these arguments (a workspace and offsets_host given) runs every level without
+ * float atomics -- every level on the record-sort path, or NGP_F64 -- else 0 (also for arguments no call accepts) */
+int ngp_grid_backward_is_reproducible(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                      uint32_t gridtype, int align_corners, int dtype);
+
 /* ---------------------------------------------------------------------------------------------
  * shencoder        (reference: shencoder/src/shencoder.h:9-10, bindings.cpp:5-8)
  * --------------------------------------------------------------------------------------------- */

@@ -43,6 +43,12 @@ _SIGNATURES = {
     'ngp_grid_level_table': [_u32, _f32, _u32, _vp, _vp],
     'ngp_grid_encode_backward_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _u32, _i32, _vp,
                                           _sz, _vp],
+    # the ordered (bit-reproducible) scatter: ..._backward_ws without offsets_host, and ..._backward_backward as it is
+    'ngp_grid_encode_backward_ordered': [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _vp, _vp, _u32, _i32, _u32, _i32, _f32, _vp,
+                                         _sz, _vp],
+    'ngp_grid_encode_backward_backward_ordered': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _u32, _i32,
+                                                  _vp, _sz, _vp],
+    'ngp_grid_backward_is_reproducible': [_vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _i32],
     'ngp_sh_encode_forward': [_vp, _vp, _u32, _u32, _u32, _vp, _i32, _vp],
     'ngp_sh_encode_backward': [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _i32, _vp],
     'ngp_freq_encode_forward': [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
@@ -161,6 +167,8 @@ lib.ngp_grid_backward_workspace_bytes.restype = _sz
 lib.ngp_grid_backward_backward_workspace_bytes.argtypes = [_vp, _u32, _u32, _u32, _u32, _i32]
 lib.ngp_grid_backward_backward_workspace_bytes.restype = _sz
 lib.ngp_compact_rays_workspace_bytes.restype = _sz
+lib.ngp_grid_ordered_workspace_bytes.argtypes = [_u32, _u32, _u32, _i32]
+lib.ngp_grid_ordered_workspace_bytes.restype = _sz
 lib.ngp_grid_table_adam_prefix.argtypes = [_vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _i32]
 lib.ngp_grid_table_adam_prefix.restype = _u32
 lib.ngp_coarse_occupancy_bytes.argtypes = [_u32, _u32]
@@ -180,7 +188,8 @@ EXPORTED = sorted(list(_SIGNATURES) + ['ngp_last_error', 'ngp_target_arch', 'ngp
                                        'ngp_grid_backward_workspace_bytes', 'ngp_ffmlp_backward_workspace_bytes',
                                        'ngp_ffmlp_backward_slab_count', 'ngp_density_grid_update_workspace_bytes', 'ngp_grid_forward_work_lists', 'ngp_coarse_occupancy_bytes',
                                        'ngp_grid_table_adam_prefix', 'ngp_linear_stack_flat_size',
-                                       'ngp_grid_backward_backward_workspace_bytes', 'ngp_ffmlp_backward_backward_workspace_bytes'])
+                                       'ngp_grid_backward_backward_workspace_bytes', 'ngp_ffmlp_backward_backward_workspace_bytes',
+                                       'ngp_grid_ordered_workspace_bytes'])
 
 
 def check(rc):

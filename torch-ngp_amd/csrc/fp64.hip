@@ -24,15 +24,6 @@ namespace ngp {
 
 constexpr int F64_THREADS = 256;
 
-// interpolation weight of corner k (bit d set: the upper vertex in dimension d) -- the fp32 product of k_grid_forward, same order
-template <int D>
-__device__ __forceinline__ float corner_weight(const float (&frac)[D], uint32_t k) {
-    float w = 1.0f;
-#pragma unroll
-    for (int d = 0; d < D; d++) w *= ((k >> d) & 1u) ? frac[d] : (1.0f - frac[d]);
-    return w;
-}
-
 // ------------------------------------------------------------------------------------------------
 // grid encoder: forward (gridencoder.cu:87-245)
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
-// Grid-encoder indexing shared by the fp16/fp32 kernels (gridencoder.hip), the fp64 ones (fp64.hip) and the second-order backward
-// (grid_second.hip): the per-level table, the corner-index rule and the position of a point inside a level.  One statement of each, so
-// the fp64 path locates points and computes interpolation weights exactly as the fp32 path does.  Also the host plumbing the three units
-// share: the level table of a call, the launch-grid cap and the (D, C) dispatch.
+// Grid-encoder indexing shared by the fp16/fp32 kernels (gridencoder.hip), the fp64 ones (fp64.hip), the second-order backward
+// (grid_second.hip) and the ordered scatter (grid_ordered.hip): the per-level table, the corner-index rule, the position of a point inside
+// a level, the corner weight and the first backward's input term.  One statement of each, so the fp64 path locates points and computes
+// interpolation weights exactly as the fp32 path does.  Also the host plumbing the units share: the level table of a call, the launch-grid
+// cap and the (D, C) dispatch.
 #pragma once
 #include "common.h"
 
@@ -167,6 +168,31 @@ __device__ __forceinline__ bool locate_d2(const float* __restrict__ x, float sca
         frac[d] = p;
     }
     return true;
+}
+
+// interpolation weight of corner k (bit d set: the upper vertex in dimension d) -- the fp32 product of k_grid_forward, same order
+template <int D>
+__device__ __forceinline__ float corner_weight(const float (&frac)[D], uint32_t k) {
+    float w = 1.0f;
+#pragma unroll
+    for (int d = 0; d < D; d++) w *= ((k >> d) & 1u) ? frac[d] : (1.0f - frac[d]);
+    return w;
+}
+
+// gridencoder.cu:343-369: grad_inputs[b, d] = sum_{l, c} grad[l, b, c] * dy_dx[b, l, d, c] -- one statement for the first-order backward
+// (gridencoder.hip) and its ordered form (grid_ordered.hip): the same bits from both
+template <typename T>
+__global__ void k_grid_input_backward(const T* __restrict__ grad, const T* __restrict__ dy_dx, T* __restrict__ grad_inputs,
+                                      uint32_t B, uint32_t L, uint32_t D, uint32_t C) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * D) return;
+    const uint32_t b = t / D, d = t - b * D;
+    const T* dd = dy_dx + (size_t)b * L * D * C;
+    float r = 0.0f;
+    for (uint32_t l = 0; l < L; l++)
+        for (uint32_t c = 0; c < C; c++)
+            r = __builtin_fmaf((float)grad[((size_t)l * B + b) * C + c], (float)dd[(l * D + d) * C + c], r);
+    grad_inputs[t] = (T)r;
 }
 
 }  // namespace ngp

@@ -1643,21 +1643,6 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
     if (found_inf && __any(nonfinite) && (tid & 63) == 0) found_inf[0] = 1.0f;
 }
 
-// gridencoder.cu:343-369
-template <typename T>
-__global__ void k_grid_input_backward(const T* __restrict__ grad, const T* __restrict__ dy_dx, T* __restrict__ grad_inputs,
-                                      uint32_t B, uint32_t L, uint32_t D, uint32_t C) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * D) return;
-    const uint32_t b = t / D, d = t - b * D;
-    const T* dd = dy_dx + (size_t)b * L * D * C;
-    float r = 0.0f;
-    for (uint32_t l = 0; l < L; l++)
-        for (uint32_t c = 0; c < C; c++)
-            r = __builtin_fmaf((float)grad[((size_t)l * B + b) * C + c], (float)dd[(l * D + d) * C + c], r);
-    grad_inputs[t] = (T)r;
-}
-
 // gridencoder.cu:506-610
 template <typename T, int D, int C>
 __global__ __launch_bounds__(FWD_THREADS) void k_grad_tv(const T* __restrict__ inputs, const T* __restrict__ grid,
@@ -2190,6 +2175,14 @@ extern "C" uint32_t ngp_grid_table_adam_prefix(const int32_t* offsets_host, uint
     uint32_t k;
     if (!dense_level_prefix(plan, k)) return 0xffffffffu;
     return (uint32_t)offsets_host[k];   // (binned levels are listed in level order when every level is binned: index == level)
+}
+
+extern "C" int ngp_grid_backward_is_reproducible(const int32_t* offsets_host, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                                 uint32_t gridtype, int align_corners, int dtype) {
+    if (L < 1 || L > NGP_MAX_LEVELS || D < 2 || D > 5 || !(C == 1 || C == 2 || C == 4 || C == 8)) return 0;
+    if (dtype == NGP_F64) return 1;   // the record sort of fp64.hip, whatever the shape
+    BackwardPlan plan;
+    return plan_for_query(plan, offsets_host, B, D, C, L, S, H, gridtype, align_corners, dtype) && plan.every_level_sorted(L) ? 1 : 0;
 }
 
 template <typename T>

@@ -46,6 +46,81 @@ def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, 
         None if arr is None else capi.ctypes.cast(arr, capi.ctypes.c_void_p), capi.ptr(ws), nbytes, capi.stream()))
 
 
+def _dtype_code(dtype):
+    if isinstance(dtype, int):
+        return dtype
+    codes = {capi.torch.float32: capi.NGP_F32, capi.torch.float16: capi.NGP_F16, capi.torch.float64: capi.NGP_F64}
+    if dtype not in codes:
+        raise RuntimeError(f"scatter_path: the table dtype must be float32, float16 or float64 (got {dtype})")
+    return codes[dtype]
+
+
+def scatter_path(B, D, C, L, S, H, gridtype, align_corners, dtype, deterministic, order, offsets=None):
+    """How the table gradient of a backward is scattered (host computation only): 'fp64' (the record sort of the fp64 path), 'sorted' (the
+    first order's record-sort plan covers every level: already free of float atomics), 'ordered' (the ordered scatter) or
+    'atomic'.  order: 1 = the first backward, 2 = the second-order one.  dtype: the table's (a torch dtype or an NGP_F* code).
+    deterministic: True / False, None = torch.are_deterministic_algorithms_enabled() now.  offsets: the table's offsets (tensor, sequence or
+    ctypes int32 array) -- the first order's plan depends on the level sizes; without them it counts as not reproducible, as a backward
+    call without the host offsets runs."""
+    if order not in (1, 2):
+        raise ValueError(f"scatter_path: order must be 1 or 2 (got {order})")
+    code = _dtype_code(dtype)
+    if code == capi.NGP_F64:
+        return 'fp64'
+    if deterministic is None:
+        deterministic = capi.torch.are_deterministic_algorithms_enabled()
+    if order == 1 and offsets is not None:
+        if isinstance(offsets, capi.torch.Tensor):
+            arr = capi.host_offsets(offsets)
+        elif isinstance(offsets, capi.ctypes.Array):
+            arr = offsets
+        else:
+            arr = (capi.ctypes.c_int32 * len(offsets))(*[int(v) for v in offsets])
+        if arr is not None and capi.lib.ngp_grid_backward_is_reproducible(capi.ctypes.cast(arr, capi.ctypes.c_void_p), B, D, C, L, float(S), H, gridtype,
+                                                                          int(bool(align_corners)), code) == 1:
+            return 'sorted'
+    return 'ordered' if deterministic else 'atomic'
+
+
+def _ordered_workspace(B, D, C, code, device):
+    nbytes = int(capi.lib.ngp_grid_ordered_workspace_bytes(B, D, C, code))
+    return (capi.torch.empty(nbytes, dtype=capi.torch.uint8, device=device) if nbytes else None), nbytes
+
+
+def grid_encode_backward_ordered(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                                 align_corners, interp):
+    """grid_encode_backward with the ordered scatter (ngp_grid_encode_backward_ordered): the same arguments, bit-reproducible
+    grad_embeddings, fp32 and fp16 tables"""
+    _check_common(inputs, embeddings, offsets)
+    capi.dense(grad, 'grad')
+    capi.dense(grad_embeddings, 'grad_embeddings')
+    code = capi.float_code(grad, 'grad')
+    for t, name in ((grad_embeddings, 'grad_embeddings'), (dy_dx, 'dy_dx'), (grad_inputs, 'grad_inputs')):
+        if t is not None and t.dtype != grad.dtype:
+            raise RuntimeError(f"{name} must have the dtype of grad, {grad.dtype} (got {t.dtype})")
+    ws, nbytes = _ordered_workspace(B, D, C, code, inputs.device)
+    capi.check(capi.lib.ngp_grid_encode_backward_ordered(
+        capi.ptr(grad), capi.ptr(inputs), capi.ptr(embeddings), capi.ptr(offsets), capi.ptr(grad_embeddings), B, D, C, L, float(S), H,
+        capi.ptr(dy_dx), capi.ptr(grad_inputs), gridtype, int(bool(align_corners)), interp, code, 0.0, capi.ptr(ws), nbytes, capi.stream()))
+
+
+def grid_encode_backward_backward_ordered(grad, inputs, embeddings, offsets, u, grad_grad, grad_embeddings, grad_inputs2, B, D, C, L, S, H,
+                                          gridtype, align_corners, interp):
+    """ngp_grid_encode_backward_backward_ordered on tensors, the arguments of grid.grid_encode_backward_backward"""
+    _check_common(inputs, embeddings, offsets)
+    for t, name in ((grad, 'grad'), (u, 'grad_grad_inputs'), (grad_embeddings, 'grad_embeddings'), (grad_grad, 'grad_grad'),
+                    (grad_inputs2, 'grad_inputs2')):
+        if t is not None:
+            capi.dense(t, name)
+            if t.dtype != embeddings.dtype:
+                raise RuntimeError(f"{name} must have the table's dtype {embeddings.dtype} (got {t.dtype})")
+    code = capi.float_code(embeddings, 'embeddings')
+    ws, nbytes = _ordered_workspace(B, D, C, code, inputs.device)
+    capi.check(capi.lib.ngp_grid_encode_backward_backward_ordered(
+        capi.ptr(grad), capi.ptr(inputs), capi.ptr(embeddings), capi.ptr(offsets), capi.ptr(u), capi.ptr(grad_grad), capi.ptr(grad_embeddings),
+        capi.ptr(grad_inputs2), B, D, C, L, float(S), H, gridtype, int(bool(align_corners)), interp, code, capi.ptr(ws), nbytes, capi.stream()))
+
+
 def grad_total_variation(inputs, embeddings, grad, offsets, weight, B, D, C, L, S, H, gridtype, align_corners):
     capi.dense(inputs, 'inputs')
     capi.dense(embeddings, 'embeddings')

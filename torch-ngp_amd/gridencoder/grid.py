@@ -42,16 +42,38 @@ def level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_
     return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
 
 
-def _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, geometry):
-    """d loss / d inputs (None without dy_dx) and d loss / d embeddings from the upstream gradient [B, L*C]"""
+def _wants_determinism(deterministic):
+    """the module's `deterministic` when a backward runs: None follows PyTorch's determinism switch as it stands then.  False (the default of
+    grid_encode) asks nothing of the host: the call runs what it always ran"""
+    return torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+
+
+def _ordered_backend():
+    """gridencoder/backend.py, which holds scatter_path and the ordered entries' wrappers: loaded when a backward first asks for determinism,
+    so that a process on the compiled `_gridencoder` module imports what it always imported"""
+    from . import backend
+    return backend
+
+
+def _scatter_path(geometry, embeddings, offsets, deterministic, order):
+    """scatter_path (gridencoder/backend.py) of a backward of this op"""
+    n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
+    return _ordered_backend().scatter_path(n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, align_corners, embeddings.dtype, deterministic,
+                        order, offsets if order == 1 else None)
+
+
+def _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, geometry, deterministic=False):
+    """d loss / d inputs (None without dy_dx) and d loss / d embeddings from the upstream gradient [B, L*C]; deterministic: the table
+    gradient without float atomics where the call's own plan has them (scatter_path 'ordered': the same arguments, the ordered entry)"""
     n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
     grad_level_major = grad.view(n_points, n_levels, feat).permute(1, 0, 2).contiguous()
     grad_embeddings = torch.zeros_like(embeddings)
     grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
 
-    _backend.grid_encode_backward(grad_level_major, inputs, embeddings, offsets, grad_embeddings, n_points, dim, feat,
-                                  n_levels, log2_scale, base_resolution, dy_dx, grad_inputs, gridtype, align_corners,
-                                  interpolation)
+    ordered = _wants_determinism(deterministic) and _scatter_path(geometry, embeddings, offsets, True, 1) == 'ordered'
+    (_ordered_backend().grid_encode_backward_ordered if ordered else _backend.grid_encode_backward)(
+        grad_level_major, inputs, embeddings, offsets, grad_embeddings, n_points, dim, feat, n_levels, log2_scale, base_resolution, dy_dx,
+        grad_inputs, gridtype, align_corners, interpolation)
     if grad_inputs is not None:
         grad_inputs = grad_inputs.to(inputs.dtype)
     return grad_inputs, grad_embeddings
@@ -61,7 +83,7 @@ class _grid_encode(Function):
     @staticmethod
     @custom_fwd(device_type='cuda')
     def forward(ctx, inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs=False, gridtype=0,
-                align_corners=False, interpolation=0):
+                align_corners=False, interpolation=0, deterministic=False):
         # inputs [B, D] fp32 in [0, 1]; embeddings [n_entries, C]; offsets [L+1] int32 -> [B, L*C]
         inputs_src, table_src = inputs, embeddings
         inputs = inputs.contiguous()
@@ -87,6 +109,7 @@ class _grid_encode(Function):
         # first-order backward neither reads them nor checks their version
         ctx.sources = (None if inputs_src is inputs else inputs_src, None if table_src is embeddings else table_src)
         ctx.geometry = (n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners)
+        ctx.deterministic = deterministic
         return level_major.permute(1, 0, 2).reshape(n_points, n_levels * feat)
 
     @staticmethod
@@ -95,10 +118,11 @@ class _grid_encode(Function):
         inputs, embeddings, offsets, dy_dx = ctx.saved_tensors
         if torch.is_grad_enabled():
             # create_graph=True (eikonal / SDF losses on d enc / d x): the same backend calls as a differentiable op
-            grad_inputs, grad_embeddings = _grid_encode_backward.apply(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry, *ctx.sources)
+            grad_inputs, grad_embeddings = _grid_encode_backward.apply(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry, *ctx.sources,
+                                                                       ctx.deterministic)
         else:
-            grad_inputs, grad_embeddings = _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry)
-        return grad_inputs, grad_embeddings, None, None, None, None, None, None, None
+            grad_inputs, grad_embeddings = _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, ctx.geometry, ctx.deterministic)
+        return grad_inputs, grad_embeddings, None, None, None, None, None, None, None, None
 
 
 class _grid_encode_backward(Function):
@@ -107,12 +131,13 @@ class _grid_encode_backward(Function):
     3.6)."""
 
     @staticmethod
-    def forward(ctx, grad, inputs, embeddings, offsets, dy_dx, geometry, inputs_src=None, table_src=None):
+    def forward(ctx, grad, inputs, embeddings, offsets, dy_dx, geometry, inputs_src=None, table_src=None, deterministic=False):
         # inputs_src / table_src: the tensors the encoder was called with when `inputs` / `embeddings` are copies of them (the half table of
         # autocast): the second-order gradients go there
-        grad_inputs, grad_embeddings = _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, geometry)
+        grad_inputs, grad_embeddings = _first_order_backward(grad, inputs, embeddings, offsets, dy_dx, geometry, deterministic)
         ctx.save_for_backward(grad, inputs, embeddings, offsets)
         ctx.geometry = geometry
+        ctx.deterministic = deterministic
         ctx.sources = (inputs_src, table_src)
         # an output nobody differentiates (grad_embeddings in an eikonal loss, grad_inputs in a gradgradcheck over the table) reaches
         # backward as None, and its terms are skipped
@@ -127,10 +152,10 @@ class _grid_encode_backward(Function):
         needs = (need[0], need[1] or need[6], need[2] or need[7])
         d_grad, d_inputs, d_embeddings = _grid_encode_second.apply(
             grad_grad_inputs, grad_grad_embeddings, grad, inputs if inputs_src is None else inputs_src,
-            embeddings if table_src is None else table_src, inputs, embeddings, offsets, ctx.geometry, needs)
+            embeddings if table_src is None else table_src, inputs, embeddings, offsets, ctx.geometry, needs, ctx.deterministic)
         inputs_copied, table_copied = inputs_src is not None, table_src is not None
         return (d_grad, None if inputs_copied else d_inputs, None if table_copied else d_embeddings, None, None, None,
-                d_inputs if inputs_copied else None, d_embeddings if table_copied else None)
+                d_inputs if inputs_copied else None, d_embeddings if table_copied else None, None)
 
 
 class _grid_encode_second(Function):
@@ -141,7 +166,8 @@ class _grid_encode_second(Function):
     differentiating its results once more reaches backward, which refuses third order."""
 
     @staticmethod
-    def forward(ctx, grad_grad_inputs, grad_grad_embeddings, grad, inputs_anchor, table_anchor, inputs, embeddings, offsets, geometry, needs):
+    def forward(ctx, grad_grad_inputs, grad_grad_embeddings, grad, inputs_anchor, table_anchor, inputs, embeddings, offsets, geometry, needs,
+                deterministic=False):
         n_points, dim, feat, n_levels, log2_scale, base_resolution, gridtype, interpolation, align_corners = geometry
         need_grad, need_inputs, need_embeddings = needs
         dtype = embeddings.dtype
@@ -154,8 +180,10 @@ class _grid_encode_second(Function):
             d_embeddings = torch.zeros_like(embeddings)
             d_grad = torch.empty(n_levels, n_points, feat, device=inputs.device, dtype=dtype) if need_grad else None
             d_inputs = torch.empty(n_points, dim, device=inputs.device, dtype=dtype) if need_inputs else None
-            grid_encode_backward_backward(grad_level_major, inputs, embeddings, offsets, u, d_grad, d_embeddings, d_inputs, n_points, dim,
-                                          feat, n_levels, log2_scale, base_resolution, gridtype, align_corners, interpolation)
+            ordered = _wants_determinism(deterministic) and _scatter_path(geometry, embeddings, offsets, True, 2) == 'ordered'
+            (_ordered_backend().grid_encode_backward_backward_ordered if ordered else grid_encode_backward_backward)(
+                grad_level_major, inputs, embeddings, offsets, u, d_grad, d_embeddings, d_inputs, n_points, dim, feat, n_levels, log2_scale,
+                base_resolution, gridtype, align_corners, interpolation)
             if not need_embeddings:
                 d_embeddings = None
 
@@ -216,7 +244,9 @@ grid_encode = _grid_encode.apply
 
 class GridEncoder(nn.Module):
     def __init__(self, input_dim=3, num_levels=16, level_dim=2, per_level_scale=2, base_resolution=16, log2_hashmap_size=19,
-                 desired_resolution=None, gridtype='hash', align_corners=False, interpolation='linear'):
+                 desired_resolution=None, gridtype='hash', align_corners=False, interpolation='linear', deterministic=None):
+        # deterministic: the table gradient (first and second order) without float atomics, bit-reproducible.  None follows
+        # torch.are_deterministic_algorithms_enabled() when the backward runs, True / False force the choice
         super().__init__()
         if desired_resolution is not None:
             # geometric progression from base_resolution to desired_resolution over the levels (grid.py:101-102)
@@ -234,6 +264,7 @@ class GridEncoder(nn.Module):
         self.interpolation = interpolation
         self.interp_id = INTERP_IDS[interpolation]
         self.align_corners = align_corners
+        self.deterministic = deterministic
         self.max_params = 2 ** log2_hashmap_size
 
         offsets = level_offsets(input_dim, num_levels, per_level_scale, base_resolution, log2_hashmap_size, align_corners)
@@ -262,7 +293,7 @@ class GridEncoder(nn.Module):
         lead = list(unit.shape[:-1])
         flat = unit.view(-1, self.input_dim)
         out = grid_encode(flat, self.embeddings, self.offsets, self.per_level_scale, self.base_resolution, flat.requires_grad,
-                          self.gridtype_id, self.align_corners, self.interp_id)
+                          self.gridtype_id, self.align_corners, self.interp_id, self.deterministic)
         return out.view(lead + [self.output_dim])
 
     @torch.amp.autocast('cuda', enabled=False)
