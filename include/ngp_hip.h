@@ -883,6 +883,31 @@ int ngp_optim_shard_verdict(const void* shard_grad_fp16, float* state, void* fla
  * tensors per call */
 int ngp_optim_ema_update(int count, const uint64_t* n, float* const* params, float* const* ema, float one_minus_decay, ngp_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * native command list: record the stream operations of a chain of entries once, replay them from C
+ * ---------------------------------------------------------------------------------------------
+ * Between ngp_cmdlist_begin and ngp_cmdlist_end every stream operation (kernel launch, memset, copy) that the entries of this header issue
+ * ON THE CALLING THREAD is appended to the list -- function, grid, block, dynamic LDS and a private copy of every kernel argument -- and is
+ * still issued on the stream it was given (a surrounding stream capture sees what it saw before).  ngp_cmdlist_replay issues the recorded
+ * operations in order on `stream`; the caller keeps every buffer the recorded arguments point to alive for as long as the list is replayed.
+ * A list is recorded once.  An entry that fails while a list records leaves the list unusable (replay refuses it).
+ * Marks: ngp_cmdlist_mark(list, id, after) names a position -- after < 0: the current end (while recording: behind what was issued so
+ * far), else behind the first `after` operations; a replay records a list-owned event (timing disabled) on its stream there, and
+ * ngp_cmdlist_wait_mark makes another stream wait for that event of the most recent replay.
+ * Refused with NGP_ERR_INVALID before any device work: a NULL or destroyed list (every entry, a second destroy included); begin while a
+ * recording is open on the thread; end without begin; replay / wait_mark / destroy of a list that is still recording; replay / wait_mark
+ * of an empty or unusable list; wait_mark of a mark id that was never recorded, or before the first replay that records it. */
+int ngp_cmdlist_create(void** out_list);
+int ngp_cmdlist_begin(void* list);
+int ngp_cmdlist_mark(void* list, uint32_t mark_id, int after);
+int ngp_cmdlist_end(void* list);
+int ngp_cmdlist_count(const void* list, uint32_t* out_count);
+/* entry `index` by name: the kernel's symbol (or "memset" / "memcpy"), NUL-terminated and cut to out_bytes */
+int ngp_cmdlist_entry_name(const void* list, uint32_t index, char* out_name, uint32_t out_bytes);
+int ngp_cmdlist_replay(void* list, ngp_stream_t stream);
+int ngp_cmdlist_wait_mark(void* list, uint32_t mark_id, ngp_stream_t stream);
+int ngp_cmdlist_destroy(void* list);
+
 #ifdef __cplusplus
 }
 #endif

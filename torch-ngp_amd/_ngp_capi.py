@@ -145,6 +145,16 @@ _SIGNATURES = {
     'ngp_pad_2d_fp16': [_vp, _u32, _u32, _u32, _vp, _u32, _u32, _vp],
     'ngp_allocate_splitk': [_sz],
     'ngp_free_splitk': [],
+    # native command list (csrc/cmdlist.cpp): record a chain of entries once, replay its launches from C
+    'ngp_cmdlist_create': [_vp],
+    'ngp_cmdlist_begin': [_vp],
+    'ngp_cmdlist_mark': [_vp, _u32, _i32],
+    'ngp_cmdlist_end': [_vp],
+    'ngp_cmdlist_count': [_vp, _vp],
+    'ngp_cmdlist_entry_name': [_vp, _u32, _vp, _u32],
+    'ngp_cmdlist_replay': [_vp, _vp],
+    'ngp_cmdlist_wait_mark': [_vp, _u32, _vp],
+    'ngp_cmdlist_destroy': [_vp],
 }
 for _name, _args in _SIGNATURES.items():
     _fn = getattr(lib, _name)

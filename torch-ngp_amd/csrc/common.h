@@ -7,6 +7,7 @@
 #include <cstdarg>
 
 #include "../../include/ngp_hip.h"
+#include "cmdlist_core.h"
 
 namespace ngp {
 
@@ -21,7 +22,8 @@ typedef float float16_t __attribute__((ext_vector_type(16)));
 constexpr int WAVE = 64;
 
 // ---- error plumbing: every extern "C" entry returns 0 / non-zero and records a message ----
-void set_error(const char* fmt, ...);
+void set_error(const char* fmt, ...);          // a list recording on the thread becomes unusable (cmdlist_core.h)
+void set_error_message(const char* message);  // the message alone (the command list entries' own refusals)
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
@@ -44,6 +46,35 @@ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 inline uint64_t cdiv64(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 inline hipStream_t as_stream(ngp_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- THE launch helpers: every stream operation of the library is issued here, and appended to the command list that is recording on the
+// calling thread (cmdlist_core.h, cmdlist.cpp: ngp_cmdlist_begin .. _end) -- a launch site that bypassed them would escape every list.
+// NGP_LAUNCH takes what hipLaunchKernelGGL takes and converts the arguments to the kernel's parameter types the same way; the launch error,
+// if any, is left for check_launch() (NGP_LAUNCH_STATUS returns it as well).
+template <typename T> struct launch_param { using type = T; };
+template <typename... KA>
+inline hipError_t launch(const char* name, void (*kernel)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const typename launch_param<KA>::type&... a) {
+    void* argv[] = {const_cast<void*>(static_cast<const void*>(&a))..., nullptr};
+    const hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, argv, lds, st);
+    if (cmdlist::List* l = cmdlist::recording()) {
+        static const size_t sizes[] = {sizeof(KA)..., 0}, aligns[] = {alignof(KA)..., 0};
+        l->record_launch(reinterpret_cast<const void*>(kernel), name, cmdlist::Dim{grid.x, grid.y, grid.z}, cmdlist::Dim{block.x, block.y, block.z},
+                         (uint32_t)lds, (uint32_t)sizeof...(KA), argv, sizes, aligns);
+    }
+    return e;
+}
+#define NGP_LAUNCH_STATUS(kernel, grid, block, lds, st, ...) ::ngp::launch(#kernel, kernel, grid, block, lds, st, __VA_ARGS__)
+#define NGP_LAUNCH(...) ((void)NGP_LAUNCH_STATUS(__VA_ARGS__))
+inline hipError_t memset_async(void* dst, int value, size_t bytes, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(dst, value, bytes, st);
+    if (cmdlist::List* l = cmdlist::recording()) e == hipSuccess ? l->record_memset(dst, value, bytes) : l->poison();
+    return e;
+}
+inline hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
+    if (cmdlist::List* l = cmdlist::recording()) e == hipSuccess ? l->record_memcpy(dst, src, bytes, (int)kind) : l->poison();
+    return e;
+}
 
 // ---- debug build (make DEBUG_BOUNDS=1 -> libngp_hip_dbg.so): device-side range traps on the indices the fast paths trust ----
 // (encoder work lists and table indices, record-sort slots / descriptors / counters, accumulate record and entry indices, marcher sample

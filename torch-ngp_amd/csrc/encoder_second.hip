@@ -162,12 +162,12 @@ static int launch_freq_bwd_bwd(const void* grad, const void* outputs, const void
     const uint32_t CP = C | 1u;
     if (CP <= TILE) {
         const uint32_t P = min(TILE / CP, (uint32_t)ES_THREADS);
-        hipLaunchKernelGGL((k_freq_bwd_bwd<T>), dim3((uint32_t)cdiv64(B, P)), dim3(ES_THREADS), 0, st, (const T*)grad, (const T*)outputs, (const T*)u, B, D, deg,
+        NGP_LAUNCH((k_freq_bwd_bwd<T>), dim3((uint32_t)cdiv64(B, P)), dim3(ES_THREADS), 0, st, (const T*)grad, (const T*)outputs, (const T*)u, B, D, deg,
                            C, P, CP, (T*)grad_grad, (T*)grad_inputs2);
     } else {
         uint64_t blocks = cdiv64((uint64_t)B * C, ES_THREADS);
         if (blocks > 65536u) blocks = 65536u;
-        hipLaunchKernelGGL((k_freq_bwd_bwd_wide<T>), dim3((uint32_t)blocks), dim3(ES_THREADS), 0, st, (const T*)grad, (const T*)outputs, (const T*)u, B, D,
+        NGP_LAUNCH((k_freq_bwd_bwd_wide<T>), dim3((uint32_t)blocks), dim3(ES_THREADS), 0, st, (const T*)grad, (const T*)outputs, (const T*)u, B, D,
                            deg, C, (T*)grad_grad, (T*)grad_inputs2);
     }
     return check_launch("freq_encode_backward_backward");
@@ -256,7 +256,7 @@ static int launch_sh_bwd_bwd_x(const void* grad, const void* inputs, const void*
     // 64 * (N | 1) elements of LDS per wave: at degree 8 66560 B = 65 KiB per block (4 x 16640 B in fp32, 2 x 33280 B in fp64) of the CU's
     // 160 KiB, i.e. two blocks per CU there
     constexpr int WAVES = sizeof(T) == 8 ? 2 : 4;
-    hipLaunchKernelGGL((k_sh_bwd_bwd_x<T, BANDS, WAVES>), dim3((uint32_t)cdiv64(B, WAVES * 64)), dim3(WAVES * 64), 0, st, (const T*)grad, (const T*)inputs,
+    NGP_LAUNCH((k_sh_bwd_bwd_x<T, BANDS, WAVES>), dim3((uint32_t)cdiv64(B, WAVES * 64)), dim3(WAVES * 64), 0, st, (const T*)grad, (const T*)inputs,
                        (const T*)u, B, (T*)grad_inputs2);
     return check_launch("sh_encode_backward_backward");
 }
@@ -267,7 +267,7 @@ static int launch_sh_bwd_bwd(const void* grad, const void* inputs, const void* d
     if (grad_grad) {
         uint64_t blocks = cdiv64((uint64_t)B * C * C, ES_THREADS);
         if (blocks > 65536u) blocks = 65536u;
-        hipLaunchKernelGGL((k_sh_bwd_bwd_g<T>), dim3((uint32_t)blocks), dim3(ES_THREADS), 0, st, (const T*)dy_dx, (const T*)u, B, C * C, (T*)grad_grad);
+        NGP_LAUNCH((k_sh_bwd_bwd_g<T>), dim3((uint32_t)blocks), dim3(ES_THREADS), 0, st, (const T*)dy_dx, (const T*)u, B, C * C, (T*)grad_grad);
         const int rc = check_launch("sh_encode_backward_backward");
         if (rc) return rc;
     }
@@ -275,7 +275,7 @@ static int launch_sh_bwd_bwd(const void* grad, const void* inputs, const void* d
     switch (C) {
         case 1:
         case 2: {  // constant and linear polynomials have no Hessian: zeros, without reading g
-            const hipError_t e = hipMemsetAsync(grad_inputs2, 0, (size_t)B * 3 * sizeof(T), st);
+            const hipError_t e = ::ngp::memset_async(grad_inputs2, 0, (size_t)B * 3 * sizeof(T), st);
             NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "sh_encode_backward_backward: zero fill failed: %s", hipGetErrorString(e));
             return NGP_OK;
         }
@@ -307,7 +307,7 @@ extern "C" int ngp_freq_encode_forward_f64(const double* inputs, uint32_t B, uin
     NGP_REQUIRE(inputs && outputs, NGP_ERR_INVALID, "freq_encode_forward_f64: NULL tensor");
     uint64_t blocks = cdiv64((uint64_t)B * C, ES_THREADS);
     if (blocks > 65536u) blocks = 65536u;
-    hipLaunchKernelGGL(k_f64_freq_forward, dim3((uint32_t)blocks), dim3(ES_THREADS), 0, as_stream(stream), inputs, B, D, C, outputs);
+    NGP_LAUNCH(k_f64_freq_forward, dim3((uint32_t)blocks), dim3(ES_THREADS), 0, as_stream(stream), inputs, B, D, C, outputs);
     return check_launch("freq_encode_forward_f64");
 }
 
@@ -319,7 +319,7 @@ extern "C" int ngp_freq_encode_backward_f64(const double* grad, const double* ou
     NGP_REQUIRE(grad && outputs && grad_inputs, NGP_ERR_INVALID, "freq_encode_backward_f64: NULL tensor");
     uint64_t blocks = cdiv64((uint64_t)B * D, ES_THREADS);
     if (blocks > 65536u) blocks = 65536u;
-    hipLaunchKernelGGL(k_f64_freq_backward, dim3((uint32_t)blocks), dim3(ES_THREADS), 0, as_stream(stream), grad, outputs, B, D, deg, C, grad_inputs);
+    NGP_LAUNCH(k_f64_freq_backward, dim3((uint32_t)blocks), dim3(ES_THREADS), 0, as_stream(stream), grad, outputs, B, D, deg, C, grad_inputs);
     return check_launch("freq_encode_backward_f64");
 }
 

@@ -1939,7 +1939,7 @@ static int raise_lds(const void* kern, size_t lds, const char* what) {
 static int reduce_slabs(const void* slabs, uint32_t n_slabs, uint32_t n_params, void* grad_weights, hipStream_t st, const char* what) {
     SlabSets sets = {};
     const uint32_t blocks = slab_set(sets, 0, slabs, n_slabs, n_params, grad_weights, false);
-    hipLaunchKernelGGL(k_ffmlp_reduce_slabs_pair, dim3(blocks), dim3(RS_PARAMS * RS_GROUPS), 0, st, sets, (float*)nullptr);
+    NGP_LAUNCH(k_ffmlp_reduce_slabs_pair, dim3(blocks), dim3(RS_PARAMS * RS_GROUPS), 0, st, sets, (float*)nullptr);
     return check_launch(what);
 }
 
@@ -1966,7 +1966,7 @@ static int launch_forward_layered(const void* inputs, const void* weights, uint3
     uint32_t blocks = (uint32_t)device_info().cus * (per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu));
     const uint32_t need = cdiv(n_tiles, FF_WAVES);
     if (blocks > need) blocks = need;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)inputs, (const half_t*)weights, (half_t*)buffer,
+    NGP_LAUNCH(kern, dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)inputs, (const half_t*)weights, (half_t*)buffer,
                        (half_t*)outputs, n_tiles, in_dim, num_layers, act, out_act, (flags & NGP_FF_INPUT_PLANAR) != 0);
     return check_launch(TRAIN ? "ffmlp_forward(layered)" : "ffmlp_inference(layered)");
 }
@@ -1988,24 +1988,18 @@ static int launch_forward(const void* inputs, const void* weights, uint32_t B, u
     // the specialisation without the other activations' code is a fifth of the size (instruction fetch at kernel start matters for a
     // 25 us kernel)
     const bool plain = act == ACT_RELU && out_act == ACT_NONE;
-    const void* kern;
-    if constexpr (WIDTH > 64) kern = plain ? reinterpret_cast<const void*>(k_ffmlp_forward_wide<WIDTH, TRAIN, true>)
-                                           : reinterpret_cast<const void*>(k_ffmlp_forward_wide<WIDTH, TRAIN, false>);
-    else kern = plain ? reinterpret_cast<const void*>(k_ffmlp_forward<WIDTH, TRAIN, true>) : reinterpret_cast<const void*>(k_ffmlp_forward<WIDTH, TRAIN, false>);
-    int rc = raise_lds(kern, lds, "ffmlp");
+    using forward_kernel_t = void (*)(const half_t*, const half_t*, half_t*, half_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, bool);
+    forward_kernel_t kern;
+    if constexpr (WIDTH > 64) kern = plain ? k_ffmlp_forward_wide<WIDTH, TRAIN, true> : k_ffmlp_forward_wide<WIDTH, TRAIN, false>;
+    else kern = plain ? k_ffmlp_forward<WIDTH, TRAIN, true> : k_ffmlp_forward<WIDTH, TRAIN, false>;
+    int rc = raise_lds(reinterpret_cast<const void*>(kern), lds, "ffmlp");
     if (rc) return rc;
     const uint32_t per_cu = (uint32_t)((160 * 1024) / (lds + 1024));
     uint32_t blocks = (uint32_t)device_info().cus * (per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
     const uint32_t need = cdiv(n_tiles, FF_WAVES);
     if (blocks > need) blocks = need;
-    const half_t* a0 = (const half_t*)inputs;
-    const half_t* a1 = (const half_t*)weights;
-    half_t* a2 = (half_t*)fwd;
-    half_t* a3 = (half_t*)outputs;
-    uint32_t a4 = n_tiles, a5 = in_dim, a6 = num_layers, a7 = act, a8 = out_act;
-    bool a9 = (flags & NGP_FF_INPUT_PLANAR) != 0;
-    void* args[] = {&a0, &a1, &a2, &a3, &a4, &a5, &a6, &a7, &a8, &a9};
-    hipError_t e = hipLaunchKernel(kern, dim3(blocks), dim3(FF_THREADS), args, lds, st);
+    const hipError_t e = NGP_LAUNCH_STATUS(kern, dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)inputs, (const half_t*)weights, (half_t*)fwd,
+                                           (half_t*)outputs, n_tiles, in_dim, num_layers, act, out_act, (flags & NGP_FF_INPUT_PLANAR) != 0);
     NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp: kernel launch failed: %s", hipGetErrorString(e));
     return check_launch(TRAIN ? "ffmlp_forward" : "ffmlp_inference");
     }
@@ -2035,10 +2029,10 @@ static int launch_backward_layered(const void* grad, const void* inputs, const v
     const uint32_t need = cdiv(n_tiles, FF_WAVES);
     if (blocks > need) blocks = need;
     if (act == ACT_RELU)
-        hipLaunchKernelGGL((k_ffmlp_dgrad_layered<WIDTH, true>), dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)weights,
+        NGP_LAUNCH((k_ffmlp_dgrad_layered<WIDTH, true>), dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)weights,
                            (const half_t*)fwd, (half_t*)backward_buffer, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs, dx_planar);
     else
-        hipLaunchKernelGGL((k_ffmlp_dgrad_layered<WIDTH, false>), dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)weights,
+        NGP_LAUNCH((k_ffmlp_dgrad_layered<WIDTH, false>), dim3(blocks), dim3(FF_THREADS), lds, st, (const half_t*)grad, (const half_t*)weights,
                            (const half_t*)fwd, (half_t*)backward_buffer, n_tiles, in_dim, num_layers, act, with_dx, (half_t*)grad_inputs, dx_planar);
     rc = check_launch("ffmlp_backward(dgrad)");
     if (rc) return rc;
@@ -2058,7 +2052,7 @@ static int launch_backward_layered(const void* grad, const void* inputs, const v
     const uint32_t tiles_per_chunk = cdiv(n_tiles, chunks);
     chunks = cdiv(n_tiles, tiles_per_chunk);
     const bool direct = chunks == 1;
-    hipLaunchKernelGGL(k_ffmlp_wgrad<WIDTH>, dim3(chunks, jobs), dim3(FF_THREADS), 0, st, (const half_t*)grad, (const half_t*)inputs, (const half_t*)fwd,
+    NGP_LAUNCH(k_ffmlp_wgrad<WIDTH>, dim3(chunks, jobs), dim3(FF_THREADS), 0, st, (const half_t*)grad, (const half_t*)inputs, (const half_t*)fwd,
                        (const half_t*)backward_buffer, n_tiles, in_dim, num_layers, in_planar, tiles_per_chunk, direct ? (float*)nullptr : (float*)workspace,
                        direct ? (half_t*)grad_weights : (half_t*)nullptr);
     rc = check_launch("ffmlp_backward(wgrad)");
@@ -2164,7 +2158,7 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             auto pk = k_ffmlp_backward_paired<WIDTH, IN_JB, NHM, RELU, true>;
             return launch_and_reduce(reinterpret_cast<const void*>(pk), lds_r.total, blocks, defer, backward_buffer, grad_weights, n_params, st,
                                      [&](dim3 grid, float* slabs, half_t* direct) {
-                hipLaunchKernelGGL(pk, grid, dim3(FP_THREADS), lds_r.total, st, g, x, w, (const half_t*)nullptr, n_tiles, in_dim, num_layers, act, with_dx,
+                NGP_LAUNCH(pk, grid, dim3(FP_THREADS), lds_r.total, st, g, x, w, (const half_t*)nullptr, n_tiles, in_dim, num_layers, act, with_dx,
                                    (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds_r.pf_depth, mid, (uint32_t)lds_r.total, serial);
             });
         } else {
@@ -2177,7 +2171,7 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             auto pk = k_ffmlp_backward_paired<WIDTH, IN_JB, NHM, RELU>;
             return launch_and_reduce(reinterpret_cast<const void*>(pk), lds.total, blocks, defer, backward_buffer, grad_weights, n_params, st,
                                      [&](dim3 grid, float* slabs, half_t* direct) {
-                hipLaunchKernelGGL(pk, grid, dim3(FP_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
+                NGP_LAUNCH(pk, grid, dim3(FP_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
                                    (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds.pf_depth, mid, (uint32_t)lds.total, serial);
             });
         }
@@ -2186,7 +2180,7 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
     auto kern = k_ffmlp_backward<WIDTH, IN_JB, NHM, RELU>;
     return launch_and_reduce(reinterpret_cast<const void*>(kern), lds.total, blocks, false, backward_buffer, grad_weights, n_params, st,
                              [&](dim3 grid, float* slabs, half_t* direct) {
-        hipLaunchKernelGGL(kern, grid, dim3(FF_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
+        NGP_LAUNCH(kern, grid, dim3(FF_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
                            (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds.pf_depth, (uint32_t)lds.total, serial);
     });
 }
@@ -2260,7 +2254,7 @@ extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const
         // over uninitialised memory: every other path OVERWRITES it) -- ADVICE r5.  (With NGP_FF_DEFER_REDUCE the later reduction writes it.)
         if (grad_weights && !(flags & NGP_FF_DEFER_REDUCE)) {
             const size_t n_w = (size_t)hidden_dim * ((size_t)input_dim + (size_t)hidden_dim * (num_layers - 1) + (size_t)output_dim);
-            hipError_t e = hipMemsetAsync(grad_weights, 0, n_w * sizeof(half_t), as_stream(stream));
+            hipError_t e = ::ngp::memset_async(grad_weights, 0, n_w * sizeof(half_t), as_stream(stream));
             NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
         }
         return NGP_OK;
@@ -2321,7 +2315,7 @@ extern "C" int ngp_ffmlp_reduce_slabs_pair(const void* slabs_a, uint32_t n_slabs
     if (blocks_a + blocks_b == 0) return NGP_OK;
     NGP_REQUIRE((!blocks_a || ((slabs_a || !n_slabs_a) && grad_weights_a)) && (!blocks_b || ((slabs_b || !n_slabs_b) && grad_weights_b)),
                 NGP_ERR_INVALID, "ffmlp_reduce_slabs_pair: NULL tensor");
-    hipLaunchKernelGGL(k_ffmlp_reduce_slabs_pair, dim3(blocks_a + blocks_b), dim3(RS_PARAMS * RS_GROUPS), 0, as_stream(stream), sets, found_inf);
+    NGP_LAUNCH(k_ffmlp_reduce_slabs_pair, dim3(blocks_a + blocks_b), dim3(RS_PARAMS * RS_GROUPS), 0, as_stream(stream), sets, found_inf);
     return check_launch("ffmlp_reduce_slabs_pair");
 }
 
@@ -2398,11 +2392,11 @@ extern "C" int ngp_network_forward_rows(const void* enc, const float* dirs, uint
     hipStream_t st = as_stream(stream);
     const bool planar = (flags & NGP_FF_INPUT_PLANAR) != 0;
     if (training)
-        hipLaunchKernelGGL((k_network_forward<true, TW, TT>), dim3(blocks), dim3(TW * 64), lds, st, (const half_t*)enc, planar, dirs, M_valid, (const half_t*)w_sigma,
+        NGP_LAUNCH((k_network_forward<true, TW, TT>), dim3(blocks), dim3(TW * 64), lds, st, (const half_t*)enc, planar, dirs, M_valid, (const half_t*)w_sigma,
                            (const half_t*)w_color, (half_t*)forward_buffer_sigma, (half_t*)h16, sigma, (half_t*)color_in, (half_t*)forward_buffer_color, rgb,
                            n_tiles, num_layers_sigma, num_layers_color, density_scale, rows_dev);
     else
-        hipLaunchKernelGGL((k_network_forward<false, IW, IT>), dim3(blocks), dim3(IW * 64), lds, st, (const half_t*)enc, planar, dirs, M_valid, (const half_t*)w_sigma,
+        NGP_LAUNCH((k_network_forward<false, IW, IT>), dim3(blocks), dim3(IW * 64), lds, st, (const half_t*)enc, planar, dirs, M_valid, (const half_t*)w_sigma,
                            (const half_t*)w_color, (half_t*)nullptr, (half_t*)nullptr, sigma, (half_t*)nullptr, (half_t*)nullptr, rgb, n_tiles,
                            num_layers_sigma, num_layers_color, density_scale, rows_dev);
     return check_launch("network_forward");

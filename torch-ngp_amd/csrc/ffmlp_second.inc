@@ -261,7 +261,7 @@ static int launch_backward_backward(const void* grad, const void* inputs, const 
     int rc;
 
     if (grad_inputs2 && !slope) {  // the first backward is linear in the inputs' direction: exactly zero
-        hipError_t e = hipMemsetAsync(grad_inputs2, 0, (size_t)B * in_dim * sizeof(half_t), st);
+        hipError_t e = ::ngp::memset_async(grad_inputs2, 0, (size_t)B * in_dim * sizeof(half_t), st);
         NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp_backward_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
     }
     if (need_d) {  // d_l of the first backward, recomputed
@@ -270,24 +270,24 @@ static int launch_backward_backward(const void* grad, const void* inputs, const 
         if ((rc = raise_lds(dk, lds_d, "ffmlp_backward_backward"))) return rc;
         const uint32_t blocks = layered_blocks(lds_d, n_tiles);
         if (act == ACT_RELU)
-            hipLaunchKernelGGL((k_ffmlp_dgrad_layered<WIDTH, true>), dim3(blocks), dim3(FF_THREADS), lds_d, st, (const half_t*)grad, (const half_t*)weights,
+            NGP_LAUNCH((k_ffmlp_dgrad_layered<WIDTH, true>), dim3(blocks), dim3(FF_THREADS), lds_d, st, (const half_t*)grad, (const half_t*)weights,
                                (const half_t*)fwd, d_buf, n_tiles, in_dim, num_layers, act, false, (half_t*)nullptr, false);
         else
-            hipLaunchKernelGGL((k_ffmlp_dgrad_layered<WIDTH, false>), dim3(blocks), dim3(FF_THREADS), lds_d, st, (const half_t*)grad, (const half_t*)weights,
+            NGP_LAUNCH((k_ffmlp_dgrad_layered<WIDTH, false>), dim3(blocks), dim3(FF_THREADS), lds_d, st, (const half_t*)grad, (const half_t*)weights,
                                (const half_t*)fwd, d_buf, n_tiles, in_dim, num_layers, act, false, (half_t*)nullptr, false);
         if ((rc = check_launch("ffmlp_backward_backward(dgrad)"))) return rc;
     }
     if (need_tangent) {
         auto kern = k_ffmlp_tangent_layered<WIDTH>;
         if ((rc = raise_lds(reinterpret_cast<const void*>(kern), lds_fwd, "ffmlp_backward_backward"))) return rc;
-        hipLaunchKernelGGL(kern, dim3(layered_blocks(lds_fwd, n_tiles)), dim3(FF_THREADS), lds_fwd, st, (const half_t*)u, (const half_t*)weights,
+        NGP_LAUNCH(kern, dim3(layered_blocks(lds_fwd, n_tiles)), dim3(FF_THREADS), lds_fwd, st, (const half_t*)u, (const half_t*)weights,
                            (const half_t*)fwd, p_buf, need_s ? q_buf : (half_t*)nullptr, (half_t*)grad_grad, n_tiles, in_dim, num_layers, act);
         if ((rc = check_launch("ffmlp_backward_backward(tangent)"))) return rc;
     }
     if (need_s) {
         auto kern = k_ffmlp_dgrad2_layered<WIDTH>;
         if ((rc = raise_lds(reinterpret_cast<const void*>(kern), lds_bwd, "ffmlp_backward_backward"))) return rc;
-        hipLaunchKernelGGL(kern, dim3(layered_blocks(lds_bwd, n_tiles)), dim3(FF_THREADS), lds_bwd, st, (const half_t*)grad, (const half_t*)weights,
+        NGP_LAUNCH(kern, dim3(layered_blocks(lds_bwd, n_tiles)), dim3(FF_THREADS), lds_bwd, st, (const half_t*)grad, (const half_t*)weights,
                            (const half_t*)fwd, (const half_t*)d_buf, (const half_t*)q_buf, s_buf, n_tiles, in_dim, num_layers, act,
                            need_dx ? (half_t*)grad_inputs2 : (half_t*)nullptr);
         if ((rc = check_launch("ffmlp_backward_backward(dgrad2)"))) return rc;
@@ -306,16 +306,16 @@ static int launch_backward_backward(const void* grad, const void* inputs, const 
     if (chunks < 1) chunks = 1;
     const uint32_t tiles_per_chunk = cdiv(n_tiles, chunks);
     chunks = cdiv(n_tiles, tiles_per_chunk);
-    hipLaunchKernelGGL(k_ffmlp_wgrad<WIDTH>, dim3(chunks, jobs), dim3(FF_THREADS), 0, st, (const half_t*)grad, (const half_t*)u, (const half_t*)p_buf,
+    NGP_LAUNCH(k_ffmlp_wgrad<WIDTH>, dim3(chunks, jobs), dim3(FF_THREADS), 0, st, (const half_t*)grad, (const half_t*)u, (const half_t*)p_buf,
                        (const half_t*)d_buf, n_tiles, in_dim, num_layers, false, tiles_per_chunk, slabs, (half_t*)nullptr);
     if ((rc = check_launch("ffmlp_backward_backward(wgrad, explicit)"))) return rc;
     uint32_t n_slabs = chunks;
     if (slope) {
         float* implicit = slabs + (size_t)chunks * n_params;
         // (the implicit terms have no output-layer part: that stretch of their slabs must read as zero in the reduction)
-        hipError_t e = hipMemsetAsync(implicit, 0, (size_t)chunks * n_params * sizeof(float), st);
+        hipError_t e = ::ngp::memset_async(implicit, 0, (size_t)chunks * n_params * sizeof(float), st);
         NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "ffmlp_backward_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(k_ffmlp_wgrad<WIDTH>, dim3(chunks, jobs - jobs_out), dim3(FF_THREADS), 0, st, (const half_t*)nullptr, (const half_t*)inputs,
+        NGP_LAUNCH(k_ffmlp_wgrad<WIDTH>, dim3(chunks, jobs - jobs_out), dim3(FF_THREADS), 0, st, (const half_t*)nullptr, (const half_t*)inputs,
                            (const half_t*)fwd, (const half_t*)s_buf, n_tiles, in_dim, num_layers, false, tiles_per_chunk, implicit, (half_t*)nullptr);
         if ((rc = check_launch("ffmlp_backward_backward(wgrad, implicit)"))) return rc;
         n_slabs = 2 * chunks;

@@ -652,10 +652,10 @@ static int launch_f64_forward(const float* inputs, const void* emb, const int32_
                               void* dy_dx, uint32_t gridtype, bool ac, uint32_t interp, hipStream_t st) {
     const dim3 grid(grid_blocks(B, F64_THREADS), L, 1);
     if (dy_dx)
-        hipLaunchKernelGGL((k_f64_grid_fwd<D, C, true>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L, lv,
+        NGP_LAUNCH((k_f64_grid_fwd<D, C, true>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L, lv,
                            (double*)dy_dx, gridtype, ac, interp);
     else
-        hipLaunchKernelGGL((k_f64_grid_fwd<D, C, false>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L,
+        NGP_LAUNCH((k_f64_grid_fwd<D, C, false>), grid, dim3(F64_THREADS), 0, st, inputs, (const double*)emb, offsets, (double*)outputs, B, L,
                            lv, (double*)nullptr, gridtype, ac, interp);
     return check_launch("grid_encode_forward(fp64)");
 }
@@ -694,13 +694,13 @@ static void f64_sort_level(const float* inputs, const int32_t* offsets, uint32_t
     const uint32_t tiles = cdiv(n, RADIX_TILE);
     const uint32_t tiles_per_group = cdiv(tiles, RADIX_MAX_GROUPS);
     const uint32_t groups = cdiv(tiles, tiles_per_group);
-    hipLaunchKernelGGL((k_f64_grid_records<D>), dim3(grid_blocks(B, F64_THREADS)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, scale, resolution,
+    NGP_LAUNCH((k_f64_grid_records<D>), dim3(grid_blocks(B, F64_THREADS)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, scale, resolution,
                        gridtype, ac, interp, keys[0], vals[0]);
     for (uint32_t pass = 0; pass < 4; pass++) {
         const uint32_t src = pass & 1u, shift = 8u * pass;
-        hipLaunchKernelGGL(k_f64_radix_hist, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], n, shift, tiles_per_group, groups, hist);
-        hipLaunchKernelGGL(k_f64_radix_scan, dim3(256), dim3(RADIX_MAX_GROUPS), 0, st, hist, groups, totals);
-        hipLaunchKernelGGL(k_f64_radix_scatter, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], vals[src], n, shift, tiles_per_group, groups, hist,
+        NGP_LAUNCH(k_f64_radix_hist, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], n, shift, tiles_per_group, groups, hist);
+        NGP_LAUNCH(k_f64_radix_scan, dim3(256), dim3(RADIX_MAX_GROUPS), 0, st, hist, groups, totals);
+        NGP_LAUNCH(k_f64_radix_scatter, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], vals[src], n, shift, tiles_per_group, groups, hist,
                            totals, keys[src ^ 1u], vals[src ^ 1u]);
     }
     // (an even number of passes: the sorted records are back in keys[0] / vals[0])
@@ -726,7 +726,7 @@ static int launch_f64_backward(const void* grad, const float* inputs, const int3
     for (uint32_t level = 0; level < L; level++) {
         const uint32_t *keys, *vals;
         f64_sort_level<D>(inputs, offsets, B, level, lv.scale[level], lv.res[level], gridtype, ac, interp, workspace, &keys, &vals, st);
-        hipLaunchKernelGGL((k_f64_grid_sum<D, C>), dim3(grid_blocks(n, F64_THREADS)), dim3(F64_THREADS), 0, st, keys, vals, n, (const double*)grad, inputs,
+        NGP_LAUNCH((k_f64_grid_sum<D, C>), dim3(grid_blocks(n, F64_THREADS)), dim3(F64_THREADS), 0, st, keys, vals, n, (const double*)grad, inputs,
                            offsets, (double*)grad_emb, B, level, lv.scale[level], ac, interp);
         const int rc = check_launch("grid_encode_backward(fp64)");
         if (rc) return rc;
@@ -752,7 +752,7 @@ int f64_grid_backward(const void* grad, const float* inputs, const int32_t* offs
         return NGP_ERR_INVALID;
     }();
     if (rc || !(dy_dx && grad_inputs)) return rc;
-    hipLaunchKernelGGL(k_f64_grid_input_bwd, dim3(cdiv(B * D, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, (const double*)dy_dx,
+    NGP_LAUNCH(k_f64_grid_input_bwd, dim3(cdiv(B * D, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, (const double*)dy_dx,
                        (double*)grad_inputs, B, L, D, C);
     return check_launch("grid_encode_backward(fp64 input)");
 }
@@ -760,7 +760,7 @@ int f64_grid_backward(const void* grad, const float* inputs, const int32_t* offs
 template <int D, int C>
 static int launch_f64_tv(const void* inputs, const void* emb, void* grad, const int32_t* offsets, float weight, uint32_t B, uint32_t L,
                          const GridLevels& lv, uint32_t gridtype, bool ac, hipStream_t st) {
-    hipLaunchKernelGGL((k_f64_grad_tv<D, C>), dim3(grid_blocks(B, F64_THREADS), L, 1), dim3(F64_THREADS), 0, st, (const double*)inputs, (const double*)emb,
+    NGP_LAUNCH((k_f64_grad_tv<D, C>), dim3(grid_blocks(B, F64_THREADS), L, 1), dim3(F64_THREADS), 0, st, (const double*)inputs, (const double*)emb,
                        (double*)grad, offsets, weight, B, lv, gridtype, ac);
     return check_launch("grad_total_variation(fp64)");
 }
@@ -779,9 +779,9 @@ template <int BANDS>
 static int launch_f64_sh(const void* inputs, void* outputs, uint32_t B, void* dy_dx, hipStream_t st) {
     const dim3 grid(cdiv(B, F64_THREADS));
     if (dy_dx)
-        hipLaunchKernelGGL((k_f64_sh_fwd<BANDS, true>), grid, dim3(F64_THREADS), 0, st, (const double*)inputs, (double*)outputs, B, (double*)dy_dx);
+        NGP_LAUNCH((k_f64_sh_fwd<BANDS, true>), grid, dim3(F64_THREADS), 0, st, (const double*)inputs, (double*)outputs, B, (double*)dy_dx);
     else
-        hipLaunchKernelGGL((k_f64_sh_fwd<BANDS, false>), grid, dim3(F64_THREADS), 0, st, (const double*)inputs, (double*)outputs, B, (double*)nullptr);
+        NGP_LAUNCH((k_f64_sh_fwd<BANDS, false>), grid, dim3(F64_THREADS), 0, st, (const double*)inputs, (double*)outputs, B, (double*)nullptr);
     return check_launch("sh_encode_forward(fp64)");
 }
 
@@ -801,7 +801,7 @@ int f64_sh_forward(const void* inputs, void* outputs, uint32_t B, uint32_t C, vo
 
 int f64_sh_backward(const void* grad, uint32_t B, uint32_t C, const void* dy_dx, void* grad_inputs, hipStream_t st) {
     if (B == 0) return NGP_OK;
-    hipLaunchKernelGGL(k_f64_sh_bwd, dim3(cdiv(B * 3, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, B, C * C, (const double*)dy_dx,
+    NGP_LAUNCH(k_f64_sh_bwd, dim3(cdiv(B * 3, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, B, C * C, (const double*)dy_dx,
                        (double*)grad_inputs);
     return check_launch("sh_encode_backward(fp64)");
 }
@@ -810,7 +810,7 @@ int f64_sh_backward(const void* grad, uint32_t B, uint32_t C, const void* dy_dx,
 
 using namespace ngp;
 
-#define F64_LAUNCH_1D(kernel, count, st, ...) hipLaunchKernelGGL(kernel, dim3(cdiv((count), F64_THREADS)), dim3(F64_THREADS), 0, st, __VA_ARGS__)
+#define F64_LAUNCH_1D(kernel, count, st, ...) NGP_LAUNCH(kernel, dim3(cdiv((count), F64_THREADS)), dim3(F64_THREADS), 0, st, __VA_ARGS__)
 
 extern "C" int ngp_near_far_from_aabb_f64(const double* rays_o, const double* rays_d, const double* aabb, uint32_t N, float min_near, double* nears,
                                           double* fars, ngp_stream_t stream) {

@@ -69,7 +69,7 @@ extern "C" int ngp_freq_encode_forward(const float* inputs, uint32_t B, uint32_t
     NGP_REQUIRE(inputs && outputs, NGP_ERR_INVALID, "freq_encode_forward: NULL tensor");
     uint64_t blocks = cdiv64((uint64_t)B * C, FQ_THREADS);
     if (blocks > 65536u) blocks = 65536u;
-    hipLaunchKernelGGL(k_freq_forward, dim3((uint32_t)blocks), dim3(FQ_THREADS), 0, as_stream(stream), inputs, B, D, C, outputs);
+    NGP_LAUNCH(k_freq_forward, dim3((uint32_t)blocks), dim3(FQ_THREADS), 0, as_stream(stream), inputs, B, D, C, outputs);
     return check_launch("freq_encode_forward");
 }
 
@@ -81,6 +81,6 @@ extern "C" int ngp_freq_encode_backward(const float* grad, const float* outputs,
     NGP_REQUIRE(grad && outputs && grad_inputs, NGP_ERR_INVALID, "freq_encode_backward: NULL tensor");
     uint64_t blocks = cdiv64((uint64_t)B * D, FQ_THREADS);
     if (blocks > 65536u) blocks = 65536u;
-    hipLaunchKernelGGL(k_freq_backward, dim3((uint32_t)blocks), dim3(FQ_THREADS), 0, as_stream(stream), grad, outputs, B, D, deg, C, grad_inputs);
+    NGP_LAUNCH(k_freq_backward, dim3((uint32_t)blocks), dim3(FQ_THREADS), 0, as_stream(stream), grad, outputs, B, D, deg, C, grad_inputs);
     return check_launch("freq_encode_backward");
 }

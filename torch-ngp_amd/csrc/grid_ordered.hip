@@ -367,22 +367,22 @@ static int launch_ordered_scatter(const OrdArgs& a, const char* what, hipStream_
     auto part_keys = [&](uint32_t i) { return i < w.n_arrays ? (uint32_t*)(ws + w.part_keys[i]) : nullptr; };
     auto part_vals = [&](uint32_t i) { return i < w.n_arrays ? (float*)(ws + w.part_vals[i]) : nullptr; };
     for (uint32_t level = 0; level < a.L; level++) {
-        hipLaunchKernelGGL((k_ord_records<D>), dim3(grid_blocks(a.B, ORD_THREADS)), dim3(ORD_THREADS), 0, st, a.inputs, a.offsets, a.B, level,
+        NGP_LAUNCH((k_ord_records<D>), dim3(grid_blocks(a.B, ORD_THREADS)), dim3(ORD_THREADS), 0, st, a.inputs, a.offsets, a.B, level,
                            a.lv.scale[level], a.lv.res[level], a.gridtype, a.align_corners, a.interp, a.im, keys[0], vals[0]);
         for (uint32_t pass = 0; pass < ORD_RADIX_PASSES; pass++) {
             const uint32_t src = pass & 1u;
-            hipLaunchKernelGGL(k_ord_radix_hist, dim3(groups), dim3(ORD_RADIX_TILE), 0, st, keys[src], n, pass, tiles_per_group, groups, a.offsets, level,
+            NGP_LAUNCH(k_ord_radix_hist, dim3(groups), dim3(ORD_RADIX_TILE), 0, st, keys[src], n, pass, tiles_per_group, groups, a.offsets, level,
                                hist);
-            hipLaunchKernelGGL(k_ord_radix_scan, dim3(256), dim3(ORD_MAX_GROUPS), 0, st, hist, groups, pass, a.offsets, level, totals);
-            hipLaunchKernelGGL(k_ord_radix_scatter, dim3(groups), dim3(ORD_RADIX_TILE), 0, st, keys[src], vals[src], n, pass, tiles_per_group, groups,
+            NGP_LAUNCH(k_ord_radix_scan, dim3(256), dim3(ORD_MAX_GROUPS), 0, st, hist, groups, pass, a.offsets, level, totals);
+            NGP_LAUNCH(k_ord_radix_scatter, dim3(groups), dim3(ORD_RADIX_TILE), 0, st, keys[src], vals[src], n, pass, tiles_per_group, groups,
                                a.offsets, level, hist, totals, keys[src ^ 1u], vals[src ^ 1u]);
         }
         // one wave per tile of 64 records, the exact grid (the order does not depend on it: a tile is a fixed slice of the array)
-        hipLaunchKernelGGL((k_ord_sum_records<T, D, C, ORDER>), dim3((uint32_t)cdiv64((uint64_t)cdiv(n, ORD_TILE) * ORD_TILE, ORD_THREADS)),
+        NGP_LAUNCH((k_ord_sum_records<T, D, C, ORDER>), dim3((uint32_t)cdiv64((uint64_t)cdiv(n, ORD_TILE) * ORD_TILE, ORD_THREADS)),
                            dim3(ORD_THREADS), 0, st, keys[0], vals[0], keys[1], vals[1], n, (const T*)a.grad, a.inputs, (const T*)a.u, a.offsets,
                            (T*)a.grad_embeddings, a.B, level, a.lv.scale[level], a.align_corners, a.interp, a.im, part_keys(0), part_vals(0));
         for (uint32_t i = 0; i < w.n_arrays; i++)
-            hipLaunchKernelGGL((k_ord_sum_partials<T, C>), dim3((uint32_t)cdiv64((uint64_t)cdiv(w.m[i], ORD_TILE) * ORD_TILE, ORD_THREADS)),
+            NGP_LAUNCH((k_ord_sum_partials<T, C>), dim3((uint32_t)cdiv64((uint64_t)cdiv(w.m[i], ORD_TILE) * ORD_TILE, ORD_THREADS)),
                                dim3(ORD_THREADS), 0, st, part_keys(i), part_vals(i), w.m[i], a.offsets, (T*)a.grad_embeddings, level, part_keys(i + 1),
                                part_vals(i + 1));
         const int rc = check_launch(what);
@@ -424,7 +424,7 @@ static int launch_ordered_second(const OrdArgs& a, const void* embeddings, void*
     if (grad_grad || grad_inputs2) {
         // the gather-only form of the atomic entry's kernel: grad_grad and grad_inputs2 with its bits
         const uint32_t blocks = (uint32_t)cdiv64(2ull * a.B, GG_THREADS);
-        hipLaunchKernelGGL((k_grid_bwd_bwd<T, D, C, false>), dim3(blocks), dim3(GG_THREADS), 0, st, (const T*)a.grad, a.inputs, (const T*)embeddings,
+        NGP_LAUNCH((k_grid_bwd_bwd<T, D, C, false>), dim3(blocks), dim3(GG_THREADS), 0, st, (const T*)a.grad, a.inputs, (const T*)embeddings,
                            a.offsets, (const T*)a.u, (T*)grad_grad, (T*)nullptr, (T*)grad_inputs2, a.B, a.L, a.lv, a.gridtype, a.align_corners,
                            a.interp);
         const int rc = check_launch(what);
@@ -484,10 +484,10 @@ extern "C" int ngp_grid_encode_backward_ordered(const void* grad, const float* i
     if (rc || !dy_dx) return rc;
     // the input term: the kernel of ngp_grid_encode_backward (grid_index.h), the same bits
     if (dtype == NGP_F16)
-        hipLaunchKernelGGL((k_grid_input_backward<half_t>), dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const half_t*)grad, (const half_t*)dy_dx,
+        NGP_LAUNCH((k_grid_input_backward<half_t>), dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const half_t*)grad, (const half_t*)dy_dx,
                            (half_t*)grad_inputs, B, L, D, C);
     else
-        hipLaunchKernelGGL((k_grid_input_backward<float>), dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const float*)grad, (const float*)dy_dx,
+        NGP_LAUNCH((k_grid_input_backward<float>), dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const float*)grad, (const float*)dy_dx,
                            (float*)grad_inputs, B, L, D, C);
     return check_launch("grid_encode_backward_ordered(input)");
 }

@@ -93,7 +93,7 @@ static int launch_bwd_bwd(const GGArgs& a, hipStream_t st) {
     } else {
         if (SCATTER || a.grad_grad || a.grad_inputs2) {
             const uint32_t blocks = (uint32_t)cdiv64(2ull * a.B, GG_THREADS);
-            hipLaunchKernelGGL((k_grid_bwd_bwd<T, D, C, SCATTER>), dim3(blocks), dim3(GG_THREADS), 0, st, (const T*)a.grad, a.inputs,
+            NGP_LAUNCH((k_grid_bwd_bwd<T, D, C, SCATTER>), dim3(blocks), dim3(GG_THREADS), 0, st, (const T*)a.grad, a.inputs,
                                (const T*)a.embeddings, a.offsets, (const T*)a.u, (T*)a.grad_grad, (T*)a.grad_embeddings, (T*)a.grad_inputs2, a.B, a.L,
                                a.lv, a.gridtype, a.align_corners, a.interp);
             const int rc = check_launch("grid_encode_backward_backward");
@@ -105,7 +105,7 @@ static int launch_bwd_bwd(const GGArgs& a, hipStream_t st) {
                 const uint32_t *keys, *vals;
                 f64_grid_sort_level((uint32_t)D, a.inputs, a.offsets, a.B, level, a.lv.scale[level], a.lv.res[level], a.gridtype, a.align_corners,
                                     a.interp, a.workspace, &keys, &vals, st);
-                hipLaunchKernelGGL((k_f64_grid_bwd_bwd_sum<D, C>), dim3(grid_blocks(n, GG_THREADS)), dim3(GG_THREADS), 0, st, keys, vals, n, (const double*)a.grad,
+                NGP_LAUNCH((k_f64_grid_bwd_bwd_sum<D, C>), dim3(grid_blocks(n, GG_THREADS)), dim3(GG_THREADS), 0, st, keys, vals, n, (const double*)a.grad,
                                    a.inputs, (const double*)a.u, a.offsets, (double*)a.grad_embeddings, a.B, level, a.lv.scale[level], a.align_corners,
                                    a.interp);
                 const int rc = check_launch("grid_encode_backward_backward(fp64)");

@@ -1786,7 +1786,7 @@ static int launch_forward(const float* inputs, const void* emb, const int32_t* o
             return NGP_ERR_INVALID;
         }
         dim3 grid(grid_blocks(B, FWD_THREADS), L, 1);
-        hipLaunchKernelGGL((k_grid_forward<T, D, C, true>), grid, dim3(FWD_THREADS), 0, st, inputs, (const T*)emb, offsets,
+        NGP_LAUNCH((k_grid_forward<T, D, C, true>), grid, dim3(FWD_THREADS), 0, st, inputs, (const T*)emb, offsets,
                            (T*)outputs, B, L, lv, (T*)dy_dx, gridtype, ac, interp);
         return check_launch("grid_encode_forward(dy_dx)");
     }
@@ -1800,7 +1800,7 @@ static int launch_forward(const float* inputs, const void* emb, const int32_t* o
         if (!ac) {  // the instant-ngp shape: index mode resolved per workgroup, dense levels one lane per point (k_grid_forward_fast)
             const bool smooth = interp == 1u, mapped = im.scale != 0.0f;
 #define NGP_LAUNCH_FWD_FAST(S, M)                                                                                                        \
-            hipLaunchKernelGGL((k_grid_forward_fast<S, M>), dim3(8u * max_slots), dim3(FWD_THREADS), 0, st, inputs, (const half_t*)emb, \
+            NGP_LAUNCH((k_grid_forward_fast<S, M>), dim3(8u * max_slots), dim3(FWD_THREADS), 0, st, inputs, (const half_t*)emb, \
                                offsets, (half_t*)outputs, B, L, lv, gridtype, interp, sched, ppb, im, sel)
             if (smooth && mapped) NGP_LAUNCH_FWD_FAST(true, true);
             else if (smooth) NGP_LAUNCH_FWD_FAST(true, false);
@@ -1810,7 +1810,7 @@ static int launch_forward(const float* inputs, const void* emb, const int32_t* o
             return check_launch("grid_encode_forward");
         }
     }
-    hipLaunchKernelGGL((k_grid_forward_pair<T, D, C>), dim3(8u * max_slots), dim3(FWD_THREADS), 0, st, inputs, (const T*)emb, offsets,
+    NGP_LAUNCH((k_grid_forward_pair<T, D, C>), dim3(8u * max_slots), dim3(FWD_THREADS), 0, st, inputs, (const T*)emb, offsets,
                        (T*)outputs, B, L, lv, gridtype, ac, interp, sched, ppb, im, sel);
     return check_launch("grid_encode_forward");
 }
@@ -1931,14 +1931,14 @@ static int launch_backward_bins(const void* grad, const float* inputs, const int
     const uint32_t blocks = persistent + ap.n_blocks;
     BinPlan bins = p.bins;
     bins.n_levels = p.n_binned;
-    hipLaunchKernelGGL(sort_kernel, dim3(blocks), dim3(BIN_THREADS), bin_smem, st, (const half_t*)grad, inputs, offsets, (half_t*)grad_emb, B, lv, gridtype,
+    NGP_LAUNCH(sort_kernel, dim3(blocks), dim3(BIN_THREADS), bin_smem, st, (const half_t*)grad, inputs, offsets, (half_t*)grad_emb, B, lv, gridtype,
                        ac, interp, im, bins, descriptors, records, ap);
     int rc = check_launch("grid_encode_backward(bin)");
     if (rc) return rc;
     static_assert(ACC_THREADS == RS_PARAMS * RS_GROUPS, "the slab reduction's blocks have the accumulate's shape");
     const uint32_t slab_blocks = p.slabs.total_blocks();
     const dim3 acc_grid(std::max(p.max_bins, slab_blocks), p.n_binned + (slab_blocks ? 1u : 0u));
-    hipLaunchKernelGGL(acc_kernel, acc_grid, dim3(ACC_THREADS), acc_smem, st, offsets, (half_t*)grad_emb, bins, (const uint32_t*)descriptors,
+    NGP_LAUNCH(acc_kernel, acc_grid, dim3(ACC_THREADS), acc_smem, st, offsets, (half_t*)grad_emb, bins, (const uint32_t*)descriptors,
                        (const uint2*)records, p.found_inf, p.slabs, p.overwrite, p.table_adam);
     p.slabs_done = slab_blocks != 0;
     return check_launch("grid_encode_backward(accumulate)");
@@ -1957,7 +1957,7 @@ static int launch_backward(const void* grad, const float* inputs, const int32_t*
         while (ppb > 128 && (uint64_t)cdiv(B, ppb) * plan.n_atomic < 2048) ppb >>= 1;
         dim3 grid(cdiv(B, ppb), plan.n_atomic, 1);
         constexpr int MERGE = BwdLanes<T, C>::LPP == 2 ? 3 : 1;  // two lanes per sample: the run merge is pure DPP
-        hipLaunchKernelGGL((k_grid_backward<T, D, C, MERGE>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets, (T*)grad_emb, B,
+        NGP_LAUNCH((k_grid_backward<T, D, C, MERGE>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets, (T*)grad_emb, B,
                            plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
         rc = check_launch("grid_encode_backward");
         if (rc) return rc;
@@ -1969,7 +1969,7 @@ static int launch_backward(const void* grad, const float* inputs, const int32_t*
         }
     }
     if (dy_dx && grad_inputs) {
-        hipLaunchKernelGGL((k_grid_input_backward<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const T*)grad,
+        NGP_LAUNCH((k_grid_input_backward<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const T*)grad,
                            (const T*)dy_dx, (T*)grad_inputs, B, L, (uint32_t)D, (uint32_t)C);
         rc = check_launch("grid_encode_backward(input)");
     }
@@ -1994,7 +1994,7 @@ template <typename T, int D, int C>
 static int launch_tv(const void* inputs, const void* emb, void* grad, const int32_t* offsets, float weight, uint32_t B,
                      uint32_t L, const GridLevels& lv, uint32_t gridtype, bool ac, hipStream_t st) {
     dim3 grid(grid_blocks(B, FWD_THREADS), L, 1);
-    hipLaunchKernelGGL((k_grad_tv<T, D, C>), grid, dim3(FWD_THREADS), 0, st, (const T*)inputs, (const T*)emb, (T*)grad,
+    NGP_LAUNCH((k_grad_tv<T, D, C>), grid, dim3(FWD_THREADS), 0, st, (const T*)inputs, (const T*)emb, (T*)grad,
                        offsets, weight, B, lv, gridtype, ac);
     return check_launch("grad_total_variation");
 }
@@ -2118,7 +2118,7 @@ extern "C" int ngp_debug_forward_bad_tile(const float* inputs, const void* embed
         }
     sc.level[0][0] = 0;
     sc.tile0[0][0] = cdiv(B, 1024u);  // one past the last tile
-    hipLaunchKernelGGL((k_grid_forward_pair<half_t, 3, 2>), dim3(8u), dim3(FWD_THREADS), 0, as_stream(stream), inputs, (const half_t*)embeddings,
+    NGP_LAUNCH((k_grid_forward_pair<half_t, 3, 2>), dim3(8u), dim3(FWD_THREADS), 0, as_stream(stream), inputs, (const half_t*)embeddings,
                        offsets, (half_t*)outputs, B, 2u, lv, 0u, false, 0u, sc, 1024u, InputMap{0.0f, 0.0f}, TableSel{nullptr, nullptr, nullptr});
     return check_launch("debug_forward_bad_tile");
 }
@@ -2223,12 +2223,12 @@ static int carried_slab_sets(SlabSets& carried, const ngp_slab_sets_t* s, bool s
 
 static int reduce_carried_alone(const SlabSets& carried, float* found_inf, hipStream_t st) {
     if (carried.total_blocks() == 0u) return NGP_OK;
-    hipLaunchKernelGGL(k_carried_reductions, dim3(carried.total_blocks()), dim3(RS_PARAMS * RS_GROUPS), 0, st, carried, found_inf);
+    NGP_LAUNCH(k_carried_reductions, dim3(carried.total_blocks()), dim3(RS_PARAMS * RS_GROUPS), 0, st, carried, found_inf);
     return check_launch("grid_encode_backward(carried reductions)");
 }
 
 static int zero_table(void* grad_embeddings, const int32_t* offsets_host, uint32_t L, uint32_t C, int dtype, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(grad_embeddings, 0, (size_t)offsets_host[L] * C * (dtype == NGP_F16 ? 2 : 4), st);
+    hipError_t e = ::ngp::memset_async(grad_embeddings, 0, (size_t)offsets_host[L] * C * (dtype == NGP_F16 ? 2 : 4), st);
     NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "grid_encode_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
     return NGP_OK;
 }
@@ -2256,9 +2256,9 @@ static int admit_table_adam(BackwardPlan& plan, const ngp_table_adam_t& tadam, b
 static int sweep_nonfinite(const void* grad_embeddings, uint64_t n, int dtype, float* found_inf, hipStream_t st) {
     const uint32_t blocks = (uint32_t)(cdiv64(n, 256 * 8) > 2048 ? 2048 : cdiv64(n, 256 * 8));
     if (dtype == NGP_F16)
-        hipLaunchKernelGGL(k_flag_nonfinite<half_t>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const half_t*)grad_embeddings, n, found_inf);
+        NGP_LAUNCH(k_flag_nonfinite<half_t>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const half_t*)grad_embeddings, n, found_inf);
     else
-        hipLaunchKernelGGL(k_flag_nonfinite<float>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const float*)grad_embeddings, n, found_inf);
+        NGP_LAUNCH(k_flag_nonfinite<float>, dim3(blocks ? blocks : 1), dim3(256), 0, st, (const float*)grad_embeddings, n, found_inf);
     return check_launch("grid_encode_backward(non-finite sweep)");
 }
 
@@ -2391,10 +2391,10 @@ extern "C" int ngp_grid_corner_indices(const float* inputs, const int32_t* offse
     dim3 grid(grid_blocks(B, FWD_THREADS), L, 1);
     const bool ac = align_corners != 0;
     switch (D) {
-        case 2: hipLaunchKernelGGL((k_grid_corner_indices<2>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
-        case 3: hipLaunchKernelGGL((k_grid_corner_indices<3>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
-        case 4: hipLaunchKernelGGL((k_grid_corner_indices<4>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
-        default: hipLaunchKernelGGL((k_grid_corner_indices<5>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
+        case 2: NGP_LAUNCH((k_grid_corner_indices<2>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
+        case 3: NGP_LAUNCH((k_grid_corner_indices<3>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
+        case 4: NGP_LAUNCH((k_grid_corner_indices<4>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
+        default: NGP_LAUNCH((k_grid_corner_indices<5>), grid, dim3(FWD_THREADS), 0, st, inputs, offsets, indices, B, lv, gridtype, ac); break;
     }
     return check_launch("grid_corner_indices");
 }

@@ -407,19 +407,19 @@ extern "C" int ngp_optim_adam_step_ex(int count, const uint64_t* n, float* const
         if (rc) return rc;
         const uint32_t blocks = opt_blocks(total);
         if (phases & NGP_OPT_PHASE_CHECK) {
-            hipLaunchKernelGGL(k_check_finite, dim3(blocks), dim3(OPT_THREADS), 0, st, ts, state);
+            NGP_LAUNCH(k_check_finite, dim3(blocks), dim3(OPT_THREADS), 0, st, ts, state);
             rc = check_launch("optim_adam_step(check)");
             if (rc) return rc;
         }
         if (phases & NGP_OPT_PHASE_UPDATE) {
-            hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(OPT_THREADS), 0, st, ts, (const float*)state, beta1, beta2, eps, grad_mult,
+            NGP_LAUNCH(k_adam, dim3(blocks), dim3(OPT_THREADS), 0, st, ts, (const float*)state, beta1, beta2, eps, grad_mult,
                                ema_one_minus_decay > 0.0f ? ema_one_minus_decay : 0.0f);
             rc = check_launch("optim_adam_step(adam)");
             if (rc) return rc;
         }
     }
     if (phases & NGP_OPT_PHASE_COMMIT) {
-        hipLaunchKernelGGL(k_update_scale, dim3(1), dim3(64), 0, st, state, growth_factor, backoff_factor, growth_interval,
+        NGP_LAUNCH(k_update_scale, dim3(1), dim3(64), 0, st, state, growth_factor, backoff_factor, growth_interval,
                            (phases & NGP_OPT_PHASE_FLIP) ? 1 : 0);
         return check_launch("optim_adam_step(scale)");
     }
@@ -467,7 +467,7 @@ extern "C" int ngp_optim_adam_small_commit(int count, const uint64_t* n, float* 
     if (prefix_blocks > 192u) prefix_blocks = 192u;
     uint32_t small_blocks = (uint32_t)cdiv64(total - table_prefix_params, (uint64_t)OPT_SMALL_THREADS);
     small_blocks = small_blocks < 1u ? 1u : (small_blocks > 32u ? 32u : small_blocks);   // (>= 1: somebody has to draw the last ticket)
-    hipLaunchKernelGGL(k_adam_small_commit, dim3(prefix_blocks + small_blocks), dim3(OPT_SMALL_THREADS), 0, as_stream(stream), ts, state, beta1, beta2, eps,
+    NGP_LAUNCH(k_adam_small_commit, dim3(prefix_blocks + small_blocks), dim3(OPT_SMALL_THREADS), 0, as_stream(stream), ts, state, beta1, beta2, eps,
                        grad_mult, growth_factor, backoff_factor, growth_interval, flip_parity, ta, reinterpret_cast<const half_t*>(table_grad_fp16),
                        table_prefix_params, prefix_blocks);
     return check_launch("optim_adam_small_commit");
@@ -475,7 +475,7 @@ extern "C" int ngp_optim_adam_small_commit(int count, const uint64_t* n, float* 
 
 extern "C" int ngp_optim_poison_shards(void* flat_grad_fp16, uint32_t shards, uint64_t payload, const float* state, ngp_stream_t stream) {
     NGP_REQUIRE(flat_grad_fp16 && state && shards >= 1 && payload >= 1, NGP_ERR_INVALID, "optim_poison_shards: NULL / empty argument");
-    hipLaunchKernelGGL(k_poison_shards, dim3(1), dim3(64), 0, as_stream(stream), reinterpret_cast<half_t*>(flat_grad_fp16), shards, payload, state);
+    NGP_LAUNCH(k_poison_shards, dim3(1), dim3(64), 0, as_stream(stream), reinterpret_cast<half_t*>(flat_grad_fp16), shards, payload, state);
     return check_launch("optim_poison_shards");
 }
 
@@ -483,7 +483,7 @@ extern "C" int ngp_optim_shard_verdict(const void* shard_grad_fp16, float* state
                                        ngp_stream_t stream) {
     NGP_REQUIRE(shard_grad_fp16 && state, NGP_ERR_INVALID, "optim_shard_verdict: NULL argument");
     NGP_REQUIRE(!flat_grad_fp16 || (shards >= 1 && payload >= 1), NGP_ERR_INVALID, "optim_shard_verdict: empty shard layout");
-    hipLaunchKernelGGL(k_shard_verdict, dim3(1), dim3(64), 0, as_stream(stream), reinterpret_cast<const half_t*>(shard_grad_fp16), state,
+    NGP_LAUNCH(k_shard_verdict, dim3(1), dim3(64), 0, as_stream(stream), reinterpret_cast<const half_t*>(shard_grad_fp16), state,
                        reinterpret_cast<half_t*>(flat_grad_fp16), shards, payload);
     return check_launch("optim_shard_verdict");
 }
@@ -497,6 +497,6 @@ extern "C" int ngp_optim_ema_update(int count, const uint64_t* n, float* const* 
     const int rc = fill_opt_tensors(ts, total, "optim_ema_update", OPT_PARAMS | OPT_EMA, count, n, params, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                     ema, 0.0f);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ema, dim3(opt_blocks(total)), dim3(OPT_THREADS), 0, as_stream(stream), ts, one_minus_decay);
+    NGP_LAUNCH(k_ema, dim3(opt_blocks(total)), dim3(OPT_THREADS), 0, as_stream(stream), ts, one_minus_decay);
     return check_launch("optim_ema_update");
 }

@@ -158,7 +158,7 @@ extern "C" int ngp_pipeline_mid_forward(const void* h16, const float* dirs, floa
                                         float density_scale, ngp_stream_t stream) {
     if (M == 0) return NGP_OK;
     NGP_REQUIRE(h16 && dirs && sigma && color_in, NGP_ERR_INVALID, "pipeline_mid_forward: NULL tensor");
-    hipLaunchKernelGGL(k_mid_forward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), (const half_t*)h16, dirs, sigma,
+    NGP_LAUNCH(k_mid_forward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), (const half_t*)h16, dirs, sigma,
                        (half_t*)color_in, M, M_valid, density_scale);
     return check_launch("pipeline_mid_forward");
 }
@@ -166,14 +166,14 @@ extern "C" int ngp_pipeline_mid_forward(const void* h16, const float* dirs, floa
 extern "C" int ngp_pipeline_rgb_forward(const void* out16, float* rgb, uint32_t M, ngp_stream_t stream) {
     if (M == 0) return NGP_OK;
     NGP_REQUIRE(out16 && rgb, NGP_ERR_INVALID, "pipeline_rgb_forward: NULL tensor");
-    hipLaunchKernelGGL(k_rgb_forward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), (const half_t*)out16, rgb, M);
+    NGP_LAUNCH(k_rgb_forward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), (const half_t*)out16, rgb, M);
     return check_launch("pipeline_rgb_forward");
 }
 
 extern "C" int ngp_pipeline_rgb_backward(const float* grad_rgb, const float* rgb, void* grad_out16, uint32_t M, ngp_stream_t stream) {
     if (M == 0) return NGP_OK;
     NGP_REQUIRE(grad_rgb && rgb && grad_out16, NGP_ERR_INVALID, "pipeline_rgb_backward: NULL tensor");
-    hipLaunchKernelGGL(k_rgb_backward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), grad_rgb, rgb, (half_t*)grad_out16, M);
+    NGP_LAUNCH(k_rgb_backward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), grad_rgb, rgb, (half_t*)grad_out16, M);
     return check_launch("pipeline_rgb_backward");
 }
 
@@ -181,7 +181,7 @@ extern "C" int ngp_pipeline_mid_backward(const float* grad_sigma, const void* h1
                                          float density_scale, ngp_stream_t stream) {
     if (M == 0) return NGP_OK;
     NGP_REQUIRE(grad_sigma && h16 && grad_color_in && grad_h16, NGP_ERR_INVALID, "pipeline_mid_backward: NULL tensor");
-    hipLaunchKernelGGL(k_mid_backward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), grad_sigma, (const half_t*)h16,
+    NGP_LAUNCH(k_mid_backward, dim3(cdiv(M, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), grad_sigma, (const half_t*)h16,
                        (const half_t*)grad_color_in, (half_t*)grad_h16, M, density_scale);
     return check_launch("pipeline_mid_backward");
 }
@@ -191,7 +191,7 @@ extern "C" int ngp_pipeline_mse_loss(const float* image, const float* target, ui
     NGP_REQUIRE(loss, NGP_ERR_INVALID, "pipeline_mse_loss: NULL tensor");
     NGP_REQUIRE(n == 0 || (image && target && grad_image), NGP_ERR_INVALID, "pipeline_mse_loss: NULL tensor");
     NGP_REQUIRE(n > 0, NGP_ERR_INVALID, "pipeline_mse_loss: empty batch (the mean of no values is undefined)");
-    hipLaunchKernelGGL(k_mse_loss, dim3(1), dim3(LOSS_THREADS), 0, as_stream(stream), image, target, n, loss_scale, loss, grad_image);
+    NGP_LAUNCH(k_mse_loss, dim3(1), dim3(LOSS_THREADS), 0, as_stream(stream), image, target, n, loss_scale, loss, grad_image);
     return check_launch("pipeline_mse_loss");
 }
 
@@ -303,7 +303,7 @@ extern "C" int ngp_linear_stack_pack(const float* const* weights, uint32_t depth
     LinearStack st;
     NGP_REQUIRE(weights && flat_fp16, NGP_ERR_INVALID, "linear_stack_pack: NULL tensor");
     if (int rc = linear_stack_args(weights, nullptr, depth, n_in, hidden, n_out, identity, st, "linear_stack_pack")) return rc;
-    hipLaunchKernelGGL(k_linear_stack_pack, dim3(cdiv(st.total(), PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), st, (half_t*)flat_fp16);
+    NGP_LAUNCH(k_linear_stack_pack, dim3(cdiv(st.total(), PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), st, (half_t*)flat_fp16);
     return check_launch("linear_stack_pack");
 }
 
@@ -312,7 +312,7 @@ extern "C" int ngp_linear_stack_unpack_grad(const void* grad_flat_fp16, uint32_t
     LinearStack st;
     NGP_REQUIRE(grads && grad_flat_fp16, NGP_ERR_INVALID, "linear_stack_unpack_grad: NULL tensor");
     if (int rc = linear_stack_args(nullptr, grads, depth, n_in, hidden, n_out, identity, st, "linear_stack_unpack_grad")) return rc;
-    hipLaunchKernelGGL(k_linear_stack_unpack, dim3(cdiv(st.total(), PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), st, (const half_t*)grad_flat_fp16);
+    NGP_LAUNCH(k_linear_stack_unpack, dim3(cdiv(st.total(), PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), st, (const half_t*)grad_flat_fp16);
     return check_launch("linear_stack_unpack_grad");
 }
 
@@ -323,7 +323,7 @@ extern "C" int ngp_pad_2d_fp16(const void* src, uint32_t src_rows, uint32_t src_
     NGP_REQUIRE(src_rows <= dst_rows && src_cols <= dst_cols && src_row_stride >= src_cols, NGP_ERR_INVALID,
                 "pad_2d_fp16: source [%u, %u] (row stride %u) does not fit the destination [%u, %u]", src_rows, src_cols, src_row_stride, dst_rows, dst_cols);
     NGP_REQUIRE((uint64_t)dst_rows * dst_cols <= 0xffffffffull, NGP_ERR_INVALID, "pad_2d_fp16: destination too large");
-    hipLaunchKernelGGL(k_pad_2d, dim3(cdiv(dst_rows * dst_cols, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), (const half_t*)src, src_rows,
+    NGP_LAUNCH(k_pad_2d, dim3(cdiv(dst_rows * dst_cols, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), (const half_t*)src, src_rows,
                        src_cols, src_row_stride, (half_t*)dst, dst_rows, dst_cols);
     return check_launch("pad_2d_fp16");
 }
@@ -334,7 +334,7 @@ extern "C" int ngp_rays_from_pixels(const float* poses, uint32_t B, float fx, fl
     NGP_REQUIRE(poses && rays_o && rays_d, NGP_ERR_INVALID, "rays_from_pixels: NULL tensor");
     NGP_REQUIRE(W > 0 && fx != 0.0f && fy != 0.0f, NGP_ERR_INVALID, "rays_from_pixels: W, fx and fy must be non-zero");
     NGP_REQUIRE((uint64_t)B * N <= 0xffffffffull, NGP_ERR_INVALID, "rays_from_pixels: B * N must fit 32 bits");
-    hipLaunchKernelGGL(k_rays_from_pixels, dim3(cdiv(B * N, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), poses, B, fx, fy, cx, cy, W,
+    NGP_LAUNCH(k_rays_from_pixels, dim3(cdiv(B * N, PL_THREADS)), dim3(PL_THREADS), 0, as_stream(stream), poses, B, fx, fy, cx, cy, W,
                        (const long long*)inds, inds_batch_stride, N, rays_o, rays_d);
     return check_launch("rays_from_pixels");
 }

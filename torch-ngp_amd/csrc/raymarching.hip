@@ -1820,7 +1820,7 @@ __global__ __launch_bounds__(CT_WAVES * 64) void k_composite_feat_bwd(const floa
 
 using namespace ngp;
 
-#define RM_LAUNCH_1D(kernel, count, st, ...) hipLaunchKernelGGL(kernel, dim3(cdiv((count), RM_THREADS)), dim3(RM_THREADS), 0, st, __VA_ARGS__)
+#define RM_LAUNCH_1D(kernel, count, st, ...) NGP_LAUNCH(kernel, dim3(cdiv((count), RM_THREADS)), dim3(RM_THREADS), 0, st, __VA_ARGS__)
 
 extern "C" int ngp_near_far_from_aabb(const float* rays_o, const float* rays_d, const float* aabb, uint32_t N, float min_near,
                                       float* nears, float* fars, ngp_stream_t stream) {
@@ -1888,7 +1888,7 @@ extern "C" int ngp_density_grid_update(const float* sigmas, const int64_t* cells
     const uint32_t blocks = cdiv(n_cells, DM_THREADS * DM_PER_THREAD);
     double* partials = reinterpret_cast<double*>(workspace);
     uint32_t* ticket = reinterpret_cast<uint32_t*>(partials + blocks);
-    hipLaunchKernelGGL(k_density_apply_mean, dim3(blocks), dim3(DM_THREADS), 0, st, density_grid, scratch, n_cells, decay, partials, ticket, mean_out);
+    NGP_LAUNCH(k_density_apply_mean, dim3(blocks), dim3(DM_THREADS), 0, st, density_grid, scratch, n_cells, decay, partials, ticket, mean_out);
     RM_LAUNCH_1D(k_packbits, n_cells / 8, st, (const float*)density_grid, n_cells / 8, density_thresh, (const float*)mean_out, bitfield);
     return check_launch("density_grid_update");
 }
@@ -1925,7 +1925,7 @@ static int march_rays_train_impl(const float* rays_o, const float* rays_d, const
     const dim3 block(MW_WAVES * 64);
     const bool const_dt = dt_gamma == 0.0f;
 #define MARCH_WAVE(WRITE, CDT)                                                                                                              \
-    hipLaunchKernelGGL((k_march_train_wave<WRITE, CDT>), dim3(ray_blocks + ((WRITE) ? extra : 0u)), block, 0, st, rays_o, rays_d, grid_bits,   \
+    NGP_LAUNCH((k_march_train_wave<WRITE, CDT>), dim3(ray_blocks + ((WRITE) ? extra : 0u)), block, 0, st, rays_o, rays_d, grid_bits,   \
                        bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays, noises, ws_windows, ws_masks,              \
                        (flags & NGP_MARCH_NOISE_FROM_SEED) != 0, aabb, min_near, ws, ray_blocks, self_scan ? counter : (int32_t*)nullptr,       \
                        zero_tail)
@@ -1936,7 +1936,7 @@ static int march_rays_train_impl(const float* rays_o, const float* rays_d, const
     rc = check_launch("march_rays_train(count)");
     if (rc) return rc;
     if (!self_scan) {
-        hipLaunchKernelGGL(k_march_train_scan, dim3(1), dim3(SCAN_THREADS), 0, st, rays, counter, N, M, (int)((flags & NGP_MARCH_RESET_COUNTER) != 0), ws);
+        NGP_LAUNCH(k_march_train_scan, dim3(1), dim3(SCAN_THREADS), 0, st, rays, counter, N, M, (int)((flags & NGP_MARCH_RESET_COUNTER) != 0), ws);
         rc = check_launch("march_rays_train(scan)");
         if (rc) return rc;
     }
@@ -1990,7 +1990,7 @@ extern "C" int ngp_composite_rays_train_forward_ex(const float* sigmas, const fl
     Finish fin;
     int rc = make_finish("composite_rays_train_forward", bg_mode, bg_scalar, bg, nears, fars, image_out, depth_out, true, &fin);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_composite_train_fwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs, deltas,
+    NGP_LAUNCH(k_composite_train_fwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs, deltas,
                        rays, M, N, T_thresh, weights_sum, depth, image, fin);
     return check_launch("composite_rays_train_forward");
 }
@@ -2016,7 +2016,7 @@ extern "C" int ngp_composite_rays_train_backward_ex(const float* grad_weights_su
     if (rc) return rc;
     const uint32_t ray_blocks = cdiv(N, CT_WAVES);
     const uint32_t tail_blocks = rows_used ? 32u : 0u;
-    hipLaunchKernelGGL(k_composite_train_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), grad_weights_sum,
+    NGP_LAUNCH(k_composite_train_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), grad_weights_sum,
                        grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, fin, rows_used,
                        ray_blocks);
     return check_launch("composite_rays_train_backward");
@@ -2028,7 +2028,7 @@ extern "C" int ngp_composite_rays_train_geo_forward(const float* sigmas, const f
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && distortion, NGP_ERR_INVALID,
                 "composite_rays_train_geo_forward: NULL tensor");
-    hipLaunchKernelGGL(k_composite_train_geo_fwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs, deltas,
+    NGP_LAUNCH(k_composite_train_geo_fwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs, deltas,
                        rays, M, N, T_thresh, weights_sum, depth, image, distortion);
     return check_launch("composite_rays_train_geo_forward");
 }
@@ -2041,7 +2041,7 @@ extern "C" int ngp_composite_rays_train_geo_backward(const float* grad_weights_s
     if (N == 0) return NGP_OK;
     NGP_REQUIRE(sigmas && rgbs && deltas && rays && weights_sum && depth && image && distortion && grad_sigmas && grad_rgbs, NGP_ERR_INVALID,
                 "composite_rays_train_geo_backward: NULL tensor");
-    hipLaunchKernelGGL(k_composite_train_geo_bwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), grad_weights_sum,
+    NGP_LAUNCH(k_composite_train_geo_bwd, dim3(cdiv(N, CT_WAVES)), dim3(CT_WAVES * 64), 0, as_stream(stream), grad_weights_sum,
                        grad_depth, grad_image, grad_distortion, sigmas, rgbs, deltas, rays, weights_sum, depth, image, distortion, M, N,
                        T_thresh, grad_sigmas, grad_rgbs);
     return check_launch("composite_rays_train_geo_backward");
@@ -2071,7 +2071,7 @@ extern "C" int ngp_composite_rays_train_features_forward(const float* sigmas, co
     const bool wide = C > 32;
     const uint32_t lp = wide ? 6u : feat_log2_segment(C);
 #define NGP_FEAT_FWD(F, WIDE)                                                                                                         \
-    hipLaunchKernelGGL((k_composite_feat_fwd<F, WIDE>), grid, block, 0, as_stream(stream), sigmas, static_cast<const F*>(feats), deltas, rays, M, N, \
+    NGP_LAUNCH((k_composite_feat_fwd<F, WIDE>), grid, block, 0, as_stream(stream), sigmas, static_cast<const F*>(feats), deltas, rays, M, N, \
                        C, lp, T_thresh, out)
     if (feat_dtype == NGP_F16) { if (wide) NGP_FEAT_FWD(_Float16, true); else NGP_FEAT_FWD(_Float16, false); }
     else { if (wide) NGP_FEAT_FWD(float, true); else NGP_FEAT_FWD(float, false); }
@@ -2091,7 +2091,7 @@ extern "C" int ngp_composite_rays_train_features_backward(const float* grad_out,
     const bool wide = C > 32;
     const uint32_t lp = wide ? 6u : feat_log2_segment(C);
 #define NGP_FEAT_BWD(F, WIDE)                                                                                                              \
-    hipLaunchKernelGGL((k_composite_feat_bwd<F, WIDE>), grid, block, 0, as_stream(stream), grad_out, sigmas, static_cast<const F*>(feats), deltas, rays, \
+    NGP_LAUNCH((k_composite_feat_bwd<F, WIDE>), grid, block, 0, as_stream(stream), grad_out, sigmas, static_cast<const F*>(feats), deltas, rays, \
                        out, M, N, C, lp, T_thresh, grad_sigmas, static_cast<F*>(grad_feats))
     if (feat_dtype == NGP_F16) { if (wide) NGP_FEAT_BWD(_Float16, true); else NGP_FEAT_BWD(_Float16, false); }
     else { if (wide) NGP_FEAT_BWD(float, true); else NGP_FEAT_BWD(float, false); }
@@ -2124,7 +2124,7 @@ extern "C" int ngp_composite_train_loss_backward(const float* sigmas, const floa
     if (rc) return rc;
     uint32_t* ws = reinterpret_cast<uint32_t*>(march_workspace);
     const uint32_t ray_blocks = cdiv(N, CT_WAVES), tail_blocks = 32u;
-    hipLaunchKernelGGL(k_composite_train_loss_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs,
+    NGP_LAUNCH(k_composite_train_loss_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs,
                        deltas, rays, M, N, T_thresh, weights_sum, fin, target, loss_scale, ray_err, ws + 1, loss, grad_sigmas,
                        (half_t*)grad_out16, (const uint32_t*)ws, ray_blocks, ws + march_ws_ticket_word(N));
     return check_launch("composite_train_loss_backward");
@@ -2152,7 +2152,7 @@ extern "C" int ngp_composite_train_geo_loss_backward(const float* sigmas, const 
     if (rc) return rc;
     uint32_t* ws = reinterpret_cast<uint32_t*>(march_workspace);
     const uint32_t ray_blocks = cdiv(N, CT_WAVES), tail_blocks = 32u;
-    hipLaunchKernelGGL(k_composite_train_geo_loss_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs,
+    NGP_LAUNCH(k_composite_train_geo_loss_bwd, dim3(ray_blocks + tail_blocks), dim3(CT_WAVES * 64), 0, as_stream(stream), sigmas, rgbs,
                        deltas, rays, M, N, T_thresh, weights_sum, fin, target, lambda_distortion, lambda_depth, target_depth, depth_weight,
                        loss_scale, depth_raw, distortion, ray_err, ws + 1, loss, grad_sigmas, (half_t*)grad_out16, (const uint32_t*)ws,
                        ray_blocks, ws + march_ws_ticket_word(N));
@@ -2231,7 +2231,7 @@ extern "C" int ngp_compact_rays(const int32_t* rays_alive, uint32_t n_alive, int
     NGP_REQUIRE(rays_alive && out_alive && out_count && workspace, NGP_ERR_INVALID, "compact_rays: NULL tensor");
     hipStream_t st = as_stream(stream);
     if (n_alive == 0) {
-        hipError_t e = hipMemsetAsync(out_count, 0, sizeof(int32_t), st);
+        hipError_t e = ::ngp::memset_async(out_count, 0, sizeof(int32_t), st);
         NGP_REQUIRE(e == hipSuccess, NGP_ERR_LAUNCH, "compact_rays: memset failed");
         return NGP_OK;
     }

@@ -12,7 +12,9 @@ void set_error(const char* fmt, ...) {
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_last_error = buf;
+    if (cmdlist::List* l = cmdlist::recording()) l->poison();   // an entry failed while a list records: the list holds half a chain
 }
+void set_error_message(const char* message) { g_last_error = message; }
 }  // namespace ngp
 
 extern "C" const char* ngp_last_error(void) { return ngp::g_last_error.c_str(); }

@@ -107,9 +107,9 @@ template <typename T, int BANDS>
 static int launch_sh(const void* inputs, void* outputs, uint32_t B, void* dy_dx, hipStream_t st) {
     dim3 grid(cdiv(B, SH_THREADS));
     if (dy_dx)
-        hipLaunchKernelGGL((k_sh_forward<T, BANDS, true>), grid, dim3(SH_THREADS), 0, st, (const T*)inputs, (T*)outputs, B, (T*)dy_dx);
+        NGP_LAUNCH((k_sh_forward<T, BANDS, true>), grid, dim3(SH_THREADS), 0, st, (const T*)inputs, (T*)outputs, B, (T*)dy_dx);
     else
-        hipLaunchKernelGGL((k_sh_forward<T, BANDS, false>), grid, dim3(SH_THREADS), 0, st, (const T*)inputs, (T*)outputs, B, (T*)nullptr);
+        NGP_LAUNCH((k_sh_forward<T, BANDS, false>), grid, dim3(SH_THREADS), 0, st, (const T*)inputs, (T*)outputs, B, (T*)nullptr);
     return check_launch("sh_encode_forward");
 }
 
@@ -154,10 +154,10 @@ extern "C" int ngp_sh_encode_backward(const void* grad, const void* inputs, uint
     if (dtype == NGP_F64) return f64_sh_backward(grad, B, C, dy_dx, grad_inputs, as_stream(stream));
     hipStream_t st = as_stream(stream);
     if (dtype == NGP_F16)
-        hipLaunchKernelGGL((k_sh_backward<half_t>), dim3(cdiv(B * 3, 256)), dim3(256), 0, st, (const half_t*)grad, B, C * C,
+        NGP_LAUNCH((k_sh_backward<half_t>), dim3(cdiv(B * 3, 256)), dim3(256), 0, st, (const half_t*)grad, B, C * C,
                            (const half_t*)dy_dx, (half_t*)grad_inputs);
     else
-        hipLaunchKernelGGL((k_sh_backward<float>), dim3(cdiv(B * 3, 256)), dim3(256), 0, st, (const float*)grad, B, C * C,
+        NGP_LAUNCH((k_sh_backward<float>), dim3(cdiv(B * 3, 256)), dim3(256), 0, st, (const float*)grad, B, C * C,
                            (const float*)dy_dx, (float*)grad_inputs);
     return check_launch("sh_encode_backward");
 }

@@ -29,11 +29,19 @@ the same order per batch; only the in-kernel start offsets of `perturb=True` are
 step count (the two agree unless a step was skipped).  The step before an occupancy refresh does not look ahead: the refreshed bitfield
 must be marched.
 
+Command lists (autograd-free iteration with `optim.NGPAdam`, single GPU; `_cmdlist_ok`): the rest graph's chain consists of the library's own
+launches, so it is also recorded into a native command list (cmdlist.py, csrc/cmdlist.cpp) while it is captured, and a step replays the
+list -- the same launches with the same arguments issued from C, 6-7 us per step less idle GPU at the step boundary than the graph launch
+(DESIGN.md section 4).  The graph is kept: it owns the buffers the list points into and serves every configuration that is not eligible.
+NGP_STEP_CMDLIST=0 keeps the graph replay; NGP_STEP_MARCH_AT moves the start of the lookahead march to a mark inside the chain (measured:
+slower everywhere but at the step boundary, the default).
+
 Requirements: a torch optimizer constructed with `capturable=True` (and preferably `fused=True`) plus a GradScaler, or
 `optim.NGPAdam` with `scaler=None` (it owns the loss scale; `averager` may then be the optimizer itself); the model has completed at least
 one `update_extra_state` after 16 eager steps (`model.mean_count > 0`) -- before that the sample buffer is sized for the
 worst case and read back, which cannot be captured, and `step()` simply runs eagerly.
 """
+import contextlib
 import os
 
 import torch
@@ -47,6 +55,14 @@ def _capture_into(g, **kw):
     if dist.is_available() and dist.is_initialized():
         kw.setdefault('capture_error_mode', 'thread_local')
     return torch.cuda.graph(g, **kw)
+
+
+# NGP_STEP_MARCH_AT: where in the main chain the side stream may begin the next batch's march (lookahead steps replayed from a command
+# list): the step boundary (what the graph replay does), or a mark at (kernel name, 1: behind that launch / 0: in front of it) --
+# behind the network forward, behind the compositor, behind the sigma backward (= where the record sort starts), behind the sort
+MARCH_MARKS = {'boundary': None, 'net': ('k_network_forward', 1), 'composite': ('k_composite_train', 1), 'sigma': ('k_grid_backward_bin', 0),
+               'sort': ('k_grid_backward_accumulate', 0)}
+MARCH_MARK_ID = 1
 
 
 _PARKED = []   # graphs of steppers that were collected while another stepper was capturing (GraphedTrainStep.close)
@@ -104,6 +120,14 @@ class GraphedTrainStep:
         self.capacity_ladder = tuple(float(f) for f in (capacity_ladder or ()))
         self.n_switches = 0
         self.graphs = None
+        # the rest graphs' launch chains as native command lists (cmdlist.CommandList, one per rest graph of the active capacity; None: the
+        # graphs are replayed).  NGP_STEP_CMDLIST=0: keep the graph replay in this build
+        self.lists = None
+        self.use_lists = os.environ.get('NGP_STEP_CMDLIST', '1') != '0'
+        self.march_at = os.environ.get('NGP_STEP_MARCH_AT', 'boundary')
+        if self.march_at not in MARCH_MARKS:
+            raise ValueError(f'NGP_STEP_MARCH_AT={self.march_at!r}: one of {sorted(MARCH_MARKS)}')
+        self.n_list_replays = 0
         self.loss = None
         self.n_captures = 0
         self.capture_error = None
@@ -181,6 +205,11 @@ class GraphedTrainStep:
                 comm.synchronize()
             if torch.cuda.is_available() and (self.graphs is not None or self.update_graphs):
                 torch.cuda.current_stream().synchronize()
+            # the lists go before the graphs that own their buffers (this object steps through the graphs from here on)
+            for snap in [self.__dict__] + list(getattr(self, '_captured', {}).values()):
+                for cl in snap.get('lists') or ():
+                    cl.destroy()
+                snap['lists'] = None
             _drain_parked()
         except Exception:  # noqa: BLE001 -- interpreter shutdown: the device context may be gone already
             pass
@@ -194,7 +223,7 @@ class GraphedTrainStep:
             return None
         return ((mc + 128 + self.quantum - 1) // self.quantum) * self.quantum
 
-    _SNAP = ('graphs', 'la', 'loss', 'la_apply', '_rest_pool', 'sharded', 'used_direct', 'table_fused', 'producers_check', '_checked_ok')
+    _SNAP = ('graphs', 'lists', 'la', 'loss', 'la_apply', '_rest_pool', 'sharded', 'used_direct', 'table_fused', 'producers_check', '_checked_ok')
 
     def _snapshot(self):
         return {k: getattr(self, k, None) for k in self._SNAP}
@@ -302,7 +331,9 @@ class GraphedTrainStep:
             replayed_fused_table_step(self.optimizer)
 
     def _captures_discarded(self):
-        """the graphs are dropped (a failed capture) or about to be recorded anew: the optimizer forgets what it recorded at capture time"""
+        """the graphs are dropped (a failed capture) or about to be recorded anew: the optimizer forgets what it recorded at capture time,
+        and the command lists go with the graphs"""
+        self.lists = None
         fn = getattr(self.optimizer, 'captures_discarded', None)
         if fn is not None:
             fn()
@@ -324,6 +355,36 @@ class GraphedTrainStep:
                                                          cfg.S, cfg.H, cfg.gridtype, cfg.align, capi.NGP_F16))
         rest = sum(p.numel() for p in getattr(self.optimizer, 'flat_params', []) if p is not emb)
         return prefix != 0xffffffff and table_fusion_fits(prefix, emb.shape[1], rest)
+
+    def _cmdlist_ok(self, with_march):
+        """THE eligibility of a captured chain for a command list: the autograd-free iteration with producer-checked gradients closed by
+        `optimizer.step(gradients_checked=True)`, no GradScaler object, no averager -- what is captured then consists of the library's own
+        launches by construction (fused.fused_train_iteration_split, optim.NGPAdam.step): a list records nothing else, so a torch kernel
+        in the chain would be lost.  Two places where torch would launch one are excluded: a background-colour TENSOR (converted inside
+        the capture) and, where the chain begins with the march (with_march: no lookahead), perturb=False -- the marcher then reads its
+        start offsets from a torch.zeros tensor filled inside the capture; with perturb=True it draws them from the seed word.
+        Everything else keeps the graph replay: torch.optim, the autograd path, replicated and sharded data-parallel steps.  Call it after
+        `_checked_ok` is decided (inside `_capture`)."""
+        kw = self.render_kwargs
+        if torch.is_tensor(kw.get('bg_color', None)) or (with_march and not kw.get('perturb', False)):
+            return False
+        return bool(self.use_lists and self.direct and self.scaler is None and self.averager is None and self._checked_ok and self._direct_ok())
+
+    def _recording(self, lists, with_march=False):
+        """context of a capture body: records it into a new command list appended to `lists` when the step is eligible, else does nothing"""
+        if not self._cmdlist_ok(with_march):
+            return contextlib.nullcontext()
+        from cmdlist import CommandList
+        lists.append(CommandList())
+        return lists[-1]
+
+    def _replay_rest(self, g, cl):
+        """one step's main chain on the current stream: from its command list where one exists, else the graph"""
+        if cl is None:
+            g.replay()
+        else:
+            cl.replay(torch.cuda.current_stream().cuda_stream)
+            self.n_list_replays += 1
 
     def _clean_deposits(self):
         """before replaying graphs whose producers ADD into the deposit buffers: zero what an overwriting producer left behind"""
@@ -441,10 +502,13 @@ class GraphedTrainStep:
             self._capture_lookahead()
         elif self.averager is None:
             g = torch.cuda.CUDAGraph()
+            lists = []
             with _capture_into(g):
-                self.loss = self._iteration_front().detach()
-                self._iteration_back()
+                with self._recording(lists, with_march=True):
+                    self.loss = self._iteration_front().detach()
+                    self._iteration_back()
             self.graphs = (g,)
+            self.lists = tuple(lists) or None
         elif self.averager is self.optimizer and getattr(self.optimizer, 'shard', False) and self._direct_ok():
             # sharded data-parallel update (optim.NGPAdam, shard=True): graphs around the two collectives,
             #   [march] -> wait for the shadow all-gather of the previous step -> [encode .. backward, local non-finite sweep, poison]
@@ -497,14 +561,14 @@ class GraphedTrainStep:
         if sharded:
             opt.wait_shadows()
             torch.cuda.synchronize()
-        la = []
+        la, lists = [], []
         for p in range(2):
             args, kwargs = self._iteration_args(self._checked_ok, p)   # (a sharded update has no fused table: it needs averager=None)
             march, rest = fused_train_iteration_split(*args, **kwargs)
             gm, gr = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with _capture_into(gm, pool=pool_march):
                 march()
-            with _capture_into(gr, pool=pool_rest):
+            with _capture_into(gr, pool=pool_rest), (contextlib.nullcontext() if sharded else self._recording(lists)):
                 opt.zero_grad(set_to_none=True)
                 loss = rest()[0][0].detach()
                 if not sharded:
@@ -525,6 +589,14 @@ class GraphedTrainStep:
                 opt.apply(zero=not self._overwrites_table())
         self.la = la
         self.graphs = tuple(g for e in la for g in e[:2])
+        self.lists = tuple(lists) or None
+        where = MARCH_MARKS[self.march_at]
+        if self.lists and where is not None:
+            for cl in self.lists:   # the event behind (before) the named launch: the side stream's march of the next batch waits for it
+                at = [i for i, n in enumerate(cl.names()) if where[0] in n]
+                if not at:
+                    raise RuntimeError(f'GraphedTrainStep: NGP_STEP_MARCH_AT={self.march_at}: no {where[0]} launch in the recorded chain')
+                cl.mark(MARCH_MARK_ID, at[-1] + where[1])
         self._rest_pool = pool_rest
         self.used_direct = True
 
@@ -666,9 +738,19 @@ class GraphedTrainStep:
             self.la_slot_event.record(main)
         self.la_ready[p] = None
         q = 1 - p
-        if next_rays is not None and (self.global_step + 1) % self.update_interval != 0:
+        ahead = next_rays is not None and (self.global_step + 1) % self.update_interval != 0
+        cl = self.lists[p] if self.lists else None
+        # a marked list: the main chain goes first and the side stream waits for the mark inside it -- later than the step boundary, never
+        # earlier (set q was read by the previous step's chain, which `main` holds in front of this one)
+        early = ahead and cl is not None and MARCH_MARKS[self.march_at] is not None
+        if early:
+            self._replay_rest(gr, cl)
+        if ahead:
             side = self.la_side
-            side.wait_stream(main)                  # set q was read by the previous step's rest graph, queued on `main` before this point
+            if early:
+                cl.wait_mark(MARCH_MARK_ID, side.cuda_stream)
+            else:
+                side.wait_stream(main)              # set q was read by the previous step's rest graph, queued on `main` before this point
             with torch.cuda.stream(side):
                 no, nd = next_rays[0], next_rays[1]
                 dst, src = [self.la_rays_o[q], self.la_rays_d[q]], [no.view_as(self.la_rays_o[q]), nd.view_as(self.la_rays_d[q])]
@@ -702,8 +784,8 @@ class GraphedTrainStep:
             opt.reduce_gradients()
             self.la_apply.replay()      # (issued eagerly instead -- one replay boundary less, three eager launches more: 0.530 against 0.516 ms, EXPERIMENTS.md)
             opt.gather_shadows()
-        else:
-            gr.replay()
+        elif not early:
+            self._replay_rest(gr, cl)
         self.la_cur = q
         return loss
 
@@ -788,7 +870,7 @@ class GraphedTrainStep:
         # the batch into the static input buffers: ONE multi-tensor copy kernel (three separate copies cost ~5 us each plus the gaps)
         torch._foreach_copy_([self.rays_o, self.rays_d, self.target], [rays_o.view_as(self.rays_o), rays_d.view_as(self.rays_d), target],
                              non_blocking=True)
-        self.graphs[0].replay()
+        self._replay_rest(self.graphs[0], self.lists[0] if self.lists else None)
         if len(self.graphs) == 2:
             self.averager.all_reduce()
             self.graphs[1].replay()
