@@ -908,6 +908,58 @@ int ngp_cmdlist_replay(void* list, ngp_stream_t stream);
 int ngp_cmdlist_wait_mark(void* list, uint32_t mark_id, ngp_stream_t stream);
 int ngp_cmdlist_destroy(void* list);
 
+/* ---------------------------------------------------------------------------------------------
+ * Camera-pose gradients through the training rays -- EXTENSION (csrc/ray_gradient.hip).  ctypes-only: the compiled
+ * _raymarching / _gridencoder tables stay the reference's.
+ * ---------------------------------------------------------------------------------------------
+ * The marcher's sample parameters are constants: a sample of ray n is x_i = clamp(o_n + t_i d_n, -bound, bound), and t_i, deltas and the
+ * choice of samples do not depend on the pose.  m_ij = 1 if |x_ij| < bound else 0 (a clamped coordinate passes no gradient).  rays [N,3]
+ * int32 = (ray index n, first sample, sample count) as ngp_march_rays_train leaves it; a row with count 0, first + count > M or n >= N owns
+ * no samples.  Every sum is taken in a fixed order without float atomics: the same bits from every launch, whatever the order of the rows
+ * of `rays`.  All entries: bound > 0; a NULL or misaligned required pointer, an unsupported shape: NGP_ERR_INVALID before any device work;
+ * M == 0 or N == 0: NGP_OK, no kernel, the outputs zeroed. */
+/* extends march_rays_train (raymarching.cu:345-460), which keeps t to itself: ts [M] recovered from its output,
+ * t_i = sum_j m_ij d_j (x_ij - o_j) / sum_j m_ij d_j^2 (0 when the denominator is 0; formed in double, rounded once).  xyzs [M,3], rays_o /
+ * rays_d [N,3]; rows no ray owns are 0. */
+int ngp_ray_sample_ts(const float* xyzs, const float* rays_o, const float* rays_d, const int32_t* rays, uint32_t M, uint32_t N, float bound,
+                      float* ts, ngp_stream_t stream);
+int ngp_ray_sample_ts_f64(const double* xyzs, const double* rays_o, const double* rays_d, const int32_t* rays, uint32_t M, uint32_t N,
+                          float bound, double* ts, ngp_stream_t stream);
+/* the sample statement of march_rays_train (raymarching.cu:433-441) on given ts: xyzs [M,3] = clamp(fma(t, d, o), -bound, bound), dirs [M,3]
+ * = d; rows no ray owns are zero */
+int ngp_ray_points_forward(const float* rays_o, const float* rays_d, const float* ts, const int32_t* rays, uint32_t M, uint32_t N, float bound,
+                           float* xyzs, float* dirs, ngp_stream_t stream);
+int ngp_ray_points_forward_f64(const double* rays_o, const double* rays_d, const double* ts, const int32_t* rays, uint32_t M, uint32_t N,
+                               float bound, double* xyzs, double* dirs, ngp_stream_t stream);
+/* its backward, one wavefront per ray like ngp_composite_rays_train_backward:
+ *   grad_rays_o[n,j] = sum_i m_ij grad_xyzs[i,j]
+ *   grad_rays_d[n,j] = sum_i t_i m_ij grad_xyzs[i,j] + sum_i grad_dirs[i,j] + (J_SH4(d_n)^T sum_i grad_sh16[i, 0:16])_j
+ * grad_dirs [M,3] (optional) and grad_sh16 [M,32] fp16 (optional, 16-byte aligned: the colour net's input gradient of
+ * ngp_ffmlp_backward_ex, columns 0..15 = dL/dSH4(d) on the raw direction as ngp_pipeline_mid_forward evaluates it) may be NULL.  Every
+ * ray's row of grad_rays_o / grad_rays_d [N,3] is written (zeros for a ray without samples); rows of the per-sample tensors that no ray
+ * owns are never read. */
+int ngp_ray_points_backward(const float* grad_xyzs, const float* grad_dirs, const void* grad_sh16, const float* xyzs, const float* ts,
+                            const float* rays_d, const int32_t* rays, uint32_t M, uint32_t N, float bound, float* grad_rays_o,
+                            float* grad_rays_d, ngp_stream_t stream);
+int ngp_ray_points_backward_f64(const double* grad_xyzs, const double* grad_dirs, const double* xyzs, const double* ts, const double* rays_d,
+                                const int32_t* rays, uint32_t M, uint32_t N, float bound, double* grad_rays_o, double* grad_rays_d,
+                                ngp_stream_t stream);
+/* extends kernel_input_backward (gridencoder.cu:343-369) to the fused path, which has no dy_dx: grad_enc [L][M][2] fp16 planar (what
+ * ngp_ffmlp_backward_ex writes with NGP_FF_DX_PLANAR), xyzs [M,3] fp32, the fp16 table and offsets of ngp_grid_encode_forward_ex ->
+ *   grad_xyzs[i,j] = 1 / (2 bound) * sum_l sum_c grad_enc[l,i,c] dy_dx[i,l,j,c]       (bound == 0: unit coordinates, factor 1)
+ * with dy_dx what ngp_grid_encode_forward defines (level scale * phi' * the weights of the other two coordinates * the difference of the
+ * two table values), recomputed from the table in fp32 instead of stored and read back in fp16; levels summed in order, a point outside
+ * the unit cube gets zeros.  D = 3, C = 2, dtype NGP_F16 only -- anything else: NGP_ERR_INVALID. */
+int ngp_grid_input_gradient(const void* grad_enc, const float* xyzs, const void* embeddings, const int32_t* offsets, uint32_t M, uint32_t D,
+                            uint32_t C, uint32_t L, float S, uint32_t H, uint32_t gridtype, int align_corners, uint32_t interp, int dtype,
+                            float bound, float* grad_xyzs, ngp_stream_t stream);
+/* the backward of ngp_rays_from_pixels in the poses (intrinsics, W, inds, inds_batch_stride as in the forward; dcam, the normalised pinhole
+ * direction, is recomputed per pixel): grad_rays_o, grad_rays_d [B,N,3] -> grad_poses [B,4,4],
+ *   grad_poses[b,r,3] = sum_n grad_rays_o[b,n,r],  grad_poses[b,r,c] = sum_n grad_rays_d[b,n,r] dcam[n,c]  (r, c < 3),  row 3 = 0 */
+int ngp_rays_from_pixels_backward(const float* grad_rays_o, const float* grad_rays_d, uint32_t B, float fx, float fy, float cx, float cy,
+                                  uint32_t W, const int64_t* inds, uint32_t inds_batch_stride, uint32_t N, float* grad_poses,
+                                  ngp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,15 @@ _SIGNATURES = {
     'ngp_cmdlist_replay': [_vp, _vp],
     'ngp_cmdlist_wait_mark': [_vp, _u32, _vp],
     'ngp_cmdlist_destroy': [_vp],
+    # camera-pose gradients through the training rays (csrc/ray_gradient.hip)
+    'ngp_ray_sample_ts': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp],
+    'ngp_ray_sample_ts_f64': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp],
+    'ngp_ray_points_forward': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp],
+    'ngp_ray_points_forward_f64': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp],
+    'ngp_ray_points_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp],
+    'ngp_ray_points_backward_f64': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp],
+    'ngp_grid_input_gradient': [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _u32, _i32, _f32, _vp, _vp],
+    'ngp_rays_from_pixels_backward': [_vp, _vp, _u32, _f32, _f32, _f32, _f32, _u32, _vp, _u32, _u32, _vp, _vp],
 }
 for _name, _args in _SIGNATURES.items():
     _fn = getattr(lib, _name)

@@ -108,6 +108,23 @@ struct LevelIndexer {
 struct InputMap {
     float shift, scale;
 };
+// host: the map of a call's `bound` (<= 0: unit coordinates)
+inline InputMap make_input_map(float bound) {
+    InputMap im{0.0f, 0.0f};
+    if (bound > 0.0f) {
+        im.shift = bound;
+        im.scale = 1.0f / (float)(2.0 * (double)bound);
+    }
+    return im;
+}
+
+// entries idx and idx + 1 of an fp16 C = 2 table -- the two corners of a dense level that differ in the first coordinate -- in one 8-byte
+// load (4-byte aligned: global_load_dwordx2); .x = entry idx, .y = entry idx + 1, each a half2
+__device__ __forceinline__ uint2 load_x_pair(const _Float16* __restrict__ table, uint32_t idx) {
+    uint2 q;
+    __builtin_memcpy(&q, table + (size_t)idx * 2, sizeof(uint2));
+    return q;
+}
 
 template <int D>
 __device__ __forceinline__ bool locate(const float* __restrict__ x, float scale, bool align_corners, uint32_t interp,

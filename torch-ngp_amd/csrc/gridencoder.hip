@@ -156,14 +156,25 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward(const float* __res
             for (int d = 0; d < D; d++) pg[d] = cell[d] + ((k >> d) & 1);
             corner[k].load(table + (size_t)indexer(pg) * C);
         }
+        // the summation order of the scheduled kernels (forward_pair_block, k_grid_forward_fast): the corners at the lower first coordinate
+        // in one chain, those at the upper one in another, then their sum -- a call that asks for dy_dx (points that require grad) returns
+        // the bits of the call that does not
+        float acch[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) acch[c] = 0.0f;
 #pragma unroll
         for (int k = 0; k < (1 << D); k++) {
             float w = 1.0f;
 #pragma unroll
             for (int d = 0; d < D; d++) w *= ((k >> d) & 1) ? frac[d] : (1.0f - frac[d]);
 #pragma unroll
-            for (int c = 0; c < C; c++) acc[c] = __builtin_fmaf(w, corner[k].v[c], acc[c]);
+            for (int c = 0; c < C; c++) {
+                if (k & 1) acch[c] = __builtin_fmaf(w, corner[k].v[c], acch[c]);
+                else acc[c] = __builtin_fmaf(w, corner[k].v[c], acc[c]);
+            }
         }
+#pragma unroll
+        for (int c = 0; c < C; c++) acc[c] += acch[c];
         store_vec<T, C>(out, acc);
 
         if (WITH_DYDX) {
@@ -415,7 +426,7 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward_fast(const float* 
             uint2 q[4];
             const uint32_t ofs[4] = {0u, s1, s2, s1 + s2};
 #pragma unroll
-            for (int j = 0; j < 4; j++) __builtin_memcpy(&q[j], table + (size_t)(i00 + ofs[j]) * 2, sizeof(uint2));  // entries x, x + 1 (4-byte aligned)
+            for (int j = 0; j < 4; j++) q[j] = load_x_pair(table, i00 + ofs[j]);  // entries x, x + 1 (grid_index.h)
             nxt.load(inputs, b + STEP, B - 1u);                     // in flight during this step's arithmetic and the next step's index work
             float accl[2] = {0.0f, 0.0f}, acch[2] = {0.0f, 0.0f};
             const float wl0 = 1.0f - frac[0], wh0 = frac[0];
@@ -2024,15 +2035,6 @@ extern "C" int ngp_grid_level_table(uint32_t L, float S, uint32_t H, float* scal
         resolution_out[l] = (uint32_t)ceilf(sc) + 1u;
     }
     return NGP_OK;
-}
-
-static InputMap make_input_map(float bound) {
-    InputMap im{0.0f, 0.0f};
-    if (bound > 0.0f) {
-        im.shift = bound;
-        im.scale = 1.0f / (float)(2.0 * (double)bound);
-    }
-    return im;
 }
 
 // The forward's per-XCD work lists as the launch would build them (host computation, no device work): 8 x 8 segments

@@ -329,9 +329,9 @@ def _render_train_network(marched, bufs, bg, offsets, cfg, rcfg, composite=True)
     return image, depth, weights_sum, saved._replace(weights_sum=weights_sum, image_raw=image_raw)
 
 
-def _render_train_backward(saved, cfg, rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc, found_inf=None, overwrite=False):
+def _render_train_backward(saved, cfg, rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc, found_inf=None, overwrite=False, input_grads=False):
     """the backward launches: grad_image [N,3] fp32 (and optionally grad_ws [N]) -> gradients accumulated into g_emb (scatter-add, must
-    hold the running sum / zeros) and written to g_ws / g_wc (fp16, flat)"""
+    hold the running sum / zeros) and written to g_ws / g_wc (fp16, flat).  input_grads: -> (g_enc, g_color_in) of `_network_backward`"""
     s = saved
     M, N = s.xyzs.shape[0], s.rays.shape[0]
     dev = s.xyzs.device
@@ -346,13 +346,20 @@ def _render_train_backward(saved, cfg, rcfg, grad_image, grad_ws, g_emb, g_ws, g
                                                               s.march_ws.data_ptr(), st))
     g_out16 = torch.empty(M, 16, device=dev, dtype=torch.half)
     capi.check(capi.lib.ngp_pipeline_rgb_backward(g_rgb.data_ptr(), s.rgb.data_ptr(), g_out16.data_ptr(), M, st))
-    _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf, None, overwrite)
+    return _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf, None, overwrite, input_grads=input_grads)
 
 
-def _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf=None, loss_job=None, overwrite=False, table_adam=None):
+def _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, found_inf=None, loss_job=None, overwrite=False, table_adam=None,
+                      input_grads=False):
     """colour MLP -> exp / feature shuffle -> sigma MLP -> grid scatter, from g_sigma [M] fp32 and g_out16 [M,16] fp16 (CONSUMED: reused as
     the sigma net's output gradient).  loss_job = (ray_err [N], loss [1]): the loss sum the compositor left to a later launch -- only
-    accepted where `_carries_reductions` holds (it rides with the slab reduction in the grid backward's last launch)"""
+    accepted where `_carries_reductions` holds (it rides with the slab reduction in the grid backward's last launch).
+    input_grads (the ray gradients): take the generic branch, which materialises the colour net's input gradient, and return
+    (g_enc [L,M,2], g_color_in [M,32]), the gradients with respect to the network's two inputs -- the same launches as that branch issues
+    without it.  It reads the stored activations: refused under NGP_FF_RECOMPUTE."""
+    if input_grads and saved.fb_c is None:
+        raise RuntimeError('fused: gradients with respect to the rays need the stored activations of the MLPs; this render was run with '
+                           'NGP_FUSED_RECOMPUTE=1 (NGP_FF_RECOMPUTE: no forward buffers) -- switch it off to refine poses')
     s = saved
     nl_sigma, nl_color, density_scale = cfg.nl_sigma, cfg.nl_color, rcfg.density_scale
     grid = (cfg.L, cfg.S, cfg.H, cfg.gridtype, cfg.align, cfg.interp, cfg.bound)
@@ -360,7 +367,8 @@ def _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, fou
     st = capi.stream()
     half = dict(device=s.xyzs.device, dtype=torch.half)
     g_enc = torch.empty(cfg.L, M, 2, **half)
-    if USE_FUSED_MID and nl_color in (2, 3) and nl_sigma in (2, 3):
+    g_color_in = None
+    if USE_FUSED_MID and nl_color in (2, 3) and nl_sigma in (2, 3) and not input_grads:
         # the colour head writes the sigma net's output gradient itself (exp backward + feature shuffle in its epilogue) and both
         # networks' weight-gradient slabs are summed by ONE launch at the end: 3 launches instead of 5
         scratch_c = torch.empty(nl_color, M, 64, **half)
@@ -401,6 +409,31 @@ def _network_backward(saved, cfg, rcfg, g_sigma, g_out16, g_emb, g_ws, g_wc, fou
                                                    0, 6, 1, scratch[:nl_sigma].data_ptr(), g_enc.data_ptr(), g_ws.data_ptr(),
                                                    _PLANAR_IN | _PLANAR_DX, st))
     _grid_backward(g_enc, s.xyzs, s.offsets, g_emb, M, *grid, st, found_inf, None, overwrite, table_adam)
+    return g_enc, g_color_in
+
+
+def _ray_gradients(saved, cfg, g_enc, g_color_in, emb16, rays_o, rays_d):
+    """ the per-sample gradients of the fused network's two inputs -> grad_rays_o, grad_rays_d [N,3] fp32: dL/dxyzs from
+    g_enc and the fp16 table without a dy_dx tensor (ngp_grid_input_gradient), the sample parameters recovered from the marcher's output
+    (ngp_ray_sample_ts), and the per-ray reduction with the SH term taken from columns 0..15 of g_color_in (ngp_ray_points_backward)"""
+    s = saved
+    M, N = s.xyzs.shape[0], s.rays.shape[0]
+    dev = s.xyzs.device
+    st = capi.stream()
+    sel = getattr(emb16, '_ngp_sel', None)
+    if sel is not None:
+        raise RuntimeError('fused: gradients with respect to the rays are not provided for a double-buffered table (optim.NGPAdam table fusion)')
+    g_xyzs = torch.empty(M, 3, device=dev)
+    capi.check(capi.lib.ngp_grid_input_gradient(g_enc.data_ptr(), s.xyzs.data_ptr(), emb16.data_ptr(), s.offsets.data_ptr(), M, 3, 2, cfg.L, cfg.S,
+                                                cfg.H, cfg.gridtype, cfg.align, cfg.interp, capi.NGP_F16, float(cfg.bound), g_xyzs.data_ptr(), st))
+    ts = torch.empty(M, device=dev)
+    capi.check(capi.lib.ngp_ray_sample_ts(s.xyzs.data_ptr(), rays_o.data_ptr(), rays_d.data_ptr(), s.rays.data_ptr(), M, N, float(cfg.bound),
+                                          ts.data_ptr(), st))
+    grad_o = torch.empty(N, 3, device=dev)
+    grad_d = torch.empty(N, 3, device=dev)
+    capi.check(capi.lib.ngp_ray_points_backward(g_xyzs.data_ptr(), None, g_color_in.data_ptr(), s.xyzs.data_ptr(), ts.data_ptr(), rays_d.data_ptr(),
+                                                s.rays.data_ptr(), M, N, float(cfg.bound), grad_o.data_ptr(), grad_d.data_ptr(), st))
+    return grad_o, grad_d
 
 
 class _fused_render_train(Function):
@@ -409,23 +442,35 @@ class _fused_render_train(Function):
         # (the forward launches of the fused training render on the current stream)
         marched = _render_train_march(rays_o, rays_d, bitfield, aabb, counter, cfg, rcfg)
         image, depth, weights_sum, saved = _render_train_network(marched, bufs, bg, offsets, cfg, rcfg)
-        ctx.save_for_backward(*saved)
+        #  rays that require grad: the backward also needs the rays themselves; the forward launches do not change
+        ctx.ray_grads = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        if ctx.ray_grads and saved.fb_c is None:
+            raise RuntimeError('fused: gradients with respect to the rays need the stored activations of the MLPs; NGP_FUSED_RECOMPUTE=1 '
+                               '(NGP_FF_RECOMPUTE: no forward buffers) does not keep them -- switch it off to refine poses')
+        ctx.save_for_backward(*saved, *((rays_o.contiguous(), rays_d.contiguous()) if ctx.ray_grads else ()))
         ctx.cfg, ctx.rcfg, ctx.n_emb, ctx.bufs = cfg, rcfg, embeddings.shape[0], bufs
         ctx.mark_non_differentiable(depth)
         return image, depth, weights_sum
 
     @staticmethod
     def backward(ctx, grad_image, grad_depth, grad_ws):
-        saved = Saved(*ctx.saved_tensors)
+        n_saved = len(Saved._fields)
+        saved = Saved(*ctx.saved_tensors[:n_saved])
         dev = saved.xyzs.device
         N = saved.rays.shape[0]
         grad_image = torch.zeros(N, 3, device=dev) if grad_image is None else grad_image.contiguous().float()
         grad_ws = None if grad_ws is None else grad_ws.contiguous().float()
         g_emb, g_ws, g_wc, deposited = _grad_targets(ctx.bufs, ctx.n_emb, dev)
-        _render_train_backward(saved, ctx.cfg, ctx.rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc)
+        grad_o = grad_d = None
+        if ctx.ray_grads:
+            rays_o, rays_d = ctx.saved_tensors[n_saved:]
+            g_enc, g_color_in = _render_train_backward(saved, ctx.cfg, ctx.rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc, input_grads=True)
+            grad_o, grad_d = _ray_gradients(saved, ctx.cfg, g_enc, g_color_in, ctx.bufs.emb16, rays_o, rays_d)
+        else:
+            _render_train_backward(saved, ctx.cfg, ctx.rcfg, grad_image, grad_ws, g_emb, g_ws, g_wc)
         if deposited:
-            return (None,) * 13
-        return None, None, g_emb, g_ws, g_wc, None, None, None, None, None, None, None, None
+            return (grad_o, grad_d) + (None,) * 11
+        return grad_o, grad_d, g_emb, g_ws, g_wc, None, None, None, None, None, None, None, None
 
 
 def network_cfg(encoder, sigma_net, color_net, bound, training):

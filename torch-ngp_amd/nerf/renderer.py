@@ -219,6 +219,14 @@ class NeRFRenderer(nn.Module):
             results['image'] = image.view(*lead, 3)
             return results
 
+        # extension: training rays that require grad.  near / far, the background lookup and the marcher (forward-only ops)
+        # see the rays as constants -- the sample parameters do not depend on the pose -- and the marcher's samples become a function of the
+        # rays, x = clamp(o + t d) with its t as constants: the same tensors (the forward does not change by a bit), with a backward that
+        # carries dL/dxyzs and dL/ddirs to the rays
+        ray_grads = self.training and torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        rays_o_in, rays_d_in = rays_o, rays_d
+        if ray_grads:
+            rays_o, rays_d = rays_o.detach(), rays_d.detach()
         nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, box, self.min_near)
         bg_color = self._background(rays_o, rays_d, bg_color)
         if self.training:
@@ -228,6 +236,9 @@ class NeRFRenderer(nn.Module):
             xyzs, dirs, deltas, rays = raymarching.march_rays_train(
                 rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars, counter,
                 self.mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps)
+            if ray_grads:
+                ts = raymarching.sample_ts(xyzs, rays_o, rays_d, rays, self.bound)
+                xyzs, dirs = raymarching.ray_points(rays_o_in, rays_d_in, ts, rays, self.bound, like=(xyzs, dirs))
             sigmas, rgbs = self(xyzs, dirs)
             sigmas = self.density_scale * sigmas
             if aux is not None:

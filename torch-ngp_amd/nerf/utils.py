@@ -70,3 +70,49 @@ def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, out=No
     results['rays_o'] = rays_o.view(B, n, 3)
     results['rays_d'] = rays_d.view(B, n, 3)
     return results
+
+
+class _pose_rays(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, poses, fx, fy, cx, cy, W, inds, n):
+        B = poses.shape[0]
+        dtype_in = poses.dtype
+        poses = poses.float().contiguous()
+        rays_o = torch.empty(B, n, 3, device=poses.device, dtype=torch.float32)
+        rays_d = torch.empty_like(rays_o)
+        inds_ptr, stride = (None, 0) if inds is None else (inds.data_ptr(), 0 if inds.dim() == 1 else n)
+        capi.check(capi.lib.ngp_rays_from_pixels(poses.data_ptr(), B, fx, fy, cx, cy, W, inds_ptr, stride, n, rays_o.data_ptr(), rays_d.data_ptr(),
+                                                 capi.stream()))
+        ctx.args = (B, fx, fy, cx, cy, W, inds, stride, n, dtype_in)
+        ctx.set_materialize_grads(False)
+        return rays_o, rays_d
+
+    @staticmethod
+    def backward(ctx, grad_o, grad_d):
+        if torch.is_grad_enabled() and any(g is not None and g.requires_grad for g in (grad_o, grad_d)):
+            raise RuntimeError('pose_rays: second-order gradients are not provided')
+        B, fx, fy, cx, cy, W, inds, stride, n, dtype_in = ctx.args
+        ref = grad_o if grad_o is not None else grad_d
+        dense = lambda g: torch.zeros(B, n, 3, device=ref.device, dtype=torch.float32) if g is None else g.float().contiguous()
+        grad_o, grad_d = dense(grad_o), dense(grad_d)
+        grad_poses = torch.empty(B, 4, 4, device=ref.device, dtype=torch.float32)
+        capi.check(capi.lib.ngp_rays_from_pixels_backward(grad_o.data_ptr(), grad_d.data_ptr(), B, fx, fy, cx, cy, W, capi.ptr(inds), stride, n,
+                                                          grad_poses.data_ptr(), capi.stream()))
+        return grad_poses.to(dtype_in), None, None, None, None, None, None, None
+
+
+def pose_rays(poses, intrinsics, H, W, inds=None):
+    """Extension (not in the reference): the rays of given pixels as a differentiable function of the camera poses.
+    poses [B,4,4] cam2world (CUDA), intrinsics (fx, fy, cx, cy), inds: int64 pixel indices [n] (shared by the poses) or [B,n], None = the full
+    H x W frame -> rays_o, rays_d [B,n,3] with the bits of get_rays for the same pixels (the same kernel); the backward is
+    ngp_rays_from_pixels_backward.  get_rays itself stays as it is (no_grad).  A pose parametrisation (e.g. poses = exp(xi) @ poses0) is
+    built in torch on top of this."""
+    if not poses.is_cuda:
+        raise RuntimeError('pose_rays: poses must be a CUDA tensor (the MI355X build has no CPU path)')
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    if inds is not None:
+        if inds.dtype != torch.int64 or inds.dim() not in (1, 2) or (inds.dim() == 2 and inds.shape[0] != poses.shape[0]):
+            raise RuntimeError('pose_rays: inds must be an int64 tensor of shape [n] or [B,n]')
+        inds = inds.to(poses.device).contiguous()
+    n = H * W if inds is None else inds.shape[-1]
+    return _pose_rays.apply(poses, fx, fy, cx, cy, int(W), inds, n)

@@ -301,6 +301,46 @@ def compact_rays_dev(state, alive_bound, n_total, n_step_cap, max_steps, rays_al
                                              capi.ptr(out_state), capi.ptr(workspace), capi.stream()))
 
 
+def ray_sample_ts(xyzs, rays_o, rays_d, rays, M, N, bound, ts):
+    """extension (include/ngp_hip.h, ngp_ray_sample_ts): the t of every sample the marcher wrote, recovered from xyzs.  ctypes-only, like the
+    geometry and feature compositors."""
+    floats = ((xyzs, 'xyzs'), (rays_o, 'rays_o'), (rays_d, 'rays_d'), (ts, 'ts'))
+    fn = capi.lib.ngp_ray_sample_ts_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_ray_sample_ts)
+    _i32(rays, 'rays')
+    capi.check(fn(capi.ptr(xyzs), capi.ptr(rays_o), capi.ptr(rays_d), capi.ptr(rays), M, N, float(bound), capi.ptr(ts), capi.stream()))
+
+
+def ray_points_forward(rays_o, rays_d, ts, rays, M, N, bound, xyzs, dirs):
+    """extension (ngp_ray_points_forward): xyzs = clamp(o + t d), dirs = d for the samples the rays own, zeros elsewhere"""
+    floats = ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (ts, 'ts'), (xyzs, 'xyzs'), (dirs, 'dirs'))
+    fn = capi.lib.ngp_ray_points_forward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_ray_points_forward)
+    _i32(rays, 'rays')
+    capi.check(fn(capi.ptr(rays_o), capi.ptr(rays_d), capi.ptr(ts), capi.ptr(rays), M, N, float(bound), capi.ptr(xyzs), capi.ptr(dirs), capi.stream()))
+
+
+def ray_points_backward(grad_xyzs, grad_dirs, grad_sh16, xyzs, ts, rays_d, rays, M, N, bound, grad_rays_o, grad_rays_d):
+    """extension (ngp_ray_points_backward): per-sample gradients -> per-ray gradients.  grad_dirs [M,3] and grad_sh16 [M,32] fp16 (fp32 calls
+    only) may be None."""
+    floats = ((grad_xyzs, 'grad_xyzs'), (grad_dirs, 'grad_dirs'), (xyzs, 'xyzs'), (ts, 'ts'), (rays_d, 'rays_d'), (grad_rays_o, 'grad_rays_o'),
+              (grad_rays_d, 'grad_rays_d'))
+    floats = tuple(p for p in floats if p[0] is not None)
+    _i32(rays, 'rays')
+    if _f64(floats):
+        if grad_sh16 is not None:
+            raise RuntimeError("ray_points_backward: grad_sh16 belongs to the float32 call (the fused path's fp16 colour-net input gradient)")
+        capi.check(capi.lib.ngp_ray_points_backward_f64(capi.ptr(grad_xyzs), capi.ptr(grad_dirs), capi.ptr(xyzs), capi.ptr(ts), capi.ptr(rays_d),
+                                                        capi.ptr(rays), M, N, float(bound), capi.ptr(grad_rays_o), capi.ptr(grad_rays_d), capi.stream()))
+        return
+    _f32_call(floats, None)
+    if grad_sh16 is not None:
+        capi.dense(grad_sh16, 'grad_sh16')
+        if grad_sh16.dtype != torch.float16 or grad_sh16.dim() != 2 or tuple(grad_sh16.shape) != (M, 32):
+            raise RuntimeError(f"grad_sh16 must be a float16 [M,32] tensor with M = {M} (got {grad_sh16.dtype}, {tuple(grad_sh16.shape)})")
+    capi.check(capi.lib.ngp_ray_points_backward(capi.ptr(grad_xyzs), capi.ptr(grad_dirs), capi.ptr(grad_sh16), capi.ptr(xyzs), capi.ptr(ts),
+                                                capi.ptr(rays_d), capi.ptr(rays), M, N, float(bound), capi.ptr(grad_rays_o), capi.ptr(grad_rays_d),
+                                                capi.stream()))
+
+
 def _accept_half(fn):
     """the reference dispatches its raymarching entry points on the tensor dtype (AT_DISPATCH_FLOATING_TYPES_AND_HALF, raymarching.cu:486);
     its own wrappers always hand over fp32 (custom_fwd(cast_inputs=float32)), so fp16 is unreachable from them.  For direct `_backend`

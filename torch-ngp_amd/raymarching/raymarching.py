@@ -22,7 +22,7 @@ except ImportError:
 from . import backend as _geo  # the geometry compositor's entries are ctypes-only: the compiled module's table is the reference's
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'packbits_capped', 'march_rays_train',
-           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'march_rays', 'composite_rays', 'composite_rays_features', 'compact_rays', 'update_density_grid', 'density_grid_state']
+           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'sample_ts', 'ray_points', 'march_rays', 'composite_rays', 'composite_rays_features', 'compact_rays', 'update_density_grid', 'density_grid_state']
 
 _f32_fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 
@@ -311,6 +311,72 @@ class _composite_rays_train_features(Function):
 
 
 composite_rays_train_features = _composite_rays_train_features.apply
+
+
+def _ray_dtype(*tensors):
+    """float64 when one of the floating tensors is, else float32 (the rule of the compositors' float64 twins)"""
+    return torch.float64 if any(t is not None and t.dtype == torch.float64 for t in tensors) else torch.float32
+
+
+def sample_ts(xyzs, rays_o, rays_d, rays, bound):
+    """Extension (not in the reference): ts [M], the t of every sample of march_rays_train's xyzs [M,3] along its ray,
+    recovered from the marcher's output (which keeps t to itself): t = sum_j m_j d_j (x_j - o_j) / sum_j m_j d_j^2 over the coordinates that
+    were not clamped to +-bound.  Rows no ray owns are 0.  No autograd: the sample parameters are constants of the pose."""
+    dtype = _ray_dtype(xyzs, rays_o, rays_d)
+    xyzs = xyzs.detach().to(dtype).contiguous()
+    rays_o, rays_d = _rays(rays_o.detach().to(dtype)), _rays(rays_d.detach().to(dtype))
+    ts = torch.empty(xyzs.shape[0], dtype=dtype, device=xyzs.device)
+    _geo.ray_sample_ts(xyzs, rays_o, rays_d, rays.contiguous(), xyzs.shape[0], rays.shape[0], bound, ts)
+    return ts
+
+
+class _ray_points(Function):
+    """Extension (not in the reference): the samples of the training rays as a differentiable function of the rays,
+    x_i = clamp(o_n + t_i d_n, -bound, bound) and dirs_i = d_n with the marcher's t_i as constants.  A clamped coordinate passes no gradient.
+    First order only."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, ts, rays, bound, like_xyzs, like_dirs):
+        dtype = _ray_dtype(rays_o, rays_d, ts, like_xyzs)
+        ctx.shapes = (rays_o.shape, rays_d.shape, rays_o.dtype, rays_d.dtype)
+        rays_o, rays_d = _rays(rays_o.to(dtype)), _rays(rays_d.to(dtype))
+        ts, rays = ts.to(dtype).contiguous(), rays.contiguous()
+        n_samples, n_rays = ts.shape[0], rays.shape[0]
+        if like_xyzs is not None:   # the marcher's own tensors: a render's forward does not change by a bit
+            xyzs, dirs = like_xyzs, like_dirs
+            if xyzs.dtype != dtype or tuple(xyzs.shape) != (n_samples, 3) or tuple(dirs.shape) != (n_samples, 3):
+                raise RuntimeError(f"ray_points: like=(xyzs, dirs) must be two [{n_samples}, 3] {dtype} tensors (got {tuple(xyzs.shape)} "
+                                   f"{xyzs.dtype}, {tuple(dirs.shape)} {dirs.dtype})")
+        else:
+            xyzs = torch.empty(n_samples, 3, dtype=dtype, device=ts.device)
+            dirs = torch.empty_like(xyzs)
+            _geo.ray_points_forward(rays_o, rays_d, ts, rays, n_samples, n_rays, bound, xyzs, dirs)
+        ctx.save_for_backward(xyzs.detach().contiguous(), ts, rays_d, rays)
+        ctx.bound = bound
+        ctx.set_materialize_grads(False)
+        return xyzs, dirs
+
+    @staticmethod
+    def backward(ctx, grad_xyzs, grad_dirs):
+        if torch.is_grad_enabled() and any(g is not None and g.requires_grad for g in (grad_xyzs, grad_dirs)):
+            raise RuntimeError("ray_points: second-order gradients are not provided (raymarching stays first-order)")
+        xyzs, ts, rays_d, rays = ctx.saved_tensors
+        shape_o, shape_d, dtype_o, dtype_d = ctx.shapes
+        n_samples, n_rays = ts.shape[0], rays.shape[0]
+        dense = lambda g: None if g is None else g.to(ts.dtype).contiguous()
+        grad_xyzs = torch.zeros_like(xyzs) if grad_xyzs is None else dense(grad_xyzs)
+        grad_rays_o = torch.empty(n_rays, 3, dtype=ts.dtype, device=ts.device)
+        grad_rays_d = torch.empty_like(grad_rays_o)
+        _geo.ray_points_backward(grad_xyzs, dense(grad_dirs), None, xyzs, ts, rays_d, rays, n_samples, n_rays, ctx.bound, grad_rays_o, grad_rays_d)
+        return grad_rays_o.view(shape_o).to(dtype_o), grad_rays_d.view(shape_d).to(dtype_d), None, None, None, None, None
+
+
+def ray_points(rays_o, rays_d, ts, rays, bound, like=None):
+    """rays_o / rays_d [N,3], ts [M] (sample_ts), rays [N,3] int32 (march_rays_train) -> xyzs [M,3], dirs [M,3], differentiable in rays_o
+    and rays_d (float32 or float64).  like=(xyzs, dirs): return the marcher's own tensors (unchanged bits) with this op's backward -- the
+    form the renderer uses; without it both are computed (ngp_ray_points_forward: clamp(fma(t, d, o)), rows no ray owns are zero)."""
+    like_xyzs, like_dirs = (None, None) if like is None else like
+    return _ray_points.apply(rays_o, rays_d, ts, rays, bound, like_xyzs, like_dirs)
 
 
 # ----------------------------------------------------------------------------------------------
