@@ -36,6 +36,8 @@ TABLES = dict(
     TILED=dict(cfg=dict(input_dim=3, num_levels=3, per_level_scale=2.0, base_resolution=4, log2_hashmap_size=9), C=2, level=1, gridtype=1),
     ALIGN=dict(cfg=dict(input_dim=3, num_levels=3, per_level_scale=2.0, base_resolution=4, log2_hashmap_size=9), C=1, level=2, align=True),
     SMOOTH=dict(cfg=dict(input_dim=3, num_levels=3, per_level_scale=2.0, base_resolution=4, log2_hashmap_size=9), C=2, level=1, interp=1),
+    # a hashed level of 2^17 entries: three 8-bit digits in the record sort (A3d's level 0 has one, the 2^9 / 2^10 tables two)
+    A3h=dict(cfg=dict(input_dim=3, num_levels=3, per_level_scale=2.0, base_resolution=32, log2_hashmap_size=17), C=2, level=2),
 )
 B_LATTICE = 1000
 B_ONE_CELL = 4133     # runs of 4133 records: more than 64 tiles, so at least two further arrays of partial sums

@@ -4,6 +4,7 @@ fp64 unit's built objects (no scratch, no last-register 64-bit shift)."""
 import ctypes
 import os
 import re
+import subprocess
 import sys
 
 import pytest
@@ -130,3 +131,20 @@ def test_fp64_unit_has_no_scratch_and_no_last_register_shift(build, tmp_path):
     # the deterministic backward uses no float atomics; TV (not on an autograd path) adds with fp64 atomics
     atomics = {k for k, ins in kernels.items() if any(re.match(r'global_atomic_\w*f(32|64)', i) for i in ins)}
     assert atomics and all('k_f64_grad_tv' in k for k in atomics)
+    # the second-order run sums (k_f64_grid_run_sum<D, C, 2>, 16 (D, C) shapes): no spills at all, not even into AGPRs or VGPR lanes, no
+    # compare-and-swap and no float atomics
+    second = [k for k in meta if re.search(r'k_f64_grid_run_sumILi\dELi\dELi2EE', k)]
+    assert len(second) == 16 and sum(1 for k in meta if 'k_f64_grid_run_sum' in k) == 32
+    notes = subprocess.check_output([isa.TOOLS[2], '--notes', co], text=True)
+    seen, spilled = set(), set()
+    for block in notes.split('.agpr_count:')[1:]:
+        symbol = re.search(r'\.symbol:\s+(\S+)\.kd', block).group(1)
+        counts = re.findall(r'\.(?:s|v)gpr_spill_count:\s+(\d+)', block)
+        assert len(counts) == 2, symbol
+        seen.add(symbol)
+        if any(int(n) for n in counts):
+            spilled.add(symbol)
+    assert set(second) <= seen and not spilled & set(second)
+    for k in second:
+        assert not any('cmpswap' in i for i in kernels[k]), k
+        assert {i.split()[0] for i in kernels[k] if i.startswith('global_atomic')} == set(), k

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_ordered_cases as goc
 import oracle
 from grid_forward_cases import grid_reference as _grid_reference   # the float64 model of the forward: the fp16 / fp32 kernels are pinned to it too
 
@@ -130,6 +131,61 @@ def test_grid_backward_is_bit_reproducible():
     assert all(torch.equal(runs[0], r) for r in runs[1:])
     # sanity: the total equals the fp64 sum of every contribution (weights of a point sum to 1)
     assert abs(runs[0].sum().item() - grad.sum().item()) < 1e-6 * grad.abs().sum().item()
+
+
+def _fp64_run_sums(keys, contrib, init):
+    """the fp64 table gradient of one level from its records (slot order): per entry the contributions in ascending slot order, added left to
+    right in float64 from 0.0, the sum added once to the entry's initial value"""
+    k, v = goc.sorted_records(np.asarray(keys, np.int64), np.asarray(contrib, np.float64))
+    want = init.copy()
+    n = int((k != goc.NONE).sum())
+    starts = np.flatnonzero(np.r_[True, k[1:n] != k[:n - 1]]) if n else np.zeros(0, np.int64)
+    zero = np.zeros((1, v.shape[1]))
+    for a, b in zip(starts, np.r_[starts[1:], n]):
+        want[k[a]] = init[k[a]] + np.cumsum(np.vstack([zero, v[a:b]]), axis=0)[-1]
+    return want
+
+
+@pytest.mark.parametrize('one_cell', [False, True], ids=['B1000', 'one_cell_4133'])
+@pytest.mark.parametrize('order', [1, 2])
+@pytest.mark.parametrize('name', goc.LATTICE_NAMES)
+def test_grid_table_gradient_has_the_bits_of_the_slot_order_model(name, order, one_cell):
+    """The fp64 table gradient, first and second order, bit for bit against a model of its order, on the lattice cases of the ordered scatter
+    (tests/grid_ordered_cases.py): every contribution w_k g / a_k g of the lattice level is exactly representable, so fma(coeff, g, acc) is
+    acc + contribution.  About 3 % of the points lie outside [0,1]^D.  The lattice levels have 64 to 2^17 entries: one, two and three 8-bit
+    digits of the record sort."""
+    from gridencoder import backend, grid
+    case = goc.lattice_case(name, order, False, one_cell)
+    tab, level, size = case['tab'], case['level'], case['size']
+    L, B, C = case['g'].shape
+    D = tab['D']
+    rng = np.random.default_rng(4300 + order + 2 * int(one_cell))
+    x = np.array(case['x'])
+    out = rng.choice(B, B // 32, replace=False)
+    x[out, rng.integers(0, D, len(out))] = np.where(rng.random(len(out)) < 0.5, np.float32(-2.0 ** -20), np.nextafter(np.float32(1), np.float32(2)))
+    keys = goc.record_keys(tab, x, level)
+    contrib = goc.contributions(tab, x, case['g'], level, order, case['u'])
+    outside = (keys.reshape(B, -1) == goc.NONE).all(axis=1)
+    assert goc.fits_fp32(contrib) and outside[out].all() and 0.03 * B <= outside.sum() <= len(out) + 1   # (+ the lattice inputs' own one)
+    assert (keys.reshape(B, -1)[~outside] != goc.NONE).all()
+    assert {1: size < 256, 2: 256 <= size < 65536, 3: 65536 <= size}[{'A3d': 1, 'A3h': 3}.get(name, 2)]
+
+    n = int(tab['offs'][-1])
+    init = rng.standard_normal((n, C))
+    xt, ot = torch.from_numpy(x).cuda(), torch.from_numpy(np.array(tab['offs'])).cuda()
+    gt = torch.from_numpy(case['g'].astype(np.float64)).cuda()
+    ge = torch.from_numpy(init).cuda()
+    E = torch.from_numpy(rng.standard_normal((n, C))).cuda()
+    if order == 1:
+        backend.grid_encode_backward(gt, xt, E, ot, ge, B, D, C, L, tab['S'], tab['H'], None, None, tab['gridtype'], tab['align'], tab['interp'])
+    else:
+        ut = torch.from_numpy(case['u'].astype(np.float64)).cuda()
+        grid.grid_encode_backward_backward(gt, xt, E, ot, ut, None, ge, None, B, D, C, L, tab['S'], tab['H'], tab['gridtype'], tab['align'],
+                                           tab['interp'])
+    lo, hi = int(tab['offs'][level]), int(tab['offs'][level + 1])
+    want = _fp64_run_sums(keys, contrib, init[lo:hi])
+    assert torch.equal(ge[lo:hi].cpu(), torch.from_numpy(want))
+    assert np.count_nonzero(want != init[lo:hi]) > 0
 
 
 def _reference_recipe():

@@ -1,7 +1,7 @@
 """CPU checks of the ordered scatter's entry points (include/ngp_hip.h: ngp_grid_encode_backward_ordered,
 ngp_grid_encode_backward_backward_ordered, ngp_grid_ordered_workspace_bytes, ngp_grid_backward_is_reproducible): declared, exported and
 bound; the ABI version unchanged; host-side validation (codes and messages, before any launch: no GPU needed); the workspace formula; the
-reproducibility query and scatter_path; the new unit's built objects (no scratch, no spills, no last-register 64-bit shift, no float
+reproducibility query and scatter_path; the built objects of the unit and of the record sort's (no scratch, no spills, no last-register 64-bit shift, no float
 atomics and no compare-and-swap in any kernel)."""
 import ctypes
 import os
@@ -211,28 +211,33 @@ def test_module_keyword():
     assert enc.deterministic is None and grid.GridEncoder(num_levels=2, log2_hashmap_size=8, deterministic=True).deterministic is True
 
 
-def _objects():
+def _objects(unit):
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import check_isa_hazards as isa
-    objs = [os.path.join(ROOT, 'torch-ngp_amd', 'csrc', d, 'grid_ordered.o') for d in ('_obj', '_obj_dbg')]
+    objs = [os.path.join(ROOT, 'torch-ngp_amd', 'csrc', d, unit + '.o') for d in ('_obj', '_obj_dbg')]
     if not isa.tools_present() or not all(os.path.exists(o) for o in objs):
-        pytest.skip('grid_ordered.o (run __graft_entry__.build()) or the LLVM tools are missing')
+        pytest.skip(unit + '.o (run __graft_entry__.build()) or the LLVM tools are missing')
     return isa, objs
 
 
-@pytest.mark.parametrize('build', [0, 1], ids=['product', 'debug_bounds'])
-def test_unit_has_no_scratch_no_hazard_and_no_float_atomics(build, tmp_path):
-    isa, objs = _objects()
+# 64 sums of the records (2 dtypes x 16 (D, C) x 2 orders), 8 sums of partial sums (2 dtypes x 4 C), 32 gather-only instantiations of the
+# second order's kernel, 2 input-gradient kernels; the record sort's unit (csrc/grid_records.hip): 4 record kernels (D), 3 radix kernels
+UNITS = {'grid_ordered': (106, ('k_ord_sum_records', 'k_ord_sum_partials', 'k_grid_bwd_bwd', 'k_grid_input_backward'), [64, 8, 32, 2]),
+         'grid_records': (7, ('k_rec_records', 'k_rec_radix'), [4, 3])}
+
+
+@pytest.mark.parametrize('build,unit', [(0, 'grid_ordered'), (1, 'grid_ordered'), (0, 'grid_records'), (1, 'grid_records')],
+                         ids=['product', 'debug_bounds', 'records-product', 'records-debug_bounds'])
+def test_unit_has_no_scratch_no_hazard_and_no_float_atomics(build, unit, tmp_path):
+    isa, objs = _objects(unit)
+    n_kernels, names, counts = UNITS[unit]
     checked, hits = isa.scan_object(objs[build])
-    assert checked == 113 and hits == []
+    assert checked == n_kernels and hits == []
     co = isa.code_object(objs[build], str(tmp_path))
     meta, kernels = isa.kernel_metadata(co), isa.disassembly(co)
-    # 64 sums of the records (2 dtypes x 16 (D, C) x 2 orders), 8 sums of partial sums (2 dtypes x 4 C), 4 record kernels (D), 3 radix
-    # kernels, 32 gather-only instantiations of the second order's kernel, 2 input-gradient kernels
     count = lambda s: sum(1 for k in meta if s in k)
-    assert len(meta) == 113
-    assert [count(s) for s in ('k_ord_sum_records', 'k_ord_sum_partials', 'k_ord_records', 'k_ord_radix', 'k_grid_bwd_bwd',
-                               'k_grid_input_backward')] == [64, 8, 4, 3, 32, 2]
+    assert len(meta) == n_kernels
+    assert [count(s) for s in names] == counts and sum(counts) == n_kernels
     assert [k for k, m in meta.items() if m['private_segment_fixed_size']] == []
     notes = subprocess.check_output([isa.TOOLS[2], '--notes', co], text=True)
     spills = re.findall(r'\.(?:s|v)gpr_spill_count:\s+(\d+)', notes)
@@ -247,10 +252,11 @@ def test_unit_has_no_scratch_no_hazard_and_no_float_atomics(build, tmp_path):
 
 
 def test_sibling_units_keep_their_kernels():
-    """the shared code moved into headers (grid_index.h, grid_second.h): the units that used it hold the kernels they held"""
+    """the shared code moved into headers (grid_index.h, grid_second.h): the second-order unit holds its own kernel alone (the fp64 run
+    sums are fp64.hip's)"""
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import check_isa_hazards as isa
     obj = os.path.join(ROOT, 'torch-ngp_amd', 'csrc', '_obj', 'grid_second.o')
     if not isa.tools_present() or not os.path.exists(obj):
         pytest.skip('grid_second.o (run __graft_entry__.build()) or the LLVM tools are missing')
-    assert isa.scan_object(obj)[0] == 60
+    assert isa.scan_object(obj)[0] == 44

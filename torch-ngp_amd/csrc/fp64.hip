@@ -7,14 +7,16 @@
 //   * grid forward: positions, fractions and interpolation weights come from the fp32 inputs through the fp32 path's own code
 //     (grid_index.h: locate, the fp32 weight product); every product with a table entry and every sum is fp64, nothing is rounded
 //     through fp32 after the weights;
-//   * grid backward: bit-reproducible.  Per level, every (point, corner) contribution becomes a record (table entry, point << D | corner)
-//     written at a fixed slot, a stable LSD radix sort on the entry (four 8-bit passes) groups the records of an entry in slot order, and
-//     one lane per entry sums its run in that order in fp64 and adds the sum once.  No float atomics, so two calls give the same bits;
+//   * grid backward, first and second order: bit-reproducible.  Per level, the record sort of grid_records.h groups the (point, corner)
+//     records of an entry in slot order, and one lane per entry sums its run in that order in fp64 (grid_second.h: record_coeff, w_k or
+//     a_k) and adds the sum once.  No float atomics, so two calls give the same bits;
 //   * TV: fp64 throughout, fp64 atomics (not on an autograd path);
 //   * SH: fp64 arithmetic and constants (sh_poly64.inc, tools/gen_sh.py);
 //   * compositing / near-far / sph / packbits: the reference's per-ray loops in fp64 (exp in double, T < T_thresh compared in double).
 #include "common.h"
 #include "grid_index.h"
+#include "grid_records.h"
+#include "grid_second.h"
 #include "fp64.h"
 #include "sh_poly64.inc"
 #include <float.h>
@@ -107,156 +109,38 @@ __global__ __launch_bounds__(F64_THREADS) void k_f64_grid_fwd(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------
-// grid encoder: deterministic backward, one level at a time
-//   records -> 4 x (histogram, scan, stable scatter) on the entry -> per-entry ordered sum
+// grid encoder: deterministic table gradients, one level at a time: the record sort of grid_records.h, then this run sum.
+// One lane per run of equal entries (the run's first record): the contributions in slot order, fma into fp64 from 0, added to the entry
+// once.  ORDER 1: w_k g, the backward; ORDER 2: a_k g with u = uin[b], the backward's backward (grid_second.hip)
 // ------------------------------------------------------------------------------------------------
-constexpr uint32_t F64_NO_ENTRY = 0xffffffffu;  // record of a point outside [0,1]^D (sorts last, contributes nothing)
-constexpr uint32_t RADIX_TILE = 256;             // items per scatter step = threads of the histogram / scatter workgroups
-constexpr uint32_t RADIX_MAX_GROUPS = 1024;      // workgroups per pass (each owns a contiguous range of tiles)
-constexpr uint32_t RADIX_COUNT_WORDS = 256 * RADIX_MAX_GROUPS + 256;   // per-(digit, group) counts, then the 256 digit totals
-
-// slot (b << D | k) of every contribution of level `level`: key = the entry inside the level, value = the slot itself
-template <int D>
-__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_records(const float* __restrict__ inputs, const int32_t* __restrict__ offsets, uint32_t B,
-                                                                   uint32_t level, float scale, uint32_t resolution, uint32_t gridtype,
-                                                                   bool align_corners, uint32_t interp, uint32_t* __restrict__ keys,
-                                                                   uint32_t* __restrict__ vals) {
-    const uint32_t off0 = (uint32_t)offsets[level];
-    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-    LevelIndexer<D> indexer;
-    indexer.init(gridtype, align_corners, hashmap_size, resolution);
-    for (uint32_t b = blockIdx.x * F64_THREADS + threadIdx.x; b < B; b += gridDim.x * F64_THREADS) {
-        float frac[D], deriv[D];
-        uint32_t cell[D];
-        const bool inside = locate<D>(inputs + (size_t)b * D, scale, align_corners, interp, frac, deriv, cell);
-#pragma unroll
-        for (int k = 0; k < (1 << D); k++) {
-            uint32_t pg[D];
-#pragma unroll
-            for (int d = 0; d < D; d++) pg[d] = cell[d] + ((k >> d) & 1);
-            const uint32_t slot = (b << D) | (uint32_t)k;
-            keys[slot] = inside ? indexer(pg) : F64_NO_ENTRY;
-            vals[slot] = slot;
-        }
-    }
-}
-
-// digit counts of one workgroup's range: hist[digit * groups + group]
-__global__ __launch_bounds__(RADIX_TILE) void k_f64_radix_hist(const uint32_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t tiles_per_group,
-                                                                uint32_t groups, uint32_t* __restrict__ hist) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t begin = blockIdx.x * tiles_per_group * RADIX_TILE;
-    const uint32_t end = min(n, begin + tiles_per_group * RADIX_TILE);
-    for (uint32_t i = begin + threadIdx.x; i < end; i += RADIX_TILE) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);
-    __syncthreads();
-    hist[threadIdx.x * groups + blockIdx.x] = h[threadIdx.x];
-}
-
-// one workgroup per digit: exclusive scan of the digit's group counts in place, the digit's total to totals[digit]
-__global__ __launch_bounds__(RADIX_MAX_GROUPS) void k_f64_radix_scan(uint32_t* __restrict__ hist, uint32_t groups, uint32_t* __restrict__ totals) {
-    __shared__ uint32_t part[RADIX_MAX_GROUPS];
-    const uint32_t t = threadIdx.x, digit = blockIdx.x;
-    const uint32_t v = t < groups ? hist[digit * groups + t] : 0u;
-    part[t] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < RADIX_MAX_GROUPS; o <<= 1) {
-        const uint32_t a = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += a;
-        __syncthreads();
-    }
-    if (t < groups) hist[digit * groups + t] = part[t] - v;
-    if (t == RADIX_MAX_GROUPS - 1) totals[digit] = part[t];
-}
-
-// stable scatter: a workgroup walks its range tile by tile in order; inside a tile an item's rank among the earlier items with its digit
-// comes from the lanes of its wave (8 ballots -> the lanes with the same digit, mbcnt) and the counts of the earlier waves.  A digit's first
-// slot for this workgroup: the totals of the smaller digits (scanned here, by every workgroup) + its scanned group count
-__global__ __launch_bounds__(RADIX_TILE) void k_f64_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in, uint32_t n,
-                                                                   uint32_t shift, uint32_t tiles_per_group, uint32_t groups,
-                                                                   const uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals,
-                                                                   uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
-    constexpr uint32_t WAVES = RADIX_TILE / 64;
-    __shared__ uint32_t run[256];
-    __shared__ uint32_t wave_count[WAVES][256];
-    const uint32_t t = threadIdx.x, wave = t >> 6;
-    run[t] = totals[t];
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const uint32_t a = t >= o ? run[t - o] : 0u;
-        __syncthreads();
-        run[t] += a;
-        __syncthreads();
-    }
-    run[t] += hist[t * groups + blockIdx.x] - totals[t];
-    const uint32_t begin = blockIdx.x * tiles_per_group * RADIX_TILE;
-    const uint32_t end = min(n, begin + tiles_per_group * RADIX_TILE);
-    for (uint32_t base = begin; base < end; base += RADIX_TILE) {
-        const uint32_t i = base + t;
-        const bool valid = i < end;
-        uint32_t key = 0u, val = 0u, digit = 0u;
-        if (valid) {
-            key = keys_in[i];
-            val = vals_in[i];
-            digit = (key >> shift) & 255u;
-        }
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; bit++) {
-            const bool set = (digit >> bit) & 1u;
-            const uint64_t m = __ballot(valid && set);
-            same &= set ? m : ~m;
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(same >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)same, 0u));
-#pragma unroll
-        for (uint32_t w = 0; w < WAVES; w++) wave_count[w][t] = 0u;
-        __syncthreads();
-        if (valid && rank == 0u) wave_count[wave][digit] = (uint32_t)__popcll(same);
-        __syncthreads();
-        if (valid) {
-            uint32_t pos = run[digit] + rank;
-            for (uint32_t w = 0; w < wave; w++) pos += wave_count[w][digit];
-            NGP_BOUNDS(pos < n);
-            keys_out[pos] = key;
-            vals_out[pos] = val;
-        }
-        __syncthreads();
-        uint32_t add = 0u;
-#pragma unroll
-        for (uint32_t w = 0; w < WAVES; w++) add += wave_count[w][t];
-        run[t] += add;
-        __syncthreads();
-    }
-}
-
-// one lane per run of equal entries (the run's first record): the contributions in slot order, summed in fp64, added once
-template <int D, int C>
-__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_sum(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
-                                                               const double* __restrict__ grad, const float* __restrict__ inputs,
-                                                               const int32_t* __restrict__ offsets, double* __restrict__ grad_grid, uint32_t B,
-                                                               uint32_t level, float scale, bool align_corners, uint32_t interp) {
+template <int D, int C, int ORDER>
+__global__ __launch_bounds__(F64_THREADS) void k_f64_grid_run_sum(const uint32_t* __restrict__ keys0, const uint32_t* __restrict__ vals0,
+                                                                   const uint32_t* __restrict__ keys1, const uint32_t* __restrict__ vals1, uint32_t n,
+                                                                   const double* __restrict__ grad, const float* __restrict__ inputs,
+                                                                   const double* __restrict__ uin, const int32_t* __restrict__ offsets,
+                                                                   double* __restrict__ grad_grid, uint32_t B, uint32_t level, float scale,
+                                                                   bool align_corners, uint32_t interp) {
+    const uint32_t level_size = level_size_of(offsets, level);
+    const bool odd = rec_sorted_side(level_size) != 0u;
+    const uint32_t* __restrict__ keys = odd ? keys1 : keys0;
+    const uint32_t* __restrict__ vals = odd ? vals1 : vals0;
+    double* __restrict__ table = grad_grid + (size_t)(uint32_t)offsets[level] * C;
     for (uint32_t i = blockIdx.x * F64_THREADS + threadIdx.x; i < n; i += gridDim.x * F64_THREADS) {
         const uint32_t e = keys[i];
-        if (e == F64_NO_ENTRY || (i > 0u && keys[i - 1u] == e)) continue;
+        if (e >= level_size || (i > 0u && keys[i - 1u] == e)) continue;   // (level_size: a record of a point outside [0,1]^D)
         double acc[C];
 #pragma unroll
         for (int c = 0; c < C; c++) acc[c] = 0.0;
         for (uint32_t j = i; j < n && keys[j] == e; j++) {
             const uint32_t slot = vals[j], b = slot >> D, k = slot & ((1u << D) - 1u);
             NGP_BOUNDS(b < B);
-            float frac[D], deriv[D];
-            uint32_t cell[D];
-            locate<D>(inputs + (size_t)b * D, scale, align_corners, interp, frac, deriv, cell);
-            const double w = (double)corner_weight<D>(frac, k);
+            const double w = record_coeff<D, ORDER>(inputs + (size_t)b * D, ORDER == 2 ? uin + (size_t)b * D : nullptr, k, scale, align_corners, interp,
+                                                    InputMap{0.0f, 0.0f});
             const double* g = grad + ((size_t)level * B + b) * C;
 #pragma unroll
             for (int c = 0; c < C; c++) acc[c] = __builtin_fma(w, g[c], acc[c]);
         }
-        const uint32_t off0 = (uint32_t)offsets[level];
-        NGP_BOUNDS(e < (uint32_t)offsets[level + 1] - off0);
-        double* dst = grad_grid + ((size_t)off0 + e) * C;
+        double* dst = table + (size_t)e * C;
 #pragma unroll
         for (int c = 0; c < C; c++) dst[c] += acc[c];
     }
@@ -670,87 +554,53 @@ int f64_grid_forward(const float* inputs, const void* embeddings, const int32_t*
     return NGP_ERR_INVALID;
 }
 
-// workspace: keys / values twice (ping-pong) for the B << D records of one level, then the digit counts and totals
-static size_t f64_array_bytes(uint64_t n) { return (n * sizeof(uint32_t) + 255) & ~(size_t)255; }
-
+// workspace: the record sort's alone (grid_records.h: rec_layout)
 size_t f64_grid_backward_workspace_bytes(uint32_t B, uint32_t D) {
     if (B == 0 || D < 2 || D > 5) return 0;
-    return 4 * f64_array_bytes((uint64_t)B << D) + RADIX_COUNT_WORDS * sizeof(uint32_t);
+    return rec_layout(B, D).bytes;
 }
 
-// the records of one level sorted by entry (k_f64_grid_records, then four stable radix passes) -> keys[0] / vals[0] of the workspace: the
-// first-order backward below and the second-order one (grid_second.hip: f64_grid_sort_level) sum the same runs in the same order
-template <int D>
-static void f64_sort_level(const float* inputs, const int32_t* offsets, uint32_t B, uint32_t level, float scale, uint32_t resolution,
-                           uint32_t gridtype, bool ac, uint32_t interp, void* workspace, const uint32_t** keys_out, const uint32_t** vals_out,
-                           hipStream_t st) {
-    const uint32_t n = B << D;
-    char* ws = (char*)workspace;
-    const size_t a = f64_array_bytes(n);
-    uint32_t* keys[2] = {(uint32_t*)ws, (uint32_t*)(ws + 2 * a)};
-    uint32_t* vals[2] = {(uint32_t*)(ws + a), (uint32_t*)(ws + 3 * a)};
-    uint32_t* hist = (uint32_t*)(ws + 4 * a);
-    uint32_t* totals = hist + 256 * RADIX_MAX_GROUPS;
-    const uint32_t tiles = cdiv(n, RADIX_TILE);
-    const uint32_t tiles_per_group = cdiv(tiles, RADIX_MAX_GROUPS);
-    const uint32_t groups = cdiv(tiles, tiles_per_group);
-    NGP_LAUNCH((k_f64_grid_records<D>), dim3(grid_blocks(B, F64_THREADS)), dim3(F64_THREADS), 0, st, inputs, offsets, B, level, scale, resolution,
-                       gridtype, ac, interp, keys[0], vals[0]);
-    for (uint32_t pass = 0; pass < 4; pass++) {
-        const uint32_t src = pass & 1u, shift = 8u * pass;
-        NGP_LAUNCH(k_f64_radix_hist, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], n, shift, tiles_per_group, groups, hist);
-        NGP_LAUNCH(k_f64_radix_scan, dim3(256), dim3(RADIX_MAX_GROUPS), 0, st, hist, groups, totals);
-        NGP_LAUNCH(k_f64_radix_scatter, dim3(groups), dim3(RADIX_TILE), 0, st, keys[src], vals[src], n, shift, tiles_per_group, groups, hist,
-                           totals, keys[src ^ 1u], vals[src ^ 1u]);
-    }
-    // (an even number of passes: the sorted records are back in keys[0] / vals[0])
-    *keys_out = keys[0];
-    *vals_out = vals[0];
+int f64_grid_check_workspace(const char* fn, const char* query, uint32_t B, uint32_t D, const void* workspace, size_t workspace_bytes) {
+    return rec_check_workspace(fn, "fp64", query, B, D, f64_grid_backward_workspace_bytes(B, D), workspace, workspace_bytes);
 }
 
-void f64_grid_sort_level(uint32_t D, const float* inputs, const int32_t* offsets, uint32_t B, uint32_t level, float scale, uint32_t resolution,
-                         uint32_t gridtype, bool align_corners, uint32_t interp, void* workspace, const uint32_t** keys, const uint32_t** vals,
-                         hipStream_t st) {
-    switch (D) {
-        case 2: f64_sort_level<2>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
-        case 3: f64_sort_level<3>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
-        case 4: f64_sort_level<4>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
-        default: f64_sort_level<5>(inputs, offsets, B, level, scale, resolution, gridtype, align_corners, interp, workspace, keys, vals, st); break;
-    }
-}
-
-template <int D, int C>
-static int launch_f64_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_emb, uint32_t B, uint32_t L,
-                               const GridLevels& lv, uint32_t gridtype, bool ac, uint32_t interp, void* workspace, hipStream_t st) {
-    const uint32_t n = B << D;
+template <int D, int C, int ORDER>
+static int launch_f64_table_grad(const void* grad, const float* inputs, const int32_t* offsets, const void* u, void* grad_emb, uint32_t B, uint32_t L,
+                                 const GridLevels& lv, uint32_t gridtype, bool ac, uint32_t interp, void* workspace, hipStream_t st) {
     for (uint32_t level = 0; level < L; level++) {
-        const uint32_t *keys, *vals;
-        f64_sort_level<D>(inputs, offsets, B, level, lv.scale[level], lv.res[level], gridtype, ac, interp, workspace, &keys, &vals, st);
-        NGP_LAUNCH((k_f64_grid_sum<D, C>), dim3(grid_blocks(n, F64_THREADS)), dim3(F64_THREADS), 0, st, keys, vals, n, (const double*)grad, inputs,
-                           offsets, (double*)grad_emb, B, level, lv.scale[level], ac, interp);
-        const int rc = check_launch("grid_encode_backward(fp64)");
+        const RecSides r = rec_sort_level(D, inputs, offsets, B, level, lv.scale[level], lv.res[level], gridtype, ac, interp, InputMap{0.0f, 0.0f},
+                                          workspace, st);
+        NGP_LAUNCH((k_f64_grid_run_sum<D, C, ORDER>), dim3(grid_blocks(r.n, F64_THREADS)), dim3(F64_THREADS), 0, st, r.keys[0], r.vals[0], r.keys[1],
+                           r.vals[1], r.n, (const double*)grad, inputs, (const double*)u, offsets, (double*)grad_emb, B, level, lv.scale[level], ac,
+                           interp);
+        const int rc = check_launch(ORDER == 1 ? "grid_encode_backward(fp64)" : "grid_encode_backward_backward(fp64)");
         if (rc) return rc;
     }
     return NGP_OK;
+}
+
+int f64_grid_table_grad(uint32_t order, const void* grad, const float* inputs, const int32_t* offsets, const void* u, void* grad_embeddings,
+                        uint32_t B, uint32_t D, uint32_t C, uint32_t L, const GridLevels& lv, uint32_t gridtype, bool align_corners, uint32_t interp,
+                        void* workspace, hipStream_t st) {
+    if (order == 1) {
+        NGP_DISPATCH_DC(D, C, launch_f64_table_grad<D_, C_, 1>(grad, inputs, offsets, u, grad_embeddings, B, L, lv, gridtype, align_corners, interp,
+                                                               workspace, st))
+    } else {
+        NGP_DISPATCH_DC(D, C, launch_f64_table_grad<D_, C_, 2>(grad, inputs, offsets, u, grad_embeddings, B, L, lv, gridtype, align_corners, interp,
+                                                               workspace, st))
+    }
+    return NGP_ERR_INVALID;   // (D and C are checked by the entries)
 }
 
 int f64_grid_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C,
                       uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, bool align_corners, uint32_t interp,
                       void* workspace, size_t workspace_bytes, hipStream_t st) {
     if (B == 0) return NGP_OK;
-    NGP_REQUIRE(((uint64_t)B << D) <= (1ull << 31), NGP_ERR_INVALID, "grid_encode_backward: fp64: B * 2^D must not exceed 2^31 (B=%u, D=%u)", B, D);
-    const size_t need = f64_grid_backward_workspace_bytes(B, D);
-    NGP_REQUIRE(workspace && workspace_bytes >= need, NGP_ERR_INVALID,
-                "grid_encode_backward: fp64 needs a workspace of %zu bytes (ngp_grid_backward_workspace_bytes), got %zu", need,
-                workspace ? workspace_bytes : (size_t)0);
-    NGP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, NGP_ERR_INVALID, "grid_encode_backward: fp64: workspace must be 256-byte aligned");
+    int rc = f64_grid_check_workspace("grid_encode_backward", "ngp_grid_backward_workspace_bytes", B, D, workspace, workspace_bytes);
+    if (rc) return rc;
     GridLevels lv;
     fill_levels(lv, L, S, H);
-    const int rc = [&]() -> int {
-        NGP_DISPATCH_DC(D, C, launch_f64_backward<D_, C_>(grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, align_corners, interp, workspace, st))
-        set_error("grid_encode_backward: unsupported (D=%u, C=%u)", D, C);
-        return NGP_ERR_INVALID;
-    }();
+    rc = f64_grid_table_grad(1, grad, inputs, offsets, nullptr, grad_embeddings, B, D, C, L, lv, gridtype, align_corners, interp, workspace, st);
     if (rc || !(dy_dx && grad_inputs)) return rc;
     NGP_LAUNCH(k_f64_grid_input_bwd, dim3(cdiv(B * D, F64_THREADS)), dim3(F64_THREADS), 0, st, (const double*)grad, (const double*)dy_dx,
                        (double*)grad_inputs, B, L, D, C);

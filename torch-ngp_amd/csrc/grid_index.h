@@ -1,6 +1,6 @@
 // Grid-encoder indexing shared by the fp16/fp32 kernels (gridencoder.hip), the fp64 ones (fp64.hip), the second-order backward
-// (grid_second.hip) and the ordered scatter (grid_ordered.hip): the per-level table, the corner-index rule, the position of a point inside
-// a level, the corner weight and the first backward's input term.  One statement of each, so the fp64 path locates points and computes
+// (grid_second.hip), the record sort (grid_records.hip) and the ordered scatter (grid_ordered.hip): the per-level table, the corner-index
+// rule, the position of a point inside a level and its input map, the corner weight and the first backward's input term.  One statement of each, so the fp64 path locates points and computes
 // interpolation weights exactly as the fp32 path does.  Also the host plumbing the units share: the level table of a call, the launch-grid
 // cap and the (D, C) dispatch.
 #pragma once

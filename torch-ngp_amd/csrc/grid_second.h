@@ -1,6 +1,7 @@
 // The second-order backward's per-corner terms and its per-point kernel (the u-terms of grid_second.hip), in a header so that the ordered
-// scatter (grid_ordered.hip) forms a_k with the same code and gets grad_grad / grad_inputs2 from a gather-only instantiation of the same
-// kernel: the same bits as ngp_grid_encode_backward_backward.
+// scatter (grid_ordered.hip) gets grad_grad / grad_inputs2 from a gather-only instantiation of the same kernel: the same bits as
+// ngp_grid_encode_backward_backward.  Also record_coeff: what a sorted record (grid_records.h) contributes to its table entry, first and
+// second order, for the run sums of fp64.hip and grid_ordered.hip.
 #pragma once
 #include "common.h"
 #include "grid_index.h"
@@ -92,6 +93,30 @@ __device__ __forceinline__ A corner_terms(const float (&phi)[D], const float (&d
         }
     }
     return a * s;
+}
+
+// The coefficient of the record of (a point, corner k) in a level's table gradient, recomputed from the point with the code of the atomic
+// paths; x, u: the point's D inputs and, for ORDER 2, its D values of u.  ORDER 1: the weight w_k, corner_weight after locate with the
+// call's input map (an fp32 value: exact in double).  ORDER 2: a_k, from the fp32 phi, 1 - phi and phi' of locate_d2 (unit inputs: `im` is
+// not read) and u in double -- the sum over d of terms of both signs cancels, and the fp32 form of the atomic path is exact only relative
+// to the terms, not to a_k.
+template <int D, int ORDER, typename U>
+__device__ __forceinline__ double record_coeff(const float* x, const U* u, uint32_t k, float scale, bool align_corners,
+                                               uint32_t interp, InputMap im) {
+    if constexpr (ORDER == 1) {
+        float frac[D], deriv[D];
+        uint32_t cell[D];
+        locate<D>(x, scale, align_corners, interp, frac, deriv, cell, im);
+        return (double)corner_weight<D>(frac, k);
+    } else {
+        float phi[D], d1[D], d2[D];
+        double ud[D], unused[D];
+        uint32_t cell[D];
+        locate_d2<D>(x, scale, align_corners, interp, phi, d1, d2, cell);
+#pragma unroll
+        for (int d = 0; d < D; d++) ud[d] = (double)u[d];
+        return corner_terms<double, D, false>(phi, d1, d2, ud, k, (double)scale, unused);
+    }
 }
 
 __device__ __forceinline__ void gg_atomic_add(float* p, float v) { unsafeAtomicAdd(p, v); }                 // global_atomic_add_f32

@@ -18,8 +18,8 @@
 // atomics, in every dtype.  The scatter:
 //   * fp32 tables: global_atomic_add_f32 (unsafeAtomicAdd); fp16 tables (even C): global_atomic_pk_add_f16; before the atomic, runs of
 //     equal destinations over the point slots of a wave are summed (segmented scan, issued only when a wave has such a run);
-//   * fp64 tables: bit-reproducible.  The records and the stable radix sort of the first-order fp64 backward (fp64.hip,
-//     f64_grid_sort_level), then one lane per run of equal entries sums a_k g in slot order in fp64 and adds the sum once.
+//   * fp64 tables: bit-reproducible, left to fp64.hip (f64_grid_table_grad, order 2): the record sort and run sum of the first-order fp64
+//     backward with the coefficient a_k.
 #include "common.h"
 #include "grid_index.h"
 #include "grid_second.h"
@@ -27,45 +27,6 @@
 #include <math.h>
 
 namespace ngp {
-
-// ------------------------------------------------------------------------------------------------
-// fp64 tables: the dL2/dE scatter, bit-reproducible.  One lane per run of equal entries of the sorted records of one level (fp64.hip:
-// f64_grid_sort_level; the run's first record), the contributions a_k g in slot order, summed in fp64, added once.
-// ------------------------------------------------------------------------------------------------
-template <int D, int C>
-__global__ __launch_bounds__(GG_THREADS) void k_f64_grid_bwd_bwd_sum(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
-                                                                     const double* __restrict__ grad, const float* __restrict__ inputs,
-                                                                     const double* __restrict__ uin, const int32_t* __restrict__ offsets,
-                                                                     double* __restrict__ grad_grid, uint32_t B, uint32_t level, float scale,
-                                                                     bool align_corners, uint32_t interp) {
-    constexpr uint32_t NO_ENTRY = 0xffffffffu;  // (fp64.hip: a record of a point outside [0,1]^D)
-    for (uint32_t i = blockIdx.x * GG_THREADS + threadIdx.x; i < n; i += gridDim.x * GG_THREADS) {
-        const uint32_t e = keys[i];
-        if (e == NO_ENTRY || (i > 0u && keys[i - 1u] == e)) continue;
-        double acc[C];
-#pragma unroll
-        for (int c = 0; c < C; c++) acc[c] = 0.0;
-        for (uint32_t j = i; j < n && keys[j] == e; j++) {
-            const uint32_t slot = vals[j], b = slot >> D, k = slot & ((1u << D) - 1u);
-            NGP_BOUNDS(b < B);
-            float phi[D], d1[D], d2[D];
-            uint32_t cell[D];
-            locate_d2<D>(inputs + (size_t)b * D, scale, align_corners, interp, phi, d1, d2, cell);
-            double u[D], unused[D];
-#pragma unroll
-            for (int d = 0; d < D; d++) u[d] = uin[(size_t)b * D + d];
-            const double a = corner_terms<double, D, false>(phi, d1, d2, u, k, (double)scale, unused);
-            const double* g = grad + ((size_t)level * B + b) * C;
-#pragma unroll
-            for (int c = 0; c < C; c++) acc[c] = __builtin_fma(a, g[c], acc[c]);
-        }
-        const uint32_t off0 = (uint32_t)offsets[level];
-        NGP_BOUNDS(e < (uint32_t)offsets[level + 1] - off0);
-        double* dst = grad_grid + ((size_t)off0 + e) * C;
-#pragma unroll
-        for (int c = 0; c < C; c++) dst[c] += acc[c];
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // host
@@ -99,19 +60,9 @@ static int launch_bwd_bwd(const GGArgs& a, hipStream_t st) {
             const int rc = check_launch("grid_encode_backward_backward");
             if (rc) return rc;
         }
-        if constexpr (!SCATTER) {
-            const uint32_t n = a.B << D;
-            for (uint32_t level = 0; level < a.L; level++) {
-                const uint32_t *keys, *vals;
-                f64_grid_sort_level((uint32_t)D, a.inputs, a.offsets, a.B, level, a.lv.scale[level], a.lv.res[level], a.gridtype, a.align_corners,
-                                    a.interp, a.workspace, &keys, &vals, st);
-                NGP_LAUNCH((k_f64_grid_bwd_bwd_sum<D, C>), dim3(grid_blocks(n, GG_THREADS)), dim3(GG_THREADS), 0, st, keys, vals, n, (const double*)a.grad,
-                                   a.inputs, (const double*)a.u, a.offsets, (double*)a.grad_embeddings, a.B, level, a.lv.scale[level], a.align_corners,
-                                   a.interp);
-                const int rc = check_launch("grid_encode_backward_backward(fp64)");
-                if (rc) return rc;
-            }
-        }
+        if constexpr (!SCATTER)
+            return f64_grid_table_grad(2, a.grad, a.inputs, a.offsets, a.u, a.grad_embeddings, a.B, D, C, a.L, a.lv, a.gridtype, a.align_corners,
+                                       a.interp, a.workspace, st);
         return NGP_OK;
     }
 }
@@ -151,12 +102,8 @@ extern "C" int ngp_grid_encode_backward_backward(const void* grad, const float* 
     NGP_REQUIRE(grad && inputs && embeddings && offsets && grad_grad_inputs && grad_embeddings, NGP_ERR_INVALID, "%s: NULL tensor", fn);
     NGP_REQUIRE(B < (1u << 31), NGP_ERR_INVALID, "%s: B must be below 2^31 (got %u)", fn, B);
     if (dtype == NGP_F64) {
-        NGP_REQUIRE(((uint64_t)B << D) <= (1ull << 31), NGP_ERR_INVALID, "%s: fp64: B * 2^D must not exceed 2^31 (B=%u, D=%u)", fn, B, D);
-        const size_t need = f64_grid_backward_workspace_bytes(B, D);
-        NGP_REQUIRE(workspace && workspace_bytes >= need, NGP_ERR_INVALID,
-                    "%s: fp64 needs a workspace of %zu bytes (ngp_grid_backward_backward_workspace_bytes), got %zu", fn, need,
-                    workspace ? workspace_bytes : (size_t)0);
-        NGP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, NGP_ERR_INVALID, "%s: fp64: workspace must be 256-byte aligned", fn);
+        const int rc = f64_grid_check_workspace(fn, "ngp_grid_backward_backward_workspace_bytes", B, D, workspace, workspace_bytes);
+        if (rc) return rc;
     }
     GGArgs a;
     a.grad = grad;
