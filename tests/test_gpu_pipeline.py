@@ -122,6 +122,28 @@ def test_on_device_render_loop_equals_host_driven_loop(density_scale, perturb):
         assert float(res[('host', k)][0].std()) > 0
 
 
+@pytest.mark.parametrize('density_scale', [1.0, 40.0])
+def test_per_stage_render_loop_issues_what_the_recorded_parent_issued(density_scale):
+    """the 4096-ray frame of tests/golden/render_loop_schedule.json through the per-stage loop with the stage probe on: every stage of every
+    iteration carries the name, lanes, rows, n_total and alive count (read from the iteration's state snapshot) that the commit the golden
+    was recorded on issued -- the frame object of nerf/render_loop.py issues what the loop it replaced issued, stage by stage"""
+    import importlib.util
+    import json
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('render_loop_schedule_dump', os.path.join(root, 'tools', 'render_loop_schedule_dump.py'))
+    dump = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dump)   # (the recorder of the golden, loaded from its file: sys.path stays as it is)
+    with open(os.path.join(root, 'tests', 'golden', 'render_loop_schedule.json')) as f:
+        want, = [fr for fr in json.load(f)['frames'] if fr['n_rays'] == 4096 and fr['density_scale'] == density_scale]
+    model, _, _, dev = _setup(emb_scale=0.5)
+    got = dump.record(model, dump.frame_rays(4096, want['seed'], dev), density_scale, want['perturb'], native=False)
+    sequence = lambda rec: [(name, *it) for it in rec['iterations'] for name in rec['stages']]   # noqa: E731
+    assert len(got['stages']) == 5 and len(got['iterations']) >= 6
+    assert sequence(got) == sequence(want['stages'])
+    assert got['debug'] == want['stages']['debug'] and got['final_alive'] == want['stages']['final_alive']
+
+
 def test_update_extra_state_and_training_loop_run():
     model, orc, bits, dev = _setup(emb_scale=1e-4)
     model.train()

@@ -11,7 +11,6 @@ quarter-occupied resampling afterwards; packbits against min(mean_density, densi
 import math
 
 import numpy as np
-import os
 import torch
 import torch.nn as nn
 
@@ -332,260 +331,11 @@ class NeRFRenderer(nn.Module):
 
     def _render_loop_on_device(self, rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image, perturb, dt_gamma, max_steps, T_thresh,
                                sync_every=8, aux_infer=None, aux_frame=None):
-        """the eval loop of run_cuda (renderer.py:341-367) with its state on the device (extension): the alive count,
-        the per-iteration n_step = max(min(N // n_alive, 8), 1) and the marched-step total live in a device word pair that the march /
-        composite / compaction kernels read, so the host issues `sync_every` iterations back to back and reads the count back once per
-        batch (the reference reads it every iteration through `rays_alive[rays_alive >= 0]`).  Between read-backs launches are sized for
-        the last known count; lanes and sample rows beyond the true count do nothing / are zero rows.  Same slot layout and compaction
-        order as the host-driven loop, and a ray's samples and their compositing order do not depend on how they are chunked into
-        iterations: same image, bit for bit (tests/test_gpu_pipeline.py) -- with one caveat: the loop ends when the SUM of the per-iteration
-        n_step reaches max_steps (renderer.py:341,367), and the adaptive row budget below changes that sequence, so a ray that is still
-        alive at that cutoff is truncated at a different sample than under the reference rule.  A ray emits at most n_step samples per
-        iteration, so the cutoff is only reachable by a ray that itself needs >= max_steps samples (none with dt_gamma = 0 inside bound 1,
-        where the longest chord is max_steps steps); `adaptive_n_step = False` keeps the reference sequence exactly.
-        Batches grow 2, 2, 4, 8, 8, ... iterations (an opaque frame is over after ~6 iterations, a transparent one needs ~100).
-        `graph_loop = True` replays the batches after the first from HIP graphs (one graph of two iterations per row-count bucket N, N/2,
-        N/4, ..., captured on first use and kept on the model; fixed reference n_step rule).  Measured on MI355X (tools/bench_render.py,
-        800x800, transparent / opaque frame): host-driven loop 26.0 / 2.2 ms, device state with the reference's n_step rule 21.3 / 1.93 ms,
-        + graphs 21.3 / 2.0 ms (the frame is bound by its kernels, not by launches: graphs are off by default), device state with the adaptive
-        row budget below (`adaptive_n_step`, default) 17.3 / 1.95 ms.  `_loop_debug = []` collects (iterations done, alive bound, boost,
-        survival per iteration) at every read-back (tools/render_loop_trace.py).
-        aux_infer / aux_frame (run_cuda): the caller's channels, composited into aux_frame['out'] by
-        composite_rays_features_dev in front of every composite_rays_dev.  A Python callable cannot be issued from C or captured: the native
-        pair call and graph_loop are declined for such a frame; culling, the adaptive row budget and the tail cap stay."""
-        from raymarching.raymarching import _backend as rb   # compiled binding when built, else ctypes (same C ABI)
-        from raymarching import backend as rf                # (the feature compositor's entries are ctypes-only)
-        import _ngp_capi as capi
-        n_rays, dev = rays_o.shape[0], rays_o.device
-        key = (n_rays, str(dev), float(dt_gamma), int(max_steps), float(T_thresh), float(self.density_scale), self.density_bitfield.data_ptr(),
-               torch.is_autocast_enabled('cuda'), self.training)
-        cache = getattr(self, '_loop_cache', None)
-        if cache is None or cache['key'] != key:
-            cache = {'key': key, 'graphs': {}, 'failed': False,
-                     'alive': [torch.empty(n_rays, dtype=torch.int32, device=dev), torch.empty(n_rays, dtype=torch.int32, device=dev)],
-                     'state': torch.zeros(2, 2, dtype=torch.int32, device=dev),
-                     'ws': torch.empty(int(capi.lib.ngp_compact_rays_workspace_bytes(n_rays)), dtype=torch.uint8, device=dev),
-                     'bufs': [torch.empty_like(t) for t in (rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image)],
-                     'arange': torch.arange(n_rays, dtype=torch.int32, device=dev)}
-            self._loop_cache = cache
-        # static buffers (the graphs hold their addresses): this frame's inputs and accumulators are copied in, the results copied out --
-        # only with graph_loop; the eager loop works on the caller's tensors (eleven 4-us copy launches per frame less)
-        static = bool(getattr(self, 'graph_loop', False)) and not cache['failed'] and aux_infer is None
-        frame = tuple(t.contiguous() for t in (rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image))
-        static = static or any(a is not b for a, b in zip(frame[5:], (weights_sum, depth, image)))   # (accumulators must be updated in place)
-        if static:
-            for dst, src in zip(cache['bufs'], (rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image)):
-                dst.copy_(src)
-            s_o, s_d, s_near, s_far, s_t, s_ws, s_depth, s_image = cache['bufs']
-        else:
-            s_o, s_d, s_near, s_far, s_t, s_ws, s_depth, s_image = frame
-        alive, state, ws = cache['alive'], cache['state'], cache['ws']
-        state.zero_()
-        # Empty-ray culling (round 5, `cull_empty_rays`, default on): in the first iteration every ray is alive and more than half of them
-        # never meet an occupied voxel -- each walks the whole box (284 of the opaque frame's ~900 us of k_march_rays) to emit nothing.
-        # A dilated (H/4)^3 occupancy per cascade and a half-cell sampling of every ray decide CONSERVATIVELY which rays those are
-        # (csrc/raymarching.hip k_cull_rays); they are left out of the initial alive list.  They would have produced no sample: same
-        # image, bit for bit (tests/test_gpu_pipeline.py).  Not with perturb: the start offsets are drawn per alive-list SLOT.
-        cull = (getattr(self, 'cull_empty_rays', True) and not perturb and self.grid_size >= 16 and (self.grid_size & (self.grid_size - 1)) == 0
-                and hasattr(rb, 'cull_rays'))
-        if cull:
-            coarse = cache.get('coarse')
-            if coarse is None:
-                coarse = cache['coarse'] = torch.empty(int(capi.lib.ngp_coarse_occupancy_bytes(self.cascade, self.grid_size)), dtype=torch.uint8, device=dev)
-                cache['flags'] = torch.empty(n_rays, dtype=torch.int32, device=dev)
-            rb.coarse_occupancy(self.density_bitfield.contiguous(), self.cascade, self.grid_size, coarse)
-            rb.cull_rays(s_o, s_d, s_near, s_far, n_rays, float(self.bound), self.cascade, self.grid_size, coarse, cache['flags'])
-            rb.compact_rays(cache['flags'], n_rays, alive[0], state[0])     # state[0] = {rays kept, 0 steps marched}
-        else:
-            alive[0].copy_(cache['arange'])
-            state[0, 0] = n_rays
-        bits = self.density_bitfield.contiguous()
-
-        def iteration(cur, lanes, rows, noises, n_total=n_rays, cap=0):
-            # n_total: what the kernels divide by the alive count to get n_step = clamp(n_total // n_alive, 1, cap) -- the frame's ray count
-            # (the reference's rule) times the host-chosen `boost` below; cap = 0: the reference's 8
-            # `_loop_probe = []` (bench.py's whole-frame accounting): HIP-event pairs around the four stages of every iteration + a copy of the
-            # iteration's device state (alive rays) -- (stage, start, end, lanes, rows, n_total, state copy); None: no events, no copies
-            probe = getattr(self, '_loop_probe', None)
-
-            def stage(name, fn):
-                if probe is None:
-                    return fn()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                out = fn()
-                e1.record()
-                probe.append((name, e0, e1, lanes, rows, n_total, snap))
-                return out
-            snap = state[cur].clone() if probe is not None else None
-            xyzs = torch.empty(rows, 3, dtype=torch.float32, device=dev)
-            dirs = torch.empty(rows, 3, dtype=torch.float32, device=dev)
-            deltas = torch.empty(rows, 2, dtype=torch.float32, device=dev)
-            stage('march_rays', lambda: rb.march_rays_dev(state[cur], lanes, n_total, cap, alive[cur], s_t, s_o, s_d, self.bound, dt_gamma, max_steps,
-                                                          self.cascade, self.grid_size, bits, s_near, s_far, xyzs, dirs, deltas, noises, rows))
-            hook = getattr(self, '_loop_iter_hook', None)
-            if hook is not None:   # bench.py's roofline pass: the rows this iteration really emitted (device count), for honest units per launch
-                hook(deltas)
-            if hasattr(self, 'forward_scaled'):   # (the fused network folds the density scale: one launch less per iteration)
-                sigmas, rgbs = stage('network (encoder + MLPs + glue)', lambda: self.forward_scaled(xyzs, dirs, self.density_scale))
-                sigmas, rgbs32 = stage('casts (density_scale, fp32 copies)', lambda: (sigmas.float().contiguous(), rgbs.float().contiguous()))
-            else:
-                sigmas, rgbs = stage('network (encoder + MLPs + glue)', lambda: self(xyzs, dirs))
-                sigmas, rgbs32 = stage('casts (density_scale, fp32 copies)', lambda: ((self.density_scale * sigmas).float().contiguous(), rgbs.float().contiguous()))
-            if aux_infer is not None:   # before composite_rays_dev: the feature kernel reads the weights_sum that call advances
-                feats = stage('aux_infer (the caller\'s channels)', lambda: self._aux_infer_feats(aux_infer, aux_frame, xyzs, dirs, sigmas, rgbs32, n_rays))
-                stage('composite_rays_features', lambda: rf.composite_rays_features_dev(state[cur], lanes, n_total, cap, T_thresh, alive[cur], sigmas, feats,
-                                                                                        deltas, s_ws, aux_frame['out']))
-            stage('composite_rays', lambda: rb.composite_rays_dev(state[cur], lanes, n_total, cap, T_thresh, alive[cur], s_t, sigmas, rgbs32, deltas, s_ws,
-                                                                  s_depth, s_image))
-            stage('compact_rays', lambda: rb.compact_rays_dev(state[cur], lanes, n_total, cap, max_steps, alive[cur], alive[1 - cur], state[1 - cur], ws))
-
-        def pad(rows):
-            return rows + 128 - rows % 128  # the marchers' padding rule (raymarching.py:328-331); the fused network wants multiples of 128
-
-        # ONE native call per pair of iterations (round 6, ngp_render_iterations_dev: march -> encode -> network -> composite -> compact twice,
-        # issued from C) where the Python `iteration` above makes ten calls and six allocations -- the tail iterations of an opaque frame carried
-        # ~30 us of GPU work against ~95 us of host issue each.  Same kernels, arguments and order: the image is the same bit for bit
-        # (tests/test_gpu_pipeline.py).  Taken when the network call would run the fused inference path on pinned fp16 weights and nobody is
-        # probing the stages; `native_loop = False` keeps the per-stage calls.
-        native = None
-        if (getattr(self, 'native_loop', True) and aux_infer is None and getattr(self, '_loop_probe', None) is None and getattr(self, '_loop_iter_hook', None) is None
-                and hasattr(self, 'forward_scaled') and hasattr(capi.lib, 'ngp_render_iterations_dev')):
-            import ctypes
-            import fused
-            w = fused.inference_weights(self, s_o)
-            if w is not None:
-                emb16, ws16, wc16, cfg = w
-                a = capi.RenderLoop()
-                a.state, a.alive[0], a.alive[1] = state.data_ptr(), alive[0].data_ptr(), alive[1].data_ptr()
-                a.rays_t, a.rays_o, a.rays_d, a.nears, a.fars, a.grid = (s_t.data_ptr(), s_o.data_ptr(), s_d.data_ptr(), s_near.data_ptr(), s_far.data_ptr(),
-                                                                         bits.data_ptr())
-                a.embeddings, a.offsets, a.w_sigma, a.w_color = emb16.data_ptr(), self.encoder.offsets.data_ptr(), ws16.data_ptr(), wc16.data_ptr()
-                a.level_cost_host = capi.ray_level_costs(cfg.L, cfg.S, cfg.H, 3.0 ** 0.5 / (1024.0 * max(float(cfg.bound), 1e-6))) if fused.USE_BALANCED_FORWARD else None
-                a.weights_sum, a.depth, a.image, a.compact_workspace = s_ws.data_ptr(), s_depth.data_ptr(), s_image.data_ptr(), ws.data_ptr()
-                a.max_steps, a.cascade, a.grid_size = int(max_steps), int(self.cascade), int(self.grid_size)
-                a.L, a.H, a.gridtype, a.interp, a.num_layers_sigma, a.num_layers_color = cfg.L, cfg.H, cfg.gridtype, cfg.interp, cfg.nl_sigma, cfg.nl_color
-                a.align_corners = cfg.align
-                a.bound, a.dt_gamma, a.T_thresh, a.S, a.density_scale = float(self.bound), float(dt_gamma), float(T_thresh), float(cfg.S), float(self.density_scale)
-                if getattr(self, 'loop_device_rows', True):
-                    # the march publishes the rows that can carry a sample; the encoder and the network -- launched for the stale host-side
-                    # bound -- stop there (ngp_march_rays_dev_rows / ngp_grid_encode_forward_sel / ngp_network_forward_rows): an oversized
-                    # iteration costs its (mostly empty) launches, not the evaluation of zero rows, so more iterations go between read-backs
-                    if 'rows_used' not in cache:
-                        cache['rows_used'] = torch.zeros(1, dtype=torch.int32, device=dev)
-                    a.rows_used = cache['rows_used'].data_ptr()
-                native = (a, (emb16, ws16, wc16), [None])
-
-        def pair(lanes, rows, noises, n_total=n_rays, cap=0):
-            """iterations on state 0 then state 1"""
-            if native is None:
-                iteration(0, lanes, rows, noises, n_total, cap)
-                iteration(1, lanes, rows, None, n_total, cap)
-                return
-            a = native[0]
-            held = native[2][0]
-            if held is None or held[0] < rows:
-                # sample buffers: ONE block per frame, re-made only when a pair needs more rows than any before it (the first pair is the
-                # largest of an opaque frame).  Allocating per pair put six allocator calls between a read-back and the first launch behind it
-                # -- measured 4-7 % on the frame, where the per-stage loop prepares its later stages under its earlier launches.
-                f32 = dict(dtype=torch.float32, device=dev)
-                bufs = (torch.empty(rows, 3, **f32), torch.empty(rows, 3, **f32), torch.empty(rows, 2, **f32),
-                        torch.empty(a.L * rows * 2, dtype=torch.half, device=dev), torch.empty(rows, **f32), torch.empty(rows, 3, **f32))
-                native[2][0] = held = (rows, bufs)
-                a.xyzs, a.dirs, a.deltas, a.enc, a.sigmas, a.rgbs = [t.data_ptr() for t in bufs]
-            native[2].append(noises)        # (alive until the frame is over: the launches are asynchronous)
-            a.noises = None if noises is None else noises.data_ptr()
-            a.lanes, a.rows, a.n_total, a.n_step_cap = int(lanes), int(rows), int(n_total), int(cap)
-            capi.check(capi.lib.ngp_render_iterations_dev(ctypes.cast(ctypes.pointer(a), ctypes.c_void_p), 2, 0, capi.stream()))
-            self._loop_native_pairs = getattr(self, '_loop_native_pairs', 0) + 1
-
-        # the first two iterations: full-frame sized, kernel-bound, the only ones that may perturb -- issued eagerly
-        # Row budget of this first pair: `loop_initial_boost` x N (default 2; 1 = the reference's n_step rule).  With N rows the opaque frame's
-        # first iterations march 1 and 2 samples per ray (n_step = N // alive) although every surviving ray has 5-10 to give: twice the
-        # rows (n_step 3 and 4 after the empty-ray culling) finish the frame in two iterations less -- 1.62 -> 1.40 ms; 3 x N evaluates
-        # too many rows of rays that end early (1.55 ms); the transparent frame does not care (14.45 -> 14.3 ms).  Same image -- EXCEPT with
-        # perturb: the start offset is added to the marcher's t of the first call only, while the compositor advances rays_t by the
-        # summed deltas from the UN-offset start (the reference's behaviour), so the samples of the first call are the offset ones and how
-        # many they are must follow the reference's rule (tests/test_gpu_pipeline.py caught it): no boost then.
-        ib = 1 if perturb else max(1, int(os.environ.get('NGP_LOOP_INITIAL_BOOST', getattr(self, 'loop_initial_boost', 2))))
-        full = pad(ib * n_rays)
-        noises = torch.rand(n_rays, dtype=torch.float32, device=dev) if perturb else None
-        pair(n_rays, full, noises, ib * n_rays)
-        done = 2
-        use_graphs = getattr(self, 'graph_loop', False) and not cache['failed'] and aux_infer is None
-        adaptive = getattr(self, 'adaptive_n_step', True) and not use_graphs
-        batch = 2
-        bound_alive = int(state[0, 0].item())
-        # Samples per ray and iteration.  The reference marches n_step = clamp(N // n_alive, 1, 8): about N sample rows per iteration.  A ray's
-        # samples and their compositing order do not depend on that chunking (same image, bit for bit), but the COST does: every
-        # march_rays call walks the rays that leave the surface to the far plane, ~0.1-0.3 ms of voxel stepping however few samples it
-        # emits (tools/march_probe.py), so a frame in which rays survive long (semi-transparent volume) pays for ~70 calls of 2-3 samples
-        # per ray.  From the 6th iteration on, while at least 9 of 10 rays survive an iteration, the row budget is doubled (n_step up to 8:
-        # `boost` x N rows), and halved again when rays start to terminate early (an opaque frame is over by then and never leaves
-        # boost = 1: no sample is evaluated in vain).
-        # The TAIL of a frame (round 5, profiles/r05_render_stages.txt): once most rays have terminated the reference's cap of 8 samples per
-        # ray and iteration leaves the row budget unused -- the opaque frame of a trained network spent 15 of its 26 iterations (~120 us of
-        # launches each) on fewer than 100 surviving rays.  `loop_tail_cap` (default 64) lifts the cap in the adaptive loop ONCE THE SURVIVORS
-        # ARE FEW: cap = clamp(N // alive at the last read-back, 8, 64), so an iteration still evaluates about N rows (lifting it while many
-        # rays are alive made the transparent frame slower: the rows are sized from a stale count and most of them were zero rows); in that
-        # tail the host also reads the count back after every pair of iterations (a batch of 8 kept launching for rays that were long gone).
-        # 26 -> 8 iterations on that frame, 3.1 -> 2.1 ms.  Same image, bit for bit (chunking does not change a ray's samples or their
-        # compositing order); the max_steps caveat of the docstring applies unchanged.  loop_tail_cap = 8 / adaptive_n_step = False: the
-        # reference sequence.
-        tail_cap = int(getattr(self, 'loop_tail_cap', os.environ.get('NGP_LOOP_TAIL_CAP', 64))) if adaptive else 8
-        tail_cap = max(8, min(tail_cap, 1024))
-        boost, prev_alive, prev_iters = 1, n_rays, 2
-        while bound_alive > 0 and done < max_steps:
-            cap = max(8, min(tail_cap, n_rays // max(bound_alive, 1)))
-            if adaptive:
-                survival = (bound_alive / max(prev_alive, 1)) ** (1.0 / max(prev_iters, 1))
-                if survival >= 0.9 and boost < 8 and done >= 6 and 2 * boost * n_rays <= int(getattr(self, 'loop_max_rows', 1 << 26)):   # (an opaque frame is over by then: its rays saturate within ~10 samples)
-                    boost *= 2
-                elif survival < 0.75 and boost > 1:
-                    boost //= 2
-            n_total = boost * n_rays
-            if getattr(self, '_loop_debug', None) is not None:
-                self._loop_debug.append((done, bound_alive, boost, round(survival, 3) if adaptive else None))
-            # row bucket: the smallest of B, B/2, B/4, ... (B = boost * N) that holds min(B, 8 * alive) rows (>= 2048)
-            need = min(n_total, cap * bound_alive)
-            bucket = n_total
-            while bucket // 2 >= max(need, 2048):
-                bucket //= 2
-            # (row buckets exist for the graphs: one captured batch per bucket; without graphs the buffers are sized exactly)
-            rows = pad(bucket if use_graphs else need)
-            lanes = min(n_rays, bound_alive) if not use_graphs else (n_rays if bucket == n_rays else bucket // 8 + 1)
-            g = cache['graphs'].get(bucket) if use_graphs else None
-            if use_graphs and g is None:
-                try:
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        iteration(0, lanes, rows, None)
-                        iteration(1, lanes, rows, None)
-                    cache['graphs'][bucket] = g
-                except Exception as e:  # noqa: BLE001 -- keep rendering eagerly; the caller can inspect _loop_cache['failed']
-                    cache['failed'] = repr(e)
-                    use_graphs, g = False, None
-                    torch.cuda.synchronize()
-            prev_alive, prev_iters = bound_alive, 0
-            for _ in range(max(1, batch // 2)):
-                if g is not None:
-                    g.replay()
-                else:
-                    pair(lanes, rows, None, n_total, 0 if cap == 8 else cap)
-                done += 2
-                prev_iters += 2
-            device_rows = native is not None and bool(native[0].rows_used)
-            batch = min(sync_every, batch * 2) if done >= 6 else (4 if device_rows else batch)
-            bound_alive = int(state[0, 0].item())
-            if adaptive and tail_cap > 8 and bound_alive * 16 <= n_rays:
-                # the tail: a pair of iterations now marches up to 2 x cap samples per ray -- look before launching more.  With device-side
-                # row counts an iteration that turns out (nearly) empty costs ~25 us of launches, a read-back turnaround 50-80 us: two pairs
-                batch = 4 if device_rows else 2
-        if static:
-            weights_sum.copy_(s_ws)
-            depth.copy_(s_depth)
-            image.copy_(s_image)
+        """the eval loop of run_cuda (renderer.py:341-367) with its state on the device: nerf/render_loop.py; weights_sum, depth
+        and image are accumulated in place, same image as the host-driven loop bit for bit"""
+        from .render_loop import FrameLoop
+        FrameLoop(self, (rays_o, rays_d, nears, fars, rays_t, weights_sum, depth, image), perturb, dt_gamma, max_steps, T_thresh, sync_every,
+                  aux_infer, aux_frame).run()
 
     # -- occupancy grid maintenance -------------------------------------------------------------
     def _cascade_points(self, coords, cas):
