@@ -960,6 +960,38 @@ int ngp_rays_from_pixels_backward(const float* grad_rays_o, const float* grad_ra
                                   uint32_t W, const int64_t* inds, uint32_t inds_batch_stride, uint32_t N, float* grad_poses,
                                   ngp_stream_t stream);
 
+/* ---- error-map ray sampling (csrc/error_map.hip) ----
+ * replaces the error-map branch of get_rays (nerf/utils.py:85-106: torch.multinomial(error_map, N, replacement=False) over the res x res
+ * map, then a uniform offset inside each drawn cell) by ONE launch that uses no torch generator: per image b, N distinct cells drawn by
+ * successive sampling without replacement proportional to error_map[b] (the exponential race torch.multinomial itself runs), refined to
+ * pixels of the H x W frame.  All integer arithmetic mod 2^32:
+ *   s = seed + (seed_dev ? *seed_dev : 0)        seed_dev: one device word read by the kernel (e.g. the optimizer's step count)
+ *   mix(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16       (the finaliser of the marcher's seeded noise)
+ *   word(i, b, k) = mix(mix((i * 0x9E3779B9) ^ (s * 0x85EBCA6B + 0x27D4EB2F)) ^ (b * 0xC2B2AE35 + k * 0x165667B1 + 0x27D4EB2F))
+ *   u_i = (float)(((word(i, b, 0) >> 9) << 1) | 1) * 2^-24                                   (exact, strictly inside (0, 1))
+ *   key_i = isfinite(w_i) && w_i > 0 ? -logf(u_i) / w_i : +inf                               (w = error_map[b]; fp32)
+ * The drawn set is the N cells smallest by (key bits as uint32, cell index), written in ASCENDING cell order: exactly N distinct cells
+ * whatever the map holds; zero, negative, NaN and inf weights are drawn only when fewer than N cells are drawable, lowest index first.
+ * Refinement (plain fp32, no fma): cell_h = (float)H / (float)res, cell_w = (float)W / (float)res,
+ *   r = (word(i, b, 1) >> 8) * 2^-24, c = (word(i, b, 2) >> 8) * 2^-24,
+ *   row = min((uint32)((float)(i / res) * cell_h + r * cell_h), H - 1), col = min((uint32)((float)(i % res) * cell_w + c * cell_w), W - 1)
+ * inds [B,N] = row * W + col, inds_coarse [B,N] = i (both int64, as torch indices).  Optional outputs: keys_out [B, res * res] (every
+ * cell's key), n_drawable [B] (cells with a finite positive weight: a caller can check without a fault or a synchronisation).
+ * One workgroup per image, keys in registers, radix select over an LDS histogram: no global atomics, no workspace, no host read-back
+ * (capturable).  NGP_ERR_INVALID before any device work: NULL error_map / inds / inds_coarse, res outside 1 .. 128, N > res * res,
+ * H == 0, W == 0 or H * W >= 2^31.  B == 0 or N == 0: nothing is launched. */
+int ngp_error_map_draw(const float* error_map, uint32_t B, uint32_t res, uint32_t N, uint32_t H, uint32_t W, uint32_t seed,
+                       const uint32_t* seed_dev, int64_t* inds, int64_t* inds_coarse, float* keys_out, uint32_t* n_drawable,
+                       ngp_stream_t stream);
+/* replaces the Trainer's error-map update (nerf/utils.py, train_step's error-map branch: error = loss.mean(-1) per ray, gather the
+ * cells' old values, ema_error = 0.1 * old + 0.9 * error, scatter_ back) for one image's row error_map_row [n_cells]: for each ray n with
+ * c = inds_coarse[n] in [0, n_cells), e_k = image[n,k] - target[n,k] (image, target [N,3] fp32),
+ *   err = ((e0 * e0 + e1 * e1) + e2 * e2) / 3.0f,   error_map_row[c] = keep * error_map_row[c] + take * err     (plain fp32)
+ * A cell index out of range skips that ray; cells that are not named keep their bits; a cell named more than once receives an
+ * unspecified one of its candidates (as scatter_ does; ngp_error_map_draw never names a cell twice).  NULL tensor: NGP_ERR_INVALID. */
+int ngp_error_map_update(float* error_map_row, const int64_t* inds_coarse, const float* image, const float* target, uint32_t N,
+                         uint32_t n_cells, float keep, float take, ngp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

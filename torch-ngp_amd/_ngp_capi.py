@@ -164,6 +164,9 @@ _SIGNATURES = {
     'ngp_ray_points_backward_f64': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _vp],
     'ngp_grid_input_gradient': [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _u32, _i32, _f32, _vp, _vp],
     'ngp_rays_from_pixels_backward': [_vp, _vp, _u32, _f32, _f32, _f32, _f32, _u32, _vp, _u32, _u32, _vp, _vp],
+    # error-map ray sampling (csrc/error_map.hip): the weighted draw without replacement and the per-step EMA scatter
+    'ngp_error_map_draw': [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    'ngp_error_map_update': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _f32, _vp],
 }
 for _name, _args in _SIGNATURES.items():
     _fn = getattr(lib, _name)

@@ -129,6 +129,9 @@ class GraphedTrainStep:
             raise ValueError(f'NGP_STEP_MARCH_AT={self.march_at!r}: one of {sorted(MARCH_MARKS)}')
         self.n_list_replays = 0
         self.loss = None
+        # the finished [N,3] fp32 image of the step that ran last: a view of a static buffer of the captured step (or the eager step's
+        # render), valid until the next step() -- what an error-map update needs besides the loss (nerf.utils.ErrorMaps)
+        self.image = None
         self.n_captures = 0
         self.capture_error = None
         self._checked_ok = False
@@ -156,6 +159,7 @@ class GraphedTrainStep:
                                  "optim.NGPAdam) and render_kwargs without 'geo' / 'staged'")
         self.lookahead = bool(lookahead) and self.direct and (averager is None or (averager is optimizer and getattr(optimizer, 'shard', False)))
         self.la = None                      # [(march graph, rest graph, loss)] x 2 once captured
+        self.la_image = None                # [image buffer] x 2 with them
         self.la_cur = 0                     # buffer set of the CURRENT batch
         self.la_ready = [None, None]        # what is marched into each set: references to the announced tensors + versions + occupancy epoch
         self.la_hits = 0                    # steps whose march had been done ahead
@@ -223,7 +227,7 @@ class GraphedTrainStep:
             return None
         return ((mc + 128 + self.quantum - 1) // self.quantum) * self.quantum
 
-    _SNAP = ('graphs', 'lists', 'la', 'loss', 'la_apply', '_rest_pool', 'sharded', 'used_direct', 'table_fused', 'producers_check', '_checked_ok')
+    _SNAP = ('graphs', 'lists', 'la', 'loss', 'image', 'la_image', 'la_apply', '_rest_pool', 'sharded', 'used_direct', 'table_fused', 'producers_check', '_checked_ok')
 
     def _snapshot(self):
         return {k: getattr(self, k, None) for k in self._SNAP}
@@ -433,7 +437,8 @@ class GraphedTrainStep:
             # After an all-reduce the sweep has to see the REDUCED values, so the replicated data-parallel path keeps it.
             self.producers_check = self._checked_ok and (self.averager is None)
             args, kwargs = self._iteration_args(self.producers_check)
-            loss = fused_train_iteration(*args, **kwargs)[0]
+            loss, image = fused_train_iteration(*args, **kwargs)[:2]
+            self.image = image
             self.used_direct = True
             return loss[0]
         self._geo_loss_needs_direct()
@@ -448,10 +453,16 @@ class GraphedTrainStep:
             with torch.autocast('cuda', dtype=self.autocast_dtype):
                 out = m.render(self.rays_o, self.rays_d, **self.render_kwargs)
                 loss = self.loss_fn(out, self.target)
+            self.image = self._image_of(out)
             self._scaled(loss).backward()
         finally:
             m._buffers['step_counter'], m.mean_count, m.local_step = saved_counter, saved_mc, saved_ls
         return loss
+
+    @staticmethod
+    def _image_of(out):
+        """the [N,3] image of a render's results as `self.image` holds it: detached, no launch where the renderer returns fp32 (it does)"""
+        return out['image'].detach().reshape(-1, 3).float()
 
     def _geo_loss_needs_direct(self):
         """a geo_loss is served by the autograd-free iteration alone: raise where the graphs about to be captured would leave it out"""
@@ -479,6 +490,7 @@ class GraphedTrainStep:
         import gc
         self.graphs = None
         self.loss = None
+        self.image = None
         gc.collect()  # drop autograd graphs of earlier eager iterations (their AccumulateGrad nodes are stream-bound)
         torch.cuda.synchronize()
         _drain_parked()
@@ -497,6 +509,7 @@ class GraphedTrainStep:
                 self.optimizer.enable_table_fusion(emb)
                 self.table_fused = True
         self.la = None
+        self.la_image = None
         self.la_ready = [None, None]
         if self.lookahead and self._direct_ok():
             self._capture_lookahead()
@@ -526,7 +539,8 @@ class GraphedTrainStep:
             with _capture_into(ga):
                 march()
             with _capture_into(gb, pool=ga.pool()):
-                self.loss = rest()[0][0].detach()
+                out = rest()
+                self.loss, self.image = out[0][0].detach(), out[1]
                 if not self._checked_ok:
                     opt.pre_reduce_check()     # (else the kernels that deposited the local gradients flagged them)
                 opt.poison_shards()            # found_inf -> NaN in element 0 of every shard: the reduce-scatter carries the verdict
@@ -561,7 +575,7 @@ class GraphedTrainStep:
         if sharded:
             opt.wait_shadows()
             torch.cuda.synchronize()
-        la, lists = [], []
+        la, lists, images = [], [], []
         for p in range(2):
             args, kwargs = self._iteration_args(self._checked_ok, p)   # (a sharded update has no fused table: it needs averager=None)
             march, rest = fused_train_iteration_split(*args, **kwargs)
@@ -570,7 +584,8 @@ class GraphedTrainStep:
                 march()
             with _capture_into(gr, pool=pool_rest), (contextlib.nullcontext() if sharded else self._recording(lists)):
                 opt.zero_grad(set_to_none=True)
-                loss = rest()[0][0].detach()
+                out = rest()
+                loss, image = out[0][0].detach(), out[1]
                 if not sharded:
                     self._iteration_back()
                 else:
@@ -582,12 +597,14 @@ class GraphedTrainStep:
                         opt.apply(zero=not self._overwrites_table())
                         opt.gather_shadows(async_op=False)   # same stream: no fork inside the graph
             la.append((gm, gr, loss, march, rest))   # (the closures keep the marched buffers alive)
+            images.append(image)
         self.la_apply = None
         if sharded and not self.graph_collectives:
             self.la_apply = torch.cuda.CUDAGraph()
             with _capture_into(self.la_apply, pool=pool_rest):
                 opt.apply(zero=not self._overwrites_table())
         self.la = la
+        self.la_image = images   # per set: the static image buffer its rest chain writes
         self.graphs = tuple(g for e in la for g in e[:2])
         self.lists = tuple(lists) or None
         where = MARCH_MARKS[self.march_at]
@@ -694,6 +711,7 @@ class GraphedTrainStep:
             else:   # the same term through autograd (the steps before the sample estimate exists)
                 out = self.model.render(rays_o, rays_d, **dict(self.render_kwargs, geo=True))
                 loss = self.loss_fn(out, target) + geo.lambda_distortion * out['distortion'].float().mean()
+        self.image = self._image_of(out)
         self._scaled(loss).backward()
         if self.averager is not None and not getattr(self.optimizer, 'shard', False):
             self.averager.all_reduce()
@@ -715,6 +733,9 @@ class GraphedTrainStep:
         m = self.model
         p = self.la_cur
         gm, gr, loss = self.la[p][:3]
+        images = getattr(self, 'la_image', None)
+        if images is not None:
+            self.image = images[p]   # (this set's static image buffer: written by the rest chain replayed below)
         main = torch.cuda.current_stream()
         ready = self.la_ready[p]
         hit = self._announced(ready, rays_o, rays_d, self.occupancy_epoch)
@@ -790,7 +811,8 @@ class GraphedTrainStep:
         return loss
 
     def step(self, rays_o, rays_d, target, next_rays=None):
-        """one training iteration on rays_o/rays_d [1,N,3], target [N,3]; returns the (device) loss of this step.
+        """one training iteration on rays_o/rays_d [1,N,3], target [N,3]; returns the (device) loss of this step.  Afterwards `self.image` is
+        the step's finished [N,3] fp32 image (a view of a static buffer: valid until the next step()).
         next_rays=(rays_o, rays_d[, target]) of the FOLLOWING step (lookahead=True only): marched (and, with the target, staged) on a side
         stream under this iteration; the following step recognises the batch by the identity of these tensors."""
         m = self.model

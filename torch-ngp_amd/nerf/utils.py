@@ -6,6 +6,10 @@ direction, normalisation, camera-to-world rotation, origin broadcast: eight elem
 kernel (ngp_rays_from_pixels) that writes the [B,N,3] outputs directly, optionally into caller-provided buffers (`out=`), e.g. the static
 input buffers of graph.GraphedTrainStep.
 
+Error-map sampling on the device (extension): `get_rays(..., error_map=, seed=)` draws the pixels with ngp_error_map_draw --
+the same weighted draw without replacement, one launch, no torch generator -- and `ErrorMaps` keeps the per-image maps and applies the
+Trainer's EMA update (ngp_error_map_update).  `seed=None` is the torch path above, unchanged.
+
 SURVEY.md 8(f).4.  Fails loudly without the HIP library: there is no CPU fallback."""
 import torch
 
@@ -35,10 +39,77 @@ def _draw_pixels(B, H, W, N, error_map, patch_size, device):
     return rows * W + cols, coarse
 
 
+def _seed_words(seed):
+    """(host word, device word or None) of a `seed=` argument: a Python int, or a one-word CUDA tensor the kernel reads itself (int32, e.g.
+    optimizer.scalars[STEP_COUNT:STEP_COUNT + 1] -- the word `noise_seed` uses; any 4-byte dtype: the bits are the seed)"""
+    if torch.is_tensor(seed):
+        if not (seed.is_cuda and seed.numel() == 1 and seed.element_size() == 4):
+            raise RuntimeError('error-map draw: a tensor seed must be a one-element 4-byte CUDA tensor (int32)')
+        return 0, seed
+    return int(seed) & 0xffffffff, None
+
+
+def draw_error_map(error_map, H, W, N, seed, res=128, keys_out=None, n_drawable=None):
+    """Extension: N distinct cells per image of error_map [B, res * res] (fp32, CUDA), drawn without replacement proportional
+    to the map, refined to pixels of the H x W frame -- ngp_error_map_draw: one launch, no torch generator, the same outputs for the same
+    (map, seed).  -> (inds [B,N], inds_coarse [B,N]) int64, ascending cell order.  keys_out [B, res * res] fp32 / n_drawable [B] int32:
+    optional tensors that receive every cell's race key / the number of cells with a finite positive weight."""
+    if not error_map.is_cuda:
+        raise RuntimeError('error-map draw: error_map must be a CUDA tensor (the MI355X build has no CPU path)')
+    if error_map.dim() != 2 or error_map.shape[1] != res * res:
+        raise RuntimeError(f'error-map draw: error_map must be [B, {res * res}] for res={res} (got {tuple(error_map.shape)})')
+    em = error_map.float().contiguous()
+    B = em.shape[0]
+    word, word_dev = _seed_words(seed)
+    inds = torch.empty(B, N, dtype=torch.int64, device=em.device)
+    coarse = torch.empty(B, N, dtype=torch.int64, device=em.device)
+    capi.check(capi.lib.ngp_error_map_draw(em.data_ptr(), B, int(res), int(N), int(H), int(W), word, capi.ptr(word_dev), inds.data_ptr(),
+                                           coarse.data_ptr(), capi.ptr(keys_out), capi.ptr(n_drawable), capi.stream()))
+    return inds, coarse
+
+
+class ErrorMaps:
+    """Extension: the per-image error maps of the reference's `--error_map` training (provider.py: torch.ones([n_images,
+    128 * 128]); Trainer.train_step: 0.1 / 0.9 EMA of the per-ray squared error at the drawn cells), kept on the device and served by the
+    two kernels of csrc/error_map.hip.  `.maps` [n_images, res * res] fp32 is a plain tensor: save and load it as one.
+
+        inds, coarse = maps.draw(i, H, W, N, seed)                    # or get_rays(..., error_map=maps.maps[i:i + 1], seed=seed)
+        ... get_rays(out=...) / pose_rays, stepper.step(...) ...
+        maps.update(i, coarse, stepper.image, target)
+
+    With GraphedTrainStep.step(next_rays=) the following batch is drawn before this update: it sees a map that is one step stale."""
+
+    def __init__(self, n_images, device, res=128):
+        if not 1 <= int(res) <= 128:
+            raise ValueError('ErrorMaps: res must be in [1, 128]')
+        self.res = int(res)
+        self.maps = torch.ones(int(n_images), self.res * self.res, dtype=torch.float32, device=device)
+
+    def draw(self, index, H, W, N, seed):
+        """-> (inds [1,N], inds_coarse [1,N]) int64 for image `index`"""
+        return draw_error_map(self.maps[index:index + 1], H, W, N, seed, res=self.res)
+
+    @torch.no_grad()
+    def update(self, index, inds_coarse, image, target, keep=0.1, take=0.9):
+        """maps[index, c] = keep * maps[index, c] + take * mean_k (image - target)^2 at the rays' cells c = inds_coarse, in place (one launch);
+        image, target [N,3] fp32 (e.g. GraphedTrainStep.image and the step's target)"""
+        row = self.maps[index]
+        n = inds_coarse.numel()
+        for t, name in ((image, 'image'), (target, 'target')):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 3 * n):
+                raise RuntimeError(f'ErrorMaps.update: {name} must be a contiguous float32 CUDA tensor of N*3 elements')
+        if not (inds_coarse.is_cuda and inds_coarse.dtype == torch.int64 and inds_coarse.is_contiguous()):
+            raise RuntimeError('ErrorMaps.update: inds_coarse must be a contiguous int64 CUDA tensor')
+        capi.check(capi.lib.ngp_error_map_update(row.data_ptr(), inds_coarse.data_ptr(), image.data_ptr(), target.data_ptr(), n, row.numel(),
+                                                 float(keep), float(take), capi.stream()))
+
+
 @torch.no_grad()
-def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, out=None):
+def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, out=None, seed=None, res=128):
     """poses [B,4,4] cam2world (CUDA, fp32), intrinsics (fx, fy, cx, cy).  `out=(rays_o, rays_d)`: optional contiguous fp32 [B,n,3]
-    tensors to fill (extension)."""
+    tensors to fill (extension).  `seed=` (extension; with an error_map and patch_size 1): a Python int or a one-word int32 CUDA tensor --
+    the pixels come from ngp_error_map_draw (draw_error_map above: no torch generator, `res` x `res` map) instead of torch.multinomial;
+    None keeps the torch path."""
     if not poses.is_cuda:
         raise RuntimeError('get_rays: poses must be a CUDA tensor (the MI355X build has no CPU path)')
     poses = poses.float().contiguous()
@@ -47,7 +118,10 @@ def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, out=No
     results = {}
     if N > 0:
         N = min(N, H * W)
-        inds, coarse = _draw_pixels(B, H, W, N, error_map, patch_size, poses.device)
+        if seed is not None and error_map is not None and patch_size <= 1:
+            inds, coarse = draw_error_map(error_map.to(poses.device), H, W, N, seed, res=res)
+        else:
+            inds, coarse = _draw_pixels(B, H, W, N, error_map, patch_size, poses.device)
         n = inds.shape[-1]
         shared = inds.dim() == 1
         inds = inds.contiguous()
