@@ -522,6 +522,31 @@ uint32_t ngp_ffmlp_backward_slab_count(uint32_t B, uint32_t input_dim, uint32_t 
 int ngp_ffmlp_reduce_slabs_pair(const void* slabs_a, uint32_t n_slabs_a, uint32_t n_params_a, void* grad_weights_a, const void* slabs_b,
                                 uint32_t n_slabs_b, uint32_t n_params_b, void* grad_weights_b, float* found_inf, ngp_stream_t stream);
 
+/* The row bound of the training chain (additive: the ABI version stays).  The training march publishes a device word -- word 0 of its
+ * workspace (ngp_march_rays_train_workspace_bytes), the end of the written row prefix -- and the per-sample kernels behind it, launched for
+ * the M rows of their buffers, then work on the rows [0, live) only:
+ *     live = min(M, *rows_dev rounded up to a multiple of 512)
+ * (512 = the record sort's chunk, a multiple of the MLP tile; ONE rule, csrc/common.h live_rows).  M stays the stride of every buffer and of
+ * the workspaces; output rows >= live are NOT written, input rows >= live are not read.  The rows [*rows_dev, live) must be defined: the
+ * march zeroes their positions, directions and deltas, the fused compositor their gradients (a zero gradient times an undefined activation
+ * would be NaN).  The word is read on the device when a kernel runs: a captured graph or a command list follows the march of the step it
+ * replays.
+ * ngp_training_row_bound(rows_dev) ARMS the bound on the calling thread; it stays armed until ngp_training_row_bound(NULL).  The signatures
+ * of the entries stay what they are (callers, and tools that wrap an entry by its name, see the same calls).  While it is armed, calls on
+ * that thread of
+ *   ngp_grid_encode_forward_sched / _sel  (fp16 / fp32, no dy_dx; _sel's own rows_dev -- an EXACT count, the eval march publishes it padded --
+ *                                         wins when given)
+ *   ngp_network_forward / _rows           (likewise: its own rows_dev wins)
+ *   ngp_network_backward_color
+ *   ngp_ffmlp_backward_ex                 (served by the paired kernel: register-resident 2- / 3-layer nets without NGP_FF_SINGLE_WAVE /
+ *                                         NGP_FF_LAYERED; refused otherwise -- NGP_ERR_INVALID, nothing launched.  A workgroup without live
+ *                                         tiles still leaves its all-zero slab: the slab count follows M)
+ *   ngp_grid_encode_backward_checked_slabs (record sort, slice accumulate -- the flush of every slice, the table's Adam sweep and the carried
+ *                                         reductions run whatever the bound, 0 included -- and the atomic levels; refused with dy_dx /
+ *                                         grad_inputs)
+ * take it; every other entry, and every call while nothing is armed, is unchanged. */
+int ngp_training_row_bound(const uint32_t* rows_dev);
+
 /* network_ff.py:55-72 between the two MLPs: h16 [M,16] fp16 (sigma-net output), dirs [M_valid,3] fp32 ->
  * sigma [M] fp32 = exp(h[:,0]) (trunc_exp), color_in [M,32] fp16 = [SH deg 4 | h[:,1:16] | 0]; rows >= M_valid use dir = 0 */
 int ngp_pipeline_mid_forward(const void* h16, const float* dirs, float* sigma, void* color_in, uint32_t M, uint32_t M_valid,

@@ -105,6 +105,8 @@ _SIGNATURES = {
     'ngp_network_forward': [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     'ngp_network_forward_rows': [_vp, _vp, _u32, _u32, _vp, _vp, _u32, _u32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp],
     'ngp_march_rays_dev_rows': [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp],
+    # arms / disarms (NULL) the row bound of the training chain on the calling thread (include/ngp_hip.h; `row_bound` below)
+    'ngp_training_row_bound': [_vp],
     'ngp_pipeline_mid_forward': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp],
     'ngp_pipeline_rgb_forward': [_vp, _vp, _u32, _vp],
     'ngp_pipeline_rgb_backward': [_vp, _vp, _vp, _u32, _vp],
@@ -218,6 +220,24 @@ def check(rc):
     """Raise RuntimeError with the library's message when a call failed."""
     if rc != 0:
         raise RuntimeError(lib.ngp_last_error().decode('utf-8', 'replace'))
+
+
+class row_bound:
+    """`with row_bound(ws):` -- the launches issued inside work on the rows the march filled (ngp_training_row_bound: word 0 of the march
+    workspace `ws`, rounded up to 512); `ws` None: nothing is armed.  Disarmed on the way out, whatever happened inside."""
+
+    def __init__(self, ws):
+        self.ws = ws
+
+    def __enter__(self):
+        if self.ws is not None:
+            check(lib.ngp_training_row_bound(self.ws.data_ptr()))
+        return self
+
+    def __exit__(self, *exc):
+        if self.ws is not None:
+            lib.ngp_training_row_bound(None)
+        return False
 
 
 class SlabSets(ctypes.Structure):

@@ -206,7 +206,25 @@ struct TableSel {
     const _Float16* alt;
     const float* parity;
     const uint32_t* rows;   // optional device word: only the first min(B, *rows) points carry work (the eval loop's emitted-row count)
+    bool rows_live;         // the word is the training march's: the first live_rows(B, *rows) points carry work (below)
+    __device__ __forceinline__ uint32_t work_rows(uint32_t B) const;
 };
+
+// ---- THE row bound of the training chain (include/ngp_hip.h, ngp_training_row_bound): a launch sized for the M rows of its sample buffers
+// works on the rows [0, live) only, live = min(M, word rounded up to LIVE_GRANULE), word = the device word the march published (word 0 of
+// its workspace: the end of the written row prefix).  512 is the record sort's chunk and a multiple of every other granule (MLP tile 32,
+// M % 128 == 0), so every bounded kernel sees whole units.  The rows [word, live) are defined zero rows: the march zeroes their positions,
+// the compositor their gradients.  rows == NULL: no bound (live = M).
+// Where the word comes from: ngp_training_row_bound() arms it on the calling thread and the entries of the chain pick it up
+// (armed_row_bound(), runtime.cpp) -- their signatures, and with them everything that wraps them by name, stay as they are.
+const uint32_t* armed_row_bound();
+constexpr uint32_t LIVE_GRANULE = 512;
+__host__ __device__ __forceinline__ uint32_t live_rows(uint32_t M, uint32_t word) {
+    const uint32_t up = word > M ? M : (word + (LIVE_GRANULE - 1u)) & ~(LIVE_GRANULE - 1u);   // (word <= M <= 2^32 - 512 here: no wrap)
+    return up < M ? up : M;
+}
+__device__ __forceinline__ uint32_t live_rows(uint32_t M, const uint32_t* __restrict__ rows) { return rows ? live_rows(M, rows[0]) : M; }
+__device__ __forceinline__ uint32_t TableSel::work_rows(uint32_t B) const { return !rows ? B : rows_live ? live_rows(B, rows[0]) : min(B, rows[0]); }
 
 // ---- fixed-order sum of per-workgroup fp32 weight-gradient slabs (the FFMLP backward's deferred reduction), TWO sets per launch ----
 // One block of RS_PARAMS x RS_GROUPS threads sums RS_PARAMS parameters of one set: group g adds slabs g, g + RS_GROUPS, ..., the groups'

@@ -450,12 +450,15 @@ __global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(NT =
     const half_t* __restrict__ enc, bool enc_planar, const float* __restrict__ dirs, uint32_t M_valid, const half_t* __restrict__ w_sigma,
     const half_t* __restrict__ w_color, half_t* __restrict__ fb_s, half_t* __restrict__ h16, float* __restrict__ sigma,
     half_t* __restrict__ color_in, half_t* __restrict__ fb_c, float* __restrict__ rgb, uint32_t n_tiles_cap, uint32_t nl_s, uint32_t nl_c,
-    float density_scale, const uint32_t* __restrict__ rows_dev) {
+    float density_scale, const uint32_t* __restrict__ rows_dev, bool rows_live) {
     constexpr int WIDTH = 64, NIB = 2, NKB = 4;
     constexpr uint32_t in_kb = 2;  // both networks take 32 inputs
     // n_tiles_cap: the buffers' rows / 32 (strides of the planar input and of the stored activations); n_tiles: the tiles that carry work --
-    // all of them, or (rows_dev: the eval loop's device-side count of emitted rows) the first ceil(*rows_dev / 32)
-    const uint32_t n_tiles = rows_dev ? min(n_tiles_cap, (rows_dev[0] + (uint32_t)FF_TILE - 1u) / (uint32_t)FF_TILE) : n_tiles_cap;
+    // all of them, or (rows_dev: the eval loop's device-side count of emitted rows) the first ceil(*rows_dev / 32), or (rows_live: the word
+    // is the training march's) the tiles of the row bound (common.h: live_rows)
+    const uint32_t n_tiles = !rows_dev ? n_tiles_cap
+                             : rows_live ? live_rows(n_tiles_cap * (uint32_t)FF_TILE, rows_dev[0]) / (uint32_t)FF_TILE
+                                         : min(n_tiles_cap, (rows_dev[0] + (uint32_t)FF_TILE - 1u) / (uint32_t)FF_TILE);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half8_t* img_s = reinterpret_cast<half8_t*>(smem);
     const uint32_t frags_s = NIB * in_kb + (nl_s - 1) * NIB * NKB + NKB;
@@ -1288,8 +1291,13 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
                              const half_t* __restrict__ forward_buffer, uint32_t n_tiles, uint32_t in_dim, uint32_t num_layers, uint32_t act,
                              bool with_dx, half_t* __restrict__ grad_inputs, float* __restrict__ slabs,
                              half_t* __restrict__ grad_weights_direct, bool in_planar, bool dx_planar, uint32_t pf_depth, MidEpilogue mid,
-                             uint32_t lds_bytes, bool serial_flush) {
+                             uint32_t lds_bytes, bool serial_flush, const uint32_t* __restrict__ rows_dev) {
     static_assert(NHM == 1 || NHM == 2, "the paired backward covers 2- and 3-layer networks");
+    // n_tiles: the buffers' rows / 32 -- the strides (layer_stride, the planar rows, the slab addressing).  n_live: the tiles that carry work,
+    // all of them or (rows_dev, common.h: live_rows) the tiles of the row bound: the tile loops of both roles, every prefetch guard and the
+    // choice of the counted wait follow it.  A workgroup whose stream is empty still runs the epilogue and leaves its all-zero slab
+    static_assert(LIVE_GRANULE % FF_TILE == 0, "the row bound is a whole number of tiles");
+    const uint32_t n_live = live_rows(n_tiles * (uint32_t)FF_TILE, rows_dev) / (uint32_t)FF_TILE;
     constexpr int NIB = Shape<WIDTH>::NIB, NKB = Shape<WIDTH>::NKB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     half8_t* img = reinterpret_cast<half8_t*>(smem);
@@ -1324,7 +1332,7 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
     // the weight images are built (the tile buffers are a region of their own): their round trip runs under the build instead of behind it.
     if (role == 0) {
         for (uint32_t d = 0; d + 1 < (pf_depth > 1 ? pf_depth : 2u); d++)
-            if (blockIdx.x * FP_PAIRS + d * base_step + pair < n_tiles) prefetch(d, blockIdx.x * FP_PAIRS + d * base_step + pair);
+            if (blockIdx.x * FP_PAIRS + d * base_step + pair < n_live) prefetch(d, blockIdx.x * FP_PAIRS + d * base_step + pair);
     }
     build_backward_image<WIDTH>(img, weights, in_dim, num_layers, with_dx);
     if (RECOMP) build_forward_image<WIDTH>(img + (size_t)nfrag * 64, weights, in_dim, num_layers, 0, ffrag);
@@ -1343,7 +1351,7 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
         if (role == 0) {
             // a tile that does not exist was not requested: its slot in the queue is missing, so only the oldest request may be waited for
             // by count while a full set of younger ones exists
-            if (deep && base + base_step + pair < n_tiles) {
+            if (deep && base + base_step + pair < n_live) {
                 switch (tile_loads) {
                     case 3u: wait_vmcnt<3>(); break;     // recomputing, 32 row-major inputs
                     case 9u: wait_vmcnt<9>(); break;     // recomputing, 32 planar inputs
@@ -1360,14 +1368,14 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
             const uint32_t ahead = pf_depth - 1;
             const uint32_t fill = cur == 0 ? pf_depth - 1 : cur - 1;   // the buffer of the round before this one: both roles are done with it
             cur = cur + 1 == pf_depth ? 0u : cur + 1;
-            if (role == 0 && base + ahead * base_step + pair < n_tiles) prefetch(fill, base + ahead * base_step + pair);
+            if (role == 0 && base + ahead * base_step + pair < n_live) prefetch(fill, base + ahead * base_step + pair);
         }
         return tb;
     };
     auto end_of_round = [&](uint32_t base) {  // single buffer: refill only after both roles are done with it
         if (pf_depth == 1) {
             __syncthreads();
-            if (role == 0 && base + base_step + pair < n_tiles) prefetch(0, base + base_step + pair);
+            if (role == 0 && base + base_step + pair < n_live) prefetch(0, base + base_step + pair);
         }
     };
     float* red = reinterpret_cast<float*>(smem);
@@ -1394,9 +1402,9 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
         for (int ib = 0; ib < NIB; ib++)
 #pragma unroll
             for (int jb = 0; jb < NIB; jb++) gw_top[ib][jb] = zero16();
-        for (uint32_t base = blockIdx.x * FP_PAIRS; base < n_tiles; base += base_step) {
+        for (uint32_t base = blockIdx.x * FP_PAIRS; base < n_live; base += base_step) {
             const unsigned char* tb = next_tile_buffer(base);
-            if (base + pair < n_tiles) {
+            if (base + pair < n_live) {
                 const half8_t* tfrag = reinterpret_cast<const half8_t*>(tb) + lane;
                 const half8_t dy = tfrag[0];
                 half8_t a_top[NKB], a_below[NKB];
@@ -1470,10 +1478,10 @@ void k_ffmlp_backward_paired(const half_t* __restrict__ grad, const half_t* __re
 #pragma unroll
                 for (int jb = 0; jb < NIB; jb++) gw_low[ib][jb] = zero16();
         }
-        for (uint32_t base = blockIdx.x * FP_PAIRS; base < n_tiles; base += base_step) {
+        for (uint32_t base = blockIdx.x * FP_PAIRS; base < n_live; base += base_step) {
             const unsigned char* tb = next_tile_buffer(base);
             const uint32_t tile = base + pair;
-            if (tile < n_tiles) {
+            if (tile < n_live) {
                 const half8_t* tfrag = reinterpret_cast<const half8_t*>(tb) + lane;
                 const half8_t dy = tfrag[0];
                 half8_t a_prev[NKB];
@@ -2139,7 +2147,7 @@ static int launch_and_reduce(const void* kern, size_t lds, uint32_t blocks, bool
 template <int WIDTH, int IN_JB, int NHM, bool RELU>
 static int launch_backward_t(const void* grad, const void* inputs, const void* weights, const void* fwd, uint32_t B, uint32_t in_dim,
                            uint32_t num_layers, uint32_t act, bool with_dx, void* backward_buffer, void* grad_inputs,
-                           void* grad_weights, uint32_t flags, hipStream_t st, const MidEpilogue* mid_in) {
+                           void* grad_weights, uint32_t flags, hipStream_t st, const MidEpilogue* mid_in, const uint32_t* rows_dev) {
     const bool in_planar = (flags & NGP_FF_INPUT_PLANAR) != 0, dx_planar = (flags & NGP_FF_DX_PLANAR) != 0;
     const bool defer = (flags & NGP_FF_DEFER_REDUCE) != 0, serial = (flags & NGP_FF_SERIAL_FLUSH) != 0;
     const MidEpilogue mid = mid_in ? *mid_in : MidEpilogue{nullptr, nullptr, nullptr, 0.0f};
@@ -2159,7 +2167,7 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             return launch_and_reduce(reinterpret_cast<const void*>(pk), lds_r.total, blocks, defer, backward_buffer, grad_weights, n_params, st,
                                      [&](dim3 grid, float* slabs, half_t* direct) {
                 NGP_LAUNCH(pk, grid, dim3(FP_THREADS), lds_r.total, st, g, x, w, (const half_t*)nullptr, n_tiles, in_dim, num_layers, act, with_dx,
-                                   (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds_r.pf_depth, mid, (uint32_t)lds_r.total, serial);
+                                   (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds_r.pf_depth, mid, (uint32_t)lds_r.total, serial, rows_dev);
             });
         } else {
             NGP_REQUIRE(false, NGP_ERR_INVALID, "ffmlp_backward: NGP_FF_RECOMPUTE serves 64-wide ReLU networks with 32 inputs and 2 or 3 layers");
@@ -2172,11 +2180,11 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
             return launch_and_reduce(reinterpret_cast<const void*>(pk), lds.total, blocks, defer, backward_buffer, grad_weights, n_params, st,
                                      [&](dim3 grid, float* slabs, half_t* direct) {
                 NGP_LAUNCH(pk, grid, dim3(FP_THREADS), lds.total, st, g, x, w, (const half_t*)fwd, n_tiles, in_dim, num_layers, act, with_dx,
-                                   (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds.pf_depth, mid, (uint32_t)lds.total, serial);
+                                   (half_t*)grad_inputs, slabs, direct, in_planar, dx_planar, lds.pf_depth, mid, (uint32_t)lds.total, serial, rows_dev);
             });
         }
     }
-    NGP_REQUIRE(!mid.grad_sigma && !defer, NGP_ERR_INVALID, "ffmlp_backward: this extension needs the paired kernel (2 or 3 layers)");
+    NGP_REQUIRE(!mid.grad_sigma && !defer && !rows_dev, NGP_ERR_INVALID, "ffmlp_backward: this extension needs the paired kernel (2 or 3 layers)");
     auto kern = k_ffmlp_backward<WIDTH, IN_JB, NHM, RELU>;
     return launch_and_reduce(reinterpret_cast<const void*>(kern), lds.total, blocks, false, backward_buffer, grad_weights, n_params, st,
                              [&](dim3 grid, float* slabs, half_t* direct) {
@@ -2188,12 +2196,13 @@ static int launch_backward_t(const void* grad, const void* inputs, const void* w
 template <int WIDTH, int IN_JB, int NHM>
 static int launch_backward(const void* grad, const void* inputs, const void* weights, const void* fwd, uint32_t B, uint32_t in_dim,
                            uint32_t num_layers, uint32_t act, bool with_dx, void* backward_buffer, void* grad_inputs,
-                           void* grad_weights, uint32_t flags, hipStream_t st, const MidEpilogue* mid = nullptr) {
+                           void* grad_weights, uint32_t flags, hipStream_t st, const MidEpilogue* mid = nullptr,
+                           const uint32_t* rows_dev = nullptr /* optional row bound (common.h: live_rows): the paired kernel only */) {
     if (act == ACT_RELU)
         return launch_backward_t<WIDTH, IN_JB, NHM, true>(grad, inputs, weights, fwd, B, in_dim, num_layers, act, with_dx, backward_buffer,
-                                                          grad_inputs, grad_weights, flags, st, mid);
+                                                          grad_inputs, grad_weights, flags, st, mid, rows_dev);
     return launch_backward_t<WIDTH, IN_JB, NHM, false>(grad, inputs, weights, fwd, B, in_dim, num_layers, act, with_dx, backward_buffer,
-                                                       grad_inputs, grad_weights, flags, st, mid);
+                                                       grad_inputs, grad_weights, flags, st, mid, rows_dev);
 }
 
 }  // namespace ngp
@@ -2242,13 +2251,18 @@ extern "C" size_t ngp_ffmlp_backward_workspace_bytes(uint32_t B, uint32_t input_
     return (size_t)WG_MAX_CHUNKS * SlabLayout{hidden_dim, input_dim, num_layers}.n_params() * sizeof(float);
 }
 
-extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, uint32_t B,
-                                     uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation,
-                                     uint32_t output_activation, int calc_grad_inputs, void* backward_buffer, void* grad_inputs,
-                                     void* grad_weights, uint32_t flags, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
-    (void)output_activation;  // the reference discards it as well (ffmlp.cu:780)
+// rows_dev (optional row bound, common.h: live_rows): served by the paired kernel (register-resident 2- / 3-layer networks without
+// NGP_FF_SINGLE_WAVE / NGP_FF_LAYERED); every other kernel refuses it before anything is launched
+static int ffmlp_backward_impl(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, uint32_t B,
+                               uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation,
+                               int calc_grad_inputs, void* backward_buffer, void* grad_inputs, void* grad_weights, uint32_t flags, void* workspace,
+                               size_t workspace_bytes, const uint32_t* rows_dev, ngp_stream_t stream) {
     int rc = check_ff_args("ffmlp_backward", B, input_dim, output_dim, hidden_dim, num_layers);
     if (rc) return rc;
+    NGP_REQUIRE(!rows_dev || (ff_register_resident(input_dim, hidden_dim, num_layers) && num_layers <= 3 &&
+                              !(flags & (NGP_FF_LAYERED | NGP_FF_SINGLE_WAVE))),
+                NGP_ERR_INVALID, "ffmlp_backward: the row bound needs the paired kernel (a register-resident network of 2 or 3 layers, neither "
+                                 "NGP_FF_LAYERED nor NGP_FF_SINGLE_WAVE)");
     if (B == 0) {
         // an empty batch: no kernel runs, but the caller's weight gradient must still be what the sum over zero samples is (callers hand
         // over uninitialised memory: every other path OVERWRITES it) -- ADVICE r5.  (With NGP_FF_DEFER_REDUCE the later reduction writes it.)
@@ -2274,7 +2288,7 @@ extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const
     }
     const uint32_t in_jb = (input_dim + 31) / 32;
 #define FF_BWD(W, J, N) \
-    return launch_backward<W, J, N>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, activation, dx, backward_buffer, grad_inputs, grad_weights, flags, st)
+    return launch_backward<W, J, N>(grad, inputs, weights, forward_buffer, B, input_dim, num_layers, activation, dx, backward_buffer, grad_inputs, grad_weights, flags, st, nullptr, rows_dev)
 #define FF_BWD_N(W, J)                      \
     switch (num_layers - 1) {               \
         case 1: FF_BWD(W, J, 1);            \
@@ -2291,12 +2305,23 @@ extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const
 #undef FF_BWD
 }
 
+extern "C" int ngp_ffmlp_backward_ws(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, uint32_t B,
+                                     uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation,
+                                     uint32_t output_activation, int calc_grad_inputs, void* backward_buffer, void* grad_inputs,
+                                     void* grad_weights, uint32_t flags, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
+    (void)output_activation;  // the reference discards it as well (ffmlp.cu:780)
+    return ffmlp_backward_impl(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim, num_layers, activation, calc_grad_inputs,
+                               backward_buffer, grad_inputs, grad_weights, flags, workspace, workspace_bytes, nullptr, stream);
+}
+
 extern "C" int ngp_ffmlp_backward_ex(const void* grad, const void* inputs, const void* weights, const void* forward_buffer, uint32_t B,
                                      uint32_t input_dim, uint32_t output_dim, uint32_t hidden_dim, uint32_t num_layers, uint32_t activation,
                                      uint32_t output_activation, int calc_grad_inputs, void* backward_buffer, void* grad_inputs,
                                      void* grad_weights, uint32_t flags, ngp_stream_t stream) {
-    return ngp_ffmlp_backward_ws(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim, num_layers, activation,
-                                 output_activation, calc_grad_inputs, backward_buffer, grad_inputs, grad_weights, flags, nullptr, 0, stream);
+    (void)output_activation;
+    // (the MLP backward entry that takes the row bound armed on the thread, ngp_training_row_bound)
+    return ffmlp_backward_impl(grad, inputs, weights, forward_buffer, B, input_dim, output_dim, hidden_dim, num_layers, activation, calc_grad_inputs,
+                               backward_buffer, grad_inputs, grad_weights, flags, nullptr, 0, armed_row_bound(), stream);
 }
 
 
@@ -2323,6 +2348,7 @@ extern "C" int ngp_network_backward_color(const void* grad_out16, const void* co
                                           uint32_t M, uint32_t num_layers_color, void* backward_buffer, const float* grad_sigma,
                                           const void* h16, float density_scale, void* grad_h16, void* grad_w_color, uint32_t flags,
                                           ngp_stream_t stream) {
+    const uint32_t* rows_dev = armed_row_bound();   // (ngp_training_row_bound)
     NGP_REQUIRE(num_layers_color == 2 || num_layers_color == 3, NGP_ERR_INVALID,
                 "network_backward_color: 2 or 3 layers (got %u); use ngp_ffmlp_backward_ex + ngp_pipeline_mid_backward", num_layers_color);
     NGP_REQUIRE(!(flags & ~(NGP_FF_DEFER_REDUCE | NGP_FF_RECOMPUTE | NGP_FF_SERIAL_FLUSH)), NGP_ERR_INVALID,
@@ -2336,9 +2362,9 @@ extern "C" int ngp_network_backward_color(const void* grad_out16, const void* co
     const MidEpilogue mid{grad_sigma, (const half_t*)h16, (half_t*)grad_h16, density_scale};
     if (num_layers_color == 2)
         return launch_backward<64, 1, 1>(grad_out16, color_in, w_color, forward_buffer_color, M, 32, 2, ACT_RELU, true, backward_buffer, nullptr,
-                                         grad_w_color, flags, as_stream(stream), &mid);
+                                         grad_w_color, flags, as_stream(stream), &mid, rows_dev);
     return launch_backward<64, 1, 2>(grad_out16, color_in, w_color, forward_buffer_color, M, 32, 3, ACT_RELU, true, backward_buffer, nullptr,
-                                     grad_w_color, flags, as_stream(stream), &mid);
+                                     grad_w_color, flags, as_stream(stream), &mid, rows_dev);
 }
 
 extern "C" int ngp_network_forward(const void* enc, const float* dirs, uint32_t M, uint32_t M_valid, const void* w_sigma, const void* w_color,
@@ -2349,10 +2375,26 @@ extern "C" int ngp_network_forward(const void* enc, const float* dirs, uint32_t 
                                     forward_buffer_sigma, h16, sigma, color_in, forward_buffer_color, rgb, flags, nullptr, stream);
 }
 
+static int network_forward_impl(const void* enc, const float* dirs, uint32_t M, uint32_t M_valid, const void* w_sigma, const void* w_color,
+                                uint32_t num_layers_sigma, uint32_t num_layers_color, float density_scale, int training,
+                                void* forward_buffer_sigma, void* h16, float* sigma, void* color_in, void* forward_buffer_color,
+                                float* rgb, uint32_t flags, const uint32_t* rows_dev, bool rows_live, ngp_stream_t stream);
+
 extern "C" int ngp_network_forward_rows(const void* enc, const float* dirs, uint32_t M, uint32_t M_valid, const void* w_sigma, const void* w_color,
                                         uint32_t num_layers_sigma, uint32_t num_layers_color, float density_scale, int training,
                                         void* forward_buffer_sigma, void* h16, float* sigma, void* color_in, void* forward_buffer_color,
                                         float* rgb, uint32_t flags, const uint32_t* rows_dev, ngp_stream_t stream) {
+    // its own device count (exact), else the row bound armed on the thread (ngp_training_row_bound: rounded by the rule of common.h)
+    const uint32_t* armed = rows_dev ? nullptr : armed_row_bound();
+    return network_forward_impl(enc, dirs, M, M_valid, w_sigma, w_color, num_layers_sigma, num_layers_color, density_scale, training,
+                                forward_buffer_sigma, h16, sigma, color_in, forward_buffer_color, rgb, flags, armed ? armed : rows_dev, armed != nullptr,
+                                stream);
+}
+
+static int network_forward_impl(const void* enc, const float* dirs, uint32_t M, uint32_t M_valid, const void* w_sigma, const void* w_color,
+                                uint32_t num_layers_sigma, uint32_t num_layers_color, float density_scale, int training,
+                                void* forward_buffer_sigma, void* h16, float* sigma, void* color_in, void* forward_buffer_color,
+                                float* rgb, uint32_t flags, const uint32_t* rows_dev, bool rows_live, ngp_stream_t stream) {
     NGP_REQUIRE(M % 128 == 0, NGP_ERR_INVALID, "network_forward: sample count must be 128 * m, but got %u", M);
     NGP_REQUIRE(num_layers_sigma >= 2 && num_layers_color >= 2, NGP_ERR_INVALID, "network_forward: num_layers should be larger than 2");
     if (M == 0) return NGP_OK;
@@ -2394,11 +2436,11 @@ extern "C" int ngp_network_forward_rows(const void* enc, const float* dirs, uint
     if (training)
         NGP_LAUNCH((k_network_forward<true, TW, TT>), dim3(blocks), dim3(TW * 64), lds, st, (const half_t*)enc, planar, dirs, M_valid, (const half_t*)w_sigma,
                            (const half_t*)w_color, (half_t*)forward_buffer_sigma, (half_t*)h16, sigma, (half_t*)color_in, (half_t*)forward_buffer_color, rgb,
-                           n_tiles, num_layers_sigma, num_layers_color, density_scale, rows_dev);
+                           n_tiles, num_layers_sigma, num_layers_color, density_scale, rows_dev, rows_live);
     else
         NGP_LAUNCH((k_network_forward<false, IW, IT>), dim3(blocks), dim3(IW * 64), lds, st, (const half_t*)enc, planar, dirs, M_valid, (const half_t*)w_sigma,
                            (const half_t*)w_color, (half_t*)nullptr, (half_t*)nullptr, sigma, (half_t*)nullptr, (half_t*)nullptr, rgb, n_tiles,
-                           num_layers_sigma, num_layers_color, density_scale, rows_dev);
+                           num_layers_sigma, num_layers_color, density_scale, rows_dev, rows_live);
     return check_launch("network_forward");
 }
 

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward_pair(const float* 
     NGP_BOUNDS((uint64_t)tile * points_per_block < (uint64_t)B);  // every listed tile holds at least one point
 
     const uint32_t b_begin = tile * points_per_block;
-    const uint32_t B_work = sel.rows ? min(B, sel.rows[0]) : B;   // (device-side row count: the rows behind it carry nothing)
+    const uint32_t B_work = sel.work_rows(B);   // (device-side row count or the training chain's row bound: the rows behind it carry nothing)
     if (b_begin >= B_work) return;
     const uint32_t b_end = min(B_work, b_begin + points_per_block);
     forward_pair_block<T, D, C>(inputs, table, olevel, scale, indexer, hashmap_size, align_corners, interp, im, b_begin, b_end);
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(FWD_THREADS) void k_grid_forward_fast(const float* 
     half_t* __restrict__ olevel = outputs + (size_t)level * B * C;
     NGP_BOUNDS((uint64_t)tile * points_per_block < (uint64_t)B);  // every listed tile holds at least one point
     const uint32_t b_begin = tile * points_per_block;
-    const uint32_t B_work = sel.rows ? min(B, sel.rows[0]) : B;   // (device-side row count: the rows behind it carry nothing)
+    const uint32_t B_work = sel.work_rows(B);   // (device-side row count or the training chain's row bound: the rows behind it carry nothing)
     if (b_begin >= B_work) return;
     const uint32_t b_end = min(B_work, b_begin + points_per_block);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -808,7 +808,8 @@ template <typename T, int D, int C, int MERGE, int THREADS>
 __device__ __forceinline__ void backward_atomic_block(const T* __restrict__ grad, const float* __restrict__ inputs,
                                                       const int32_t* __restrict__ offsets, T* __restrict__ grad_grid, uint32_t B,
                                                       uint32_t level, const GridLevels& lv, uint32_t gridtype, bool align_corners,
-                                                      uint32_t interp, uint32_t points_per_block, InputMap im, uint32_t block_x) {
+                                                      uint32_t interp, uint32_t points_per_block, InputMap im, uint32_t block_x,
+                                                      uint32_t B_live /* rows that carry work (common.h: live_rows); B stays the stride of grad */) {
     constexpr int NJ = 1 << (D - 1);  // corners per lane (all combinations of the coordinates 1..D-1)
     constexpr int CPL = BwdLanes<T, C>::CPL, CL = BwdLanes<T, C>::CL, LPP = BwdLanes<T, C>::LPP, PTS = BwdLanes<T, C>::PTS;
     const uint32_t off0 = (uint32_t)offsets[level];
@@ -824,7 +825,7 @@ __device__ __forceinline__ void backward_atomic_block(const T* __restrict__ grad
     const uint32_t xb = (uint32_t)(lane / CL) & 1u;   // which first-coordinate corner class this lane owns
     const int c0 = (lane % CL) * CPL;                 // first channel this lane owns
     const uint32_t b_begin = block_x * points_per_block;
-    const uint32_t b_end = min(B, b_begin + points_per_block);
+    const uint32_t b_end = min(B_live, b_begin + points_per_block);
 
     for (uint32_t base = b_begin + wid * PTS; base < b_end; base += (THREADS / 64) * PTS) {
         const uint32_t b = base + pl;
@@ -844,9 +845,10 @@ template <typename T, int D, int C, int MERGE>
 __global__ __launch_bounds__(BWD_THREADS) void k_grid_backward(const T* __restrict__ grad, const float* __restrict__ inputs,
                                                                const int32_t* __restrict__ offsets, T* __restrict__ grad_grid,
                                                                uint32_t B, LevelList ll, GridLevels lv, uint32_t gridtype,
-                                                               bool align_corners, uint32_t interp, uint32_t points_per_block, InputMap im) {
+                                                               bool align_corners, uint32_t interp, uint32_t points_per_block, InputMap im,
+                                                               const uint32_t* __restrict__ rows) {
     backward_atomic_block<T, D, C, MERGE, BWD_THREADS>(grad, inputs, offsets, grad_grid, B, ll.level[blockIdx.y], lv, gridtype, align_corners,
-                                                       interp, points_per_block, im, blockIdx.x);
+                                                       interp, points_per_block, im, blockIdx.x, live_rows(B, rows));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1209,7 +1211,11 @@ template <int D, int AMERGE /* run merge of the atomic workgroups (corner_runs):
 __global__ __launch_bounds__(BIN_THREADS) __attribute__((amdgpu_waves_per_eu(BPL == 2 ? NGP_BIN_WAVES_PER_EU : 4, BPL == 2 ? NGP_BIN_WAVES_PER_EU : 4)))
 void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restrict__ inputs, const int32_t* __restrict__ offsets,
                          half_t* __restrict__ grad_grid, uint32_t B, GridLevels lv, uint32_t gridtype, bool align_corners, uint32_t interp,
-                         InputMap im, BinPlan plan, uint32_t* __restrict__ descriptors, uint2* __restrict__ records, AtomicPart ap) {
+                         InputMap im, BinPlan plan, uint32_t* __restrict__ descriptors, uint2* __restrict__ records, AtomicPart ap,
+                         const uint32_t* __restrict__ rows) {
+    // rows (optional device word, common.h: live_rows): the samples [0, B_live) carry work -- the items cover the chunks below
+    // ceil(B_live / 512), the atomic workgroups stop there too; B and plan.n_chunks stay the strides of the gradient, records and descriptors
+    const uint32_t B_live = live_rows(B, rows);
     uint32_t bin_block = blockIdx.x, n_bin_blocks = gridDim.x;
     if (ap.n_blocks) {
         const uint64_t total = gridDim.x;
@@ -1218,7 +1224,7 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
         if (a1 > a0) {  // this workgroup is the a0-th of the atomic kind
             backward_atomic_block<half_t, D, 2, AMERGE, BIN_THREADS>(grad, inputs, offsets, grad_grid, B, ap.levels.level[a0 / ap.blocks_per_level], lv,
                                                                 gridtype, align_corners, interp, ap.points_per_block, im,
-                                                                a0 % ap.blocks_per_level);
+                                                                a0 % ap.blocks_per_level, B_live);
             return;
         }
         bin_block = blockIdx.x - a0;
@@ -1242,7 +1248,7 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
     const uint32_t hrow_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)hrow;
     const uint32_t prow_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)prow;
     const uint32_t n_levels = plan.n_levels;
-    const uint32_t n_items = plan.n_chunks * n_levels;
+    const uint32_t n_items = ((B_live + (uint32_t)BIN_PPB - 1u) / (uint32_t)BIN_PPB) * n_levels;   // (<= plan.n_chunks * n_levels)
     // this workgroup's items: [item, item_end), item = chunk * n_levels + li
     uint32_t item = (uint32_t)(((uint64_t)bin_block * n_items) / n_bin_blocks);
     const uint32_t item_end = (uint32_t)((((uint64_t)bin_block + 1u) * n_items) / n_bin_blocks);
@@ -1268,13 +1274,13 @@ void k_grid_backward_bin(const half_t* __restrict__ grad, const float* __restric
     uint32_t g_cur = 0u, chunk_loaded = 0xffffffffu;
     auto fetch_g = [&](uint32_t chunk_x, uint32_t li) -> uint32_t {
         const uint32_t b = chunk_x * BIN_PPB + (uint32_t)tid;
-        return b < B ? *reinterpret_cast<const uint32_t*>(grad + ((size_t)plan.level(li) * B + b) * C) : 0u;
+        return b < B_live ? *reinterpret_cast<const uint32_t*>(grad + ((size_t)plan.level(li) * B + b) * C) : 0u;
     };
     if (item < item_end) g_cur = fetch_g(it.chunk_x, it.li);
     __syncthreads();
     for (; item < item_end; item++) {
         const uint32_t b = it.chunk_x * BIN_PPB + (uint32_t)tid;
-        const bool in_range = b < B;
+        const bool in_range = b < B_live;
         if (it.chunk_x != chunk_loaded) {  // (wave-uniform) the positions: once per chunk
             chunk_loaded = it.chunk_x;
             if (in_range) {
@@ -1394,7 +1400,8 @@ template <int D, bool ADAM>
 __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_grid_backward_accumulate(const int32_t* __restrict__ offsets, half_t* __restrict__ grad_grid,
                                                                           BinPlan plan, const uint32_t* __restrict__ descriptors,
                                                                           const uint2* __restrict__ records, float* __restrict__ found_inf,
-                                                                          SlabSets slabs, bool overwrite, TableAdam ta) {
+                                                                          SlabSets slabs, bool overwrite, TableAdam ta,
+                                                                          const uint32_t* __restrict__ rows) {
     constexpr int MAX_REC = BIN_PPB * (1 << D);
     constexpr int WAVES = ACC_THREADS / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char acc_smem[];
@@ -1470,15 +1477,20 @@ __global__ __launch_bounds__(ACC_THREADS) __attribute__((amdgpu_waves_per_eu(8, 
         }
     }
     // every workgroup of a level walks the same chunks: start each one somewhere else
-    const uint32_t rot = (bin * 97u) % n_chunks;
-    auto chunk_of = [&](uint32_t i) { const uint32_t k = i + rot; return k >= n_chunks ? k - n_chunks : k; };
+    // rows (optional device word, common.h: live_rows): the sort wrote descriptors for the chunks below n_live only, so the walk stops there
+    // (n_chunks stays the stride).  The slice sums are exact integers: the walk order does not change a bit.  n_live == 0: no record, the
+    // flush below still runs (a zero gradient for every entry of the slice)
+    static_assert((uint32_t)BIN_PPB == LIVE_GRANULE, "the row bound is a whole number of chunks");
+    const uint32_t n_live = live_rows(n_chunks * (uint32_t)BIN_PPB, rows) / (uint32_t)BIN_PPB;
+    const uint32_t rot = n_live ? (bin * 97u) % n_live : 0u;
+    auto chunk_of = [&](uint32_t i) { const uint32_t k = i + rot; return k >= n_live ? k - n_live : k; };
     // (lanes of the wave talk to each other through these two arrays with nothing but the LDS's in-order execution between a store and
     // the load of another lane: the accesses are volatile, otherwise the compiler forwards a lane's OWN earlier store to its load)
     typedef volatile __attribute__((address_space(3))) uint32_t* lds_words_t;
     lds_words_t my_runs = (lds_words_t)(__attribute__((address_space(3))) void*)(run_table + wid * 64);
     lds_words_t my_heads = (lds_words_t)(__attribute__((address_space(3))) void*)(head_at + wid * 64);
-    const uint32_t per_wave = (n_chunks + WAVES - 1) / WAVES;
-    const uint32_t run_end = min(n_chunks, (uint32_t)(wid + 1) * per_wave);
+    const uint32_t per_wave = (n_live + WAVES - 1) / WAVES;
+    const uint32_t run_end = min(n_live, (uint32_t)(wid + 1) * per_wave);
     for (uint32_t run0 = (uint32_t)wid * per_wave; run0 < run_end; run0 += 64u) {  // this wave's runs, 64 at a time (a lane each)
         const uint32_t i = run0 + (uint32_t)lane;
         uint32_t first = 0u, cnt = 0u;
@@ -1838,6 +1850,7 @@ struct BackwardPlan {
     bool adam = false;           // the accumulate's flush applies Adam to the table (needs overwrite; ngp_table_adam_t)
     TableAdam table_adam = {};
     mutable bool slabs_done = false;  // set by the launch that carried them
+    const uint32_t* rows = nullptr;   // optional device word: the row bound of every launch of the call (common.h: live_rows)
     // every level of the L-level table is on the record-sort path: every entry of the table comes out of a flush (which implies what
     // plan_backward asks of a binned level: fp16, C = 2, D = 2 or 3, a workspace, the host offsets, >= BIN_MIN_SAMPLES samples)
     bool every_level_sorted(uint32_t L) const { return n_atomic == 0 && n_binned == L; }
@@ -1943,14 +1956,14 @@ static int launch_backward_bins(const void* grad, const float* inputs, const int
     BinPlan bins = p.bins;
     bins.n_levels = p.n_binned;
     NGP_LAUNCH(sort_kernel, dim3(blocks), dim3(BIN_THREADS), bin_smem, st, (const half_t*)grad, inputs, offsets, (half_t*)grad_emb, B, lv, gridtype,
-                       ac, interp, im, bins, descriptors, records, ap);
+                       ac, interp, im, bins, descriptors, records, ap, p.rows);
     int rc = check_launch("grid_encode_backward(bin)");
     if (rc) return rc;
     static_assert(ACC_THREADS == RS_PARAMS * RS_GROUPS, "the slab reduction's blocks have the accumulate's shape");
     const uint32_t slab_blocks = p.slabs.total_blocks();
     const dim3 acc_grid(std::max(p.max_bins, slab_blocks), p.n_binned + (slab_blocks ? 1u : 0u));
     NGP_LAUNCH(acc_kernel, acc_grid, dim3(ACC_THREADS), acc_smem, st, offsets, (half_t*)grad_emb, bins, (const uint32_t*)descriptors,
-                       (const uint2*)records, p.found_inf, p.slabs, p.overwrite, p.table_adam);
+                       (const uint2*)records, p.found_inf, p.slabs, p.overwrite, p.table_adam, p.rows);
     p.slabs_done = slab_blocks != 0;
     return check_launch("grid_encode_backward(accumulate)");
 }
@@ -1969,7 +1982,7 @@ static int launch_backward(const void* grad, const float* inputs, const int32_t*
         dim3 grid(cdiv(B, ppb), plan.n_atomic, 1);
         constexpr int MERGE = BwdLanes<T, C>::LPP == 2 ? 3 : 1;  // two lanes per sample: the run merge is pure DPP
         NGP_LAUNCH((k_grid_backward<T, D, C, MERGE>), grid, dim3(BWD_THREADS), 0, st, (const T*)grad, inputs, offsets, (T*)grad_emb, B,
-                           plan.atomic_levels, lv, gridtype, ac, interp, ppb, im);
+                           plan.atomic_levels, lv, gridtype, ac, interp, ppb, im, plan.rows);
         rc = check_launch("grid_encode_backward");
         if (rc) return rc;
     }
@@ -2084,11 +2097,18 @@ static int grid_encode_forward_impl(const float* inputs, const void* embeddings,
     return NGP_ERR_INVALID;
 }
 
+// the row bound armed on the thread (ngp_training_row_bound) bounds a forward launch that has no device count of its own
+static void arm_row_bound(TableSel& sel) {
+    if (!sel.rows && (sel.rows = armed_row_bound())) sel.rows_live = true;   // the word is rounded by THE rule (common.h: live_rows)
+}
+
 extern "C" int ngp_grid_encode_forward_sched(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs,
                                              uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void* dy_dx,
                                              uint32_t gridtype, int align_corners, uint32_t interp, int dtype, float bound,
                                              const float* level_cost_host, ngp_stream_t stream) {
-    return grid_encode_forward_impl(inputs, embeddings, TableSel{nullptr, nullptr, nullptr}, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners,
+    TableSel sel{nullptr, nullptr, nullptr};
+    if (!dy_dx && dtype != NGP_F64) arm_row_bound(sel);
+    return grid_encode_forward_impl(inputs, embeddings, sel, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners,
                                     interp, dtype, bound, level_cost_host, stream);
 }
 
@@ -2100,6 +2120,7 @@ extern "C" int ngp_grid_encode_forward_sel(const float* inputs, const void* embe
     NGP_REQUIRE(dtype == NGP_F16 || !(embeddings_alt && parity), NGP_ERR_INVALID, "grid_encode_forward_sel: the double-buffered table is fp16");
     TableSel sel = embeddings_alt && parity ? TableSel{reinterpret_cast<const _Float16*>(embeddings_alt), parity, nullptr} : TableSel{nullptr, nullptr, nullptr};
     sel.rows = rows_dev;
+    arm_row_bound(sel);
     return grid_encode_forward_impl(inputs, embeddings, sel, offsets, outputs, B, D, C, L, S, H, nullptr, gridtype, align_corners, interp, dtype,
                                     bound, level_cost_host, stream);
 }
@@ -2197,14 +2218,20 @@ static int dispatch_backward(uint32_t D, uint32_t C, const void* grad, const flo
     return NGP_ERR_INVALID;
 }
 
+static int grid_backward_checked_slabs(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B, uint32_t D,
+                                       uint32_t C, uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype,
+                                       int align_corners, uint32_t interp, int dtype, float bound, const int32_t* offsets_host, void* workspace,
+                                       size_t workspace_bytes, float* found_inf, const ngp_slab_sets_t* slab_sets, const uint32_t* rows_dev,
+                                       ngp_stream_t stream);
+
 extern "C" int ngp_grid_encode_backward_checked(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
                                                 void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
                                                 uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
                                                 uint32_t interp, int dtype, float bound, const int32_t* offsets_host, void* workspace,
                                                 size_t workspace_bytes, float* found_inf, ngp_stream_t stream) {
-    return ngp_grid_encode_backward_checked_slabs(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
-                                                  align_corners, interp, dtype, bound, offsets_host, workspace, workspace_bytes, found_inf, nullptr,
-                                                  stream);
+    (void)embeddings;
+    return grid_backward_checked_slabs(grad, inputs, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners, interp,
+                                       dtype, bound, offsets_host, workspace, workspace_bytes, found_inf, nullptr, nullptr, stream);
 }
 
 // The steps of ngp_grid_encode_backward_checked_slabs, in the order it takes them.
@@ -2264,13 +2291,11 @@ static int sweep_nonfinite(const void* grad_embeddings, uint64_t n, int dtype, f
     return check_launch("grid_encode_backward(non-finite sweep)");
 }
 
-extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
-                                                      void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
-                                                      uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
-                                                      uint32_t interp, int dtype, float bound, const int32_t* offsets_host, void* workspace,
-                                                      size_t workspace_bytes, float* found_inf, const ngp_slab_sets_t* slab_sets,
-                                                      ngp_stream_t stream) {
-    (void)embeddings;
+static int grid_backward_checked_slabs(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B, uint32_t D,
+                                       uint32_t C, uint32_t L, float S, uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype,
+                                       int align_corners, uint32_t interp, int dtype, float bound, const int32_t* offsets_host, void* workspace,
+                                       size_t workspace_bytes, float* found_inf, const ngp_slab_sets_t* slab_sets, const uint32_t* rows_dev,
+                                       ngp_stream_t stream) {
     hipStream_t st = as_stream(stream);
     const bool overwrite_table = slab_sets && slab_sets->overwrite_table;
     const ngp_table_adam_t* tadam = slab_sets ? slab_sets->table_adam : nullptr;
@@ -2279,6 +2304,7 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
     if (rc) return rc;
     NGP_REQUIRE(!(bound > 0.0f && dy_dx), NGP_ERR_INVALID, "grid_encode_backward: the fused input mapping does not provide grad_inputs");
     NGP_REQUIRE(!found_inf || offsets_host, NGP_ERR_INVALID, "grid_encode_backward: found_inf needs the host copy of the offsets");
+    NGP_REQUIRE(!rows_dev || !(dy_dx || grad_inputs), NGP_ERR_INVALID, "grid_encode_backward: the row bound does not serve the grad_inputs kernel");
     rc = check_grid_args("grid_encode_backward", B, D, C, L, dtype);
     if (rc) return rc;
     if (B == 0) {   // nothing to add: the table is zeroed where the caller asked for an overwrite, the carried reductions still run
@@ -2297,6 +2323,7 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
     plan_backward(plan, offsets_host, lv, B, D, C, L, dtype, gridtype, align_corners != 0, workspace != nullptr);
     plan.found_inf = found_inf;
     plan.slabs = carried;
+    plan.rows = rows_dev;
     if (tadam) {
         rc = admit_table_adam(plan, *tadam, overwrite_table, L, grad_embeddings);
         if (rc) return rc;
@@ -2322,6 +2349,18 @@ extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const fl
     if (!rc && !plan.slabs_done) rc = reduce_carried_alone(carried, found_inf, st);
     if (rc || !found_inf || plan.n_atomic == 0) return rc;
     return sweep_nonfinite(grad_embeddings, (uint64_t)offsets_host[L] * C, dtype, found_inf, st);
+}
+
+extern "C" int ngp_grid_encode_backward_checked_slabs(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                                      void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
+                                                      uint32_t H, const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners,
+                                                      uint32_t interp, int dtype, float bound, const int32_t* offsets_host, void* workspace,
+                                                      size_t workspace_bytes, float* found_inf, const ngp_slab_sets_t* slab_sets,
+                                                      ngp_stream_t stream) {
+    (void)embeddings;
+    // (the only backward entry that takes the row bound armed on the thread, ngp_training_row_bound)
+    return grid_backward_checked_slabs(grad, inputs, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners, interp,
+                                       dtype, bound, offsets_host, workspace, workspace_bytes, found_inf, slab_sets, armed_row_bound(), stream);
 }
 
 extern "C" int ngp_grid_encode_backward_ws(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,

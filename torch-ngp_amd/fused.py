@@ -557,11 +557,26 @@ USE_SLABS_IN_ACCUMULATE = os.environ.get('NGP_FUSED_SLABS_IN_ACCUMULATE', '1') !
 # backward launches pay more than that for the recomputation (42 -> 57 us and 32 -> 43 us): they are bound by their instruction stream, not
 # by the bytes (EXPERIMENTS.md, round 4).  Worth it only where the 168 MB of activations per 262 k samples do not fit.
 USE_RECOMPUTE = os.environ.get('NGP_FUSED_RECOMPUTE', '0') == '1'
+# the direct iteration bounds its per-sample kernels (grid forward, network forward, both MLP backwards, record sort, slice accumulate) by the
+# rows the march filled -- word 0 of the march workspace of the buffer set it runs on, rounded up to 512 (include/ngp_hip.h,
+# ngp_training_row_bound) -- instead of running them over the capacity of the sample buffers.  Same launches, same bits
+# (tests/test_gpu_row_bound_step.py); False / NGP_FUSED_ROW_BOUND=0: the capacity-sized form
+USE_ROW_BOUND = os.environ.get('NGP_FUSED_ROW_BOUND', '1') != '0'
 
 
 def _carries_reductions(nl_sigma, nl_color):
     """does the grid backward's last launch carry the MLPs' slab reduction (and with it the loss sum)?"""
     return bool(USE_SLABS_IN_ACCUMULATE and USE_FUSED_MID and nl_color in (2, 3) and nl_sigma in (2, 3))
+
+
+def _row_bound(marched, cfg):
+    """the march workspace whose word 0 bounds the per-sample launches of the direct iteration (`capi.row_bound`), or None.  Every launch
+    between the march and the optimizer has to take the bound or none may: the one-launch network forward, the fused compositor (its zeroing
+    sweep is what defines the gradient rows between the word and the bound) and the three-launch backward.  The paths that read per-sample
+    buffers with capacity-sized launches of their own -- ray gradients, the autograd Function, the drop-in modules -- never arm it."""
+    if USE_ROW_BOUND and USE_FUSED_NETWORK and USE_FUSED_COMPOSITE and USE_FUSED_MID and cfg.nl_color in (2, 3) and cfg.nl_sigma in (2, 3):
+        return marched.ws
+    return None
 
 
 def _recompute(nl_sigma, nl_color):
@@ -663,8 +678,10 @@ def fused_train_iteration_split(model, rays_o, rays_d, target, box, counter, cap
 
     def rest():
         ta = _table_adam_of(table_adam, model)
-        out = _train_iteration_rest(box_['m'], bufs, bg_t, model.encoder.offsets, target, loss_scale, cfg, rcfg, found_inf, overwrite_table, ta,
-                                    geo_loss)
+        # (the workspace pointer is static per buffer set: graph capture and the native command list record it like any other argument)
+        with capi.row_bound(_row_bound(box_['m'], cfg)):
+            out = _train_iteration_rest(box_['m'], bufs, bg_t, model.encoder.offsets, target, loss_scale, cfg, rcfg, found_inf, overwrite_table, ta,
+                                        geo_loss)
         if overwrite_table:
             # read (and reset) by the optimizer's next step: it keeps the buffer -- and, where this iteration's backward swept the table with
             # Adam, applies Adam to the dense-level prefix only
