@@ -1017,6 +1017,42 @@ int ngp_error_map_draw(const float* error_map, uint32_t B, uint32_t res, uint32_
 int ngp_error_map_update(float* error_map_row, const int64_t* inds_coarse, const float* image, const float* target, uint32_t N,
                          uint32_t n_cells, float keep, float take, ngp_stream_t stream);
 
+/* ---- signed-distance fields: NeuS's section opacity as a density (csrc/sdf_sigmas.hip) ----
+ * NeuS (Wang et al. 2021; models/renderer.py) renders an SDF sample with the opacity
+ *   alpha = clip((prev - next + eps) / (prev + eps), 0, 1),   prev = sigmoid(inv_s (sdf - h)),  next = sigmoid(inv_s (sdf + h)),  eps = 1e-5
+ *   c = dirs . normals,   ic = -(relu(0.5 - 0.5 c) (1 - cos_anneal) + relu(-c) cos_anneal)  (<= 0),   h = 0.5 ic d0,   d0 = deltas[i,0]
+ * Every compositor of this library takes a density and forms alpha = 1 - exp(-sigma * deltas[i,0]) itself (raymarching.cu:501-577), so the
+ * entry returns the density that reproduces NeuS's alpha, in the form that has neither the prev - next nor the 1 - alpha cancellation
+ * (1 - alpha = next / (prev + eps) exactly; h <= 0 gives next <= prev, the clip is never active):
+ *   x = log(prev + eps) + softplus(-inv_s (sdf + h))   (= -log(1 - alpha)),     sigma = min(x, 15) / d0,     sigma = 0 where d0 == 0
+ * The cap 15 is the bound of trunc_exp: a sample deep inside the surface ends the ray (1 - alpha = 3.1e-7) instead of producing inf.
+ * sdf [M], normals [M,3] (the SDF's gradient, not normalised), dirs [M,3], deltas [M,2] (only column 0 is read, as one 8-byte load),
+ * inv_s: ONE device float, read by the kernels; cos_anneal: host float in [0, 1]; sigmas [M].  One lane per row, one launch.
+ * Backward, from grad_sigmas [M], recomputing the forward terms: with P = prev, A = P (1 - P) / (P + eps), B = 1 - next, gx = grad_sigmas / d0
+ *   grad_sdf = gx inv_s (A - B),   dL/dh = -gx inv_s (A + B),   dh/dc = 0.5 d0 (0.5 (1 - cos_anneal) [c < 1] + cos_anneal [c < 0])
+ *   grad_normals = dL/dh dh/dc dirs,   grad_dirs = dL/dh dh/dc normals  (grad_dirs may be NULL: not written),
+ *   grad_inv_s[0] = sum_i gx_i (A_i (sdf_i - h_i) - B_i (sdf_i + h_i))
+ * EVERY row of grad_sdf / grad_normals / grad_dirs is written: zeros for rows with d0 == 0 and for capped rows (x >= 15: the derivative
+ * of min).  deltas gets no gradient.  grad_inv_s is summed in double in a fixed order without atomics -- an xor tree per wave, the waves of
+ * a workgroup in order into partials[workgroup] (the workspace), then one workgroup adds the partials (thread t: t, t + 256, ... in index
+ * order; the same wave / workgroup order) and rounds once; the grid is cdiv(M, 256) whatever the data: the same bits on every run.
+ * workspace: ngp_sdf_sigmas_workspace_bytes(M) bytes (monotone in M), 8-byte aligned, contents irrelevant before and after.
+ * NGP_ERR_INVALID before any device work: cos_anneal outside [0, 1]; for M > 0 a NULL tensor (other than grad_dirs), M > 2^31, a NULL or
+ * short workspace.  M == 0: nothing is launched and nothing is written (the caller provides grad_inv_s = 0). */
+size_t ngp_sdf_sigmas_workspace_bytes(uint32_t M);
+int ngp_sdf_sigmas_forward(const float* sdf, const float* normals, const float* dirs, const float* deltas, const float* inv_s, uint32_t M,
+                           float cos_anneal, float* sigmas, ngp_stream_t stream);
+int ngp_sdf_sigmas_backward(const float* grad_sigmas, const float* sdf, const float* normals, const float* dirs, const float* deltas,
+                            const float* inv_s, uint32_t M, float cos_anneal, float* grad_sdf, float* grad_normals, float* grad_dirs,
+                            float* grad_inv_s, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+/* fp64 twins (csrc/fp64.hip: the same kernel source instantiated for double): every floating tensor double, cos_anneal still a float; for
+ * torch.autograd.gradcheck */
+int ngp_sdf_sigmas_forward_f64(const double* sdf, const double* normals, const double* dirs, const double* deltas, const double* inv_s,
+                               uint32_t M, float cos_anneal, double* sigmas, ngp_stream_t stream);
+int ngp_sdf_sigmas_backward_f64(const double* grad_sigmas, const double* sdf, const double* normals, const double* dirs, const double* deltas,
+                                const double* inv_s, uint32_t M, float cos_anneal, double* grad_sdf, double* grad_normals, double* grad_dirs,
+                                double* grad_inv_s, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,11 @@ _SIGNATURES = {
     # error-map ray sampling (csrc/error_map.hip): the weighted draw without replacement and the per-step EMA scatter
     'ngp_error_map_draw': [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
     'ngp_error_map_update': [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _f32, _vp],
+    # NeuS's section opacity as a density (csrc/sdf_sigmas.hip)
+    'ngp_sdf_sigmas_forward': [_vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp],
+    'ngp_sdf_sigmas_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    'ngp_sdf_sigmas_forward_f64': [_vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp],
+    'ngp_sdf_sigmas_backward_f64': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
 }
 for _name, _args in _SIGNATURES.items():
     _fn = getattr(lib, _name)
@@ -203,6 +208,8 @@ lib.ngp_density_grid_update_workspace_bytes.argtypes = [_u32]
 lib.ngp_linear_stack_flat_size.argtypes = [_u32, _u32, _u32, _u32, _i32]
 lib.ngp_linear_stack_flat_size.restype = _u32
 lib.ngp_density_grid_update_workspace_bytes.restype = _sz
+lib.ngp_sdf_sigmas_workspace_bytes.argtypes = [_u32]
+lib.ngp_sdf_sigmas_workspace_bytes.restype = _sz
 
 if lib.ngp_abi_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH}: ABI version {lib.ngp_abi_version()} != expected {ABI_VERSION}; rebuild the extension")
@@ -213,7 +220,7 @@ EXPORTED = sorted(list(_SIGNATURES) + ['ngp_last_error', 'ngp_target_arch', 'ngp
                                        'ngp_ffmlp_backward_slab_count', 'ngp_density_grid_update_workspace_bytes', 'ngp_grid_forward_work_lists', 'ngp_coarse_occupancy_bytes',
                                        'ngp_grid_table_adam_prefix', 'ngp_linear_stack_flat_size',
                                        'ngp_grid_backward_backward_workspace_bytes', 'ngp_ffmlp_backward_backward_workspace_bytes',
-                                       'ngp_grid_ordered_workspace_bytes'])
+                                       'ngp_grid_ordered_workspace_bytes', 'ngp_sdf_sigmas_workspace_bytes'])
 
 
 def check(rc):

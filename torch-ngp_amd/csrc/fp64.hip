@@ -12,13 +12,15 @@
 //     a_k) and adds the sum once.  No float atomics, so two calls give the same bits;
 //   * TV: fp64 throughout, fp64 atomics (not on an autograd path);
 //   * SH: fp64 arithmetic and constants (sh_poly64.inc, tools/gen_sh.py);
-//   * compositing / near-far / sph / packbits: the reference's per-ray loops in fp64 (exp in double, T < T_thresh compared in double).
+//   * compositing / near-far / sph / packbits: the reference's per-ray loops in fp64 (exp in double, T < T_thresh compared in double);
+//   * sdf_sigmas: the fp32 kernels' own source (sdf_sigmas.h) instantiated for double.
 #include "common.h"
 #include "grid_index.h"
 #include "grid_records.h"
 #include "grid_second.h"
 #include "fp64.h"
 #include "sh_poly64.inc"
+#include "sdf_sigmas.h"
 #include <float.h>
 #include <math.h>
 
@@ -760,4 +762,22 @@ extern "C" int ngp_composite_rays_f64(uint32_t n_alive, uint32_t n_step, float T
     F64_LAUNCH_1D(k_f64_composite_rays, n_alive, as_stream(stream), n_alive, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum,
                   depth, image);
     return check_launch("composite_rays_f64");
+}
+
+// fp64 twins of ngp_sdf_sigmas_forward / _backward (sdf_sigmas.h: the same kernel bodies and host half instantiated for double)
+namespace ngp {
+SDF_SIGMAS_KERNELS(double, k_f64_sdf_sigmas)
+static const SdfKernels<double> sdf_kernels_f64 = {k_f64_sdf_sigmas_fwd, k_f64_sdf_sigmas_bwd, k_f64_sdf_sigmas_inv_s};
+}  // namespace ngp
+
+extern "C" int ngp_sdf_sigmas_forward_f64(const double* sdf, const double* normals, const double* dirs, const double* deltas, const double* inv_s,
+                                          uint32_t M, float cos_anneal, double* sigmas, ngp_stream_t stream) {
+    return sdf_sigmas_forward<double>("sdf_sigmas_forward_f64", sdf_kernels_f64, sdf, normals, dirs, deltas, inv_s, M, cos_anneal, sigmas, as_stream(stream));
+}
+
+extern "C" int ngp_sdf_sigmas_backward_f64(const double* grad_sigmas, const double* sdf, const double* normals, const double* dirs, const double* deltas,
+                                           const double* inv_s, uint32_t M, float cos_anneal, double* grad_sdf, double* grad_normals, double* grad_dirs,
+                                           double* grad_inv_s, void* workspace, size_t workspace_bytes, ngp_stream_t stream) {
+    return sdf_sigmas_backward<double>("sdf_sigmas_backward_f64", sdf_kernels_f64, grad_sigmas, sdf, normals, dirs, deltas, inv_s, M, cos_anneal, grad_sdf,
+                                       grad_normals, grad_dirs, grad_inv_s, workspace, workspace_bytes, as_stream(stream));
 }

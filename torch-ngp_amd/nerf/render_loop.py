@@ -32,7 +32,8 @@ class LoopOptions:
                              attribute; 1 with perturb (the first call's samples are the offset ones: their number must follow the reference's rule)
     loop_max_rows: 1 << 26   no boost beyond this many rows
     native_loop: True        one ngp_render_iterations_dev call per pair -- a Python callable cannot be issued from C (aux_infer), and nobody
-                             may be probing the stages; FrameLoop also needs the entry in the library and fused.inference_weights
+                             may be probing the stages; FrameLoop also needs the entry in the library and fused.inference_weights; not for a
+                             model with takes_deltas (it is called as model(xyzs, dirs, deltas=deltas), per stage)
     loop_device_rows: True   the native call's march publishes the rows that carry a sample; encoder and network stop there
     _loop_probe: None        a list: (stage, start event, end event, lanes, rows, n_total, state snapshot) per stage of every iteration
     _loop_iter_hook: None    called with every iteration's deltas
@@ -57,8 +58,9 @@ class LoopOptions:
         self.initial_boost = 1 if self.perturb else max(1, int(os.environ.get('NGP_LOOP_INITIAL_BOOST', getattr(model, 'loop_initial_boost', 2))))
         self.max_rows = int(getattr(model, 'loop_max_rows', 1 << 26))
         self.scaled = hasattr(model, 'forward_scaled')   # (the fused network folds the density scale: one launch less per iteration)
+        self.takes_deltas = bool(getattr(model, 'takes_deltas', False))   # (an SDF model: called with the iteration's deltas, stage by stage)
         self.native = (bool(getattr(model, 'native_loop', True)) and self.aux_infer is None and self.probe is None and self.iter_hook is None
-                       and self.scaled)
+                       and self.scaled and not self.takes_deltas)
         self.device_rows = bool(getattr(model, 'loop_device_rows', True))
         return self
 
@@ -180,8 +182,9 @@ class StageIssuer:
                                                       m.grid_size, f.bits, f.near, f.far, xyzs, dirs, deltas, noises, rows))
         if f.opt.iter_hook is not None:
             f.opt.iter_hook(deltas)
-        scaled = f.opt.scaled
-        sigmas, rgbs = stage('network (encoder + MLPs + glue)', lambda: m.forward_scaled(xyzs, dirs, m.density_scale) if scaled else m(xyzs, dirs))
+        scaled = f.opt.scaled and not f.opt.takes_deltas
+        sigmas, rgbs = stage('network (encoder + MLPs + glue)', lambda: m.forward_scaled(xyzs, dirs, m.density_scale) if scaled else
+                             m(xyzs, dirs, deltas=deltas) if f.opt.takes_deltas else m(xyzs, dirs))
         sigmas, rgbs32 = stage('casts (density_scale, fp32 copies)', lambda: ((sigmas if scaled else m.density_scale * sigmas).float().contiguous(),
                                                                                rgbs.float().contiguous()))
         if f.aux_infer is not None:   # before composite_rays_dev: the feature kernel reads the weights_sum that call advances

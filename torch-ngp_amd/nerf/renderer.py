@@ -238,7 +238,8 @@ class NeRFRenderer(nn.Module):
             if ray_grads:
                 ts = raymarching.sample_ts(xyzs, rays_o, rays_d, rays, self.bound)
                 xyzs, dirs = raymarching.ray_points(rays_o_in, rays_d_in, ts, rays, self.bound, like=(xyzs, dirs))
-            sigmas, rgbs = self(xyzs, dirs)
+            # (a model that sets takes_deltas -- an SDF model, whose density depends on the section length -- is handed the marcher's deltas)
+            sigmas, rgbs = self(xyzs, dirs, deltas=deltas) if getattr(self, 'takes_deltas', False) else self(xyzs, dirs)
             sigmas = self.density_scale * sigmas
             if aux is not None:
                 if sigmas.dim() == 2:
@@ -290,7 +291,7 @@ class NeRFRenderer(nn.Module):
                         xyzs, dirs, deltas = raymarching.march_rays(
                             n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, self.bound, self.density_bitfield, self.cascade,
                             self.grid_size, nears, fars, 128, perturb if step == 0 else False, dt_gamma, max_steps)
-                        sigmas, rgbs = self(xyzs, dirs)
+                        sigmas, rgbs = self(xyzs, dirs, deltas=deltas) if getattr(self, 'takes_deltas', False) else self(xyzs, dirs)
                         sigmas = self.density_scale * sigmas
                         if aux_infer is not None:   # the fp32 tensors composite_rays' cast would make: both ops read the same values
                             sigmas, rgbs = sigmas.float().contiguous(), rgbs.float().contiguous()

@@ -341,6 +341,28 @@ def ray_points_backward(grad_xyzs, grad_dirs, grad_sh16, xyzs, ts, rays_d, rays,
                                                 capi.stream()))
 
 
+def sdf_sigmas_forward(sdf, normals, dirs, deltas, inv_s, M, cos_anneal, sigmas):
+    """extension (include/ngp_hip.h, ngp_sdf_sigmas_forward): NeuS's section opacity as the density that reproduces it.  ctypes-only, like the
+    geometry and feature compositors."""
+    floats = ((sdf, 'sdf'), (normals, 'normals'), (dirs, 'dirs'), (deltas, 'deltas'), (inv_s, 'inv_s'), (sigmas, 'sigmas'))
+    fn = capi.lib.ngp_sdf_sigmas_forward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_sdf_sigmas_forward)
+    capi.check(fn(capi.ptr(sdf), capi.ptr(normals), capi.ptr(dirs), capi.ptr(deltas), capi.ptr(inv_s), M, float(cos_anneal), capi.ptr(sigmas),
+                  capi.stream()))
+
+
+def sdf_sigmas_backward(grad_sigmas, sdf, normals, dirs, deltas, inv_s, M, cos_anneal, grad_sdf, grad_normals, grad_dirs, grad_inv_s):
+    """extension (ngp_sdf_sigmas_backward): every row of grad_sdf / grad_normals / grad_dirs (None: not wanted) and grad_inv_s [1], the latter
+    through a fixed-order sum over a workspace allocated here (M == 0: nothing is launched, grad_inv_s stays as the caller made it)"""
+    floats = tuple(p for p in ((grad_sigmas, 'grad_sigmas'), (sdf, 'sdf'), (normals, 'normals'), (dirs, 'dirs'), (deltas, 'deltas'), (inv_s, 'inv_s'),
+                               (grad_sdf, 'grad_sdf'), (grad_normals, 'grad_normals'), (grad_dirs, 'grad_dirs'), (grad_inv_s, 'grad_inv_s'))
+                   if p[0] is not None)
+    fn = capi.lib.ngp_sdf_sigmas_backward_f64 if _f64(floats) else _f32_call(floats, capi.lib.ngp_sdf_sigmas_backward)
+    n = int(capi.lib.ngp_sdf_sigmas_workspace_bytes(M))
+    ws = torch.empty(n, dtype=torch.uint8, device=sdf.device) if n else None
+    capi.check(fn(capi.ptr(grad_sigmas), capi.ptr(sdf), capi.ptr(normals), capi.ptr(dirs), capi.ptr(deltas), capi.ptr(inv_s), M, float(cos_anneal),
+                  capi.ptr(grad_sdf), capi.ptr(grad_normals), capi.ptr(grad_dirs), capi.ptr(grad_inv_s), capi.ptr(ws), n, capi.stream()))
+
+
 def _accept_half(fn):
     """the reference dispatches its raymarching entry points on the tensor dtype (AT_DISPATCH_FLOATING_TYPES_AND_HALF, raymarching.cu:486);
     its own wrappers always hand over fp32 (custom_fwd(cast_inputs=float32)), so fp16 is unreachable from them.  For direct `_backend`

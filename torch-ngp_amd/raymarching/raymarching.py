@@ -22,7 +22,8 @@ except ImportError:
 from . import backend as _geo  # the geometry compositor's entries are ctypes-only: the compiled module's table is the reference's
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'packbits_capped', 'march_rays_train',
-           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'sample_ts', 'ray_points', 'march_rays', 'composite_rays', 'composite_rays_features', 'compact_rays', 'update_density_grid', 'density_grid_state']
+           'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'sample_ts', 'ray_points', 'march_rays', 'composite_rays', 'composite_rays_features', 'compact_rays', 'update_density_grid', 'density_grid_state',
+           'sdf_sigmas']
 
 _f32_fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 
@@ -311,6 +312,59 @@ class _composite_rays_train_features(Function):
 
 
 composite_rays_train_features = _composite_rays_train_features.apply
+
+
+class _sdf_sigmas(Function):
+    """Extension (not in the reference): render a signed-distance field with the compositors as they are.  NeuS's section
+    opacity alpha = clip((prev - next + 1e-5) / (prev + 1e-5), 0, 1), prev / next = sigmoid(inv_s (sdf -+ h)), h = 0.5 ic deltas[:,0] with
+    NeuS's annealed cosine ic <= 0 of c = dirs . normals, expressed as the density every compositor turns back into that alpha:
+    sigma = min(-log(1 - alpha), 15) / deltas[:,0] in the cancellation-free form log(prev + 1e-5) + softplus(-inv_s (sdf + h)); 0 where
+    deltas[:,0] == 0.  One launch each way.  Gradients go to sdf, normals, inv_s and -- when it requires grad -- dirs; capped and padding rows
+    get zeros; grad_inv_s is summed in a fixed order (the same bits on every run).  float64 goes in and out as float64, everything else is
+    taken as float32.  First order only; normals that come out of a create_graph=True gradient are fine (grad_normals flows back into
+    that graph)."""
+
+    @staticmethod
+    def forward(ctx, sdf, normals, dirs, deltas, inv_s, cos_anneal=1.0):
+        """sdf [M], normals [M,3], dirs [M,3], deltas [M,2], inv_s [1] device tensor, cos_anneal host float in [0, 1] -> sigmas [M]"""
+        tensors = (sdf, normals, dirs, deltas, inv_s)
+        ctx.like = tuple((t.shape, t.dtype) for t in tensors)
+        dtype = _ray_dtype(*tensors)
+        n_samples = deltas.shape[0]
+        if sdf.numel() != n_samples or tuple(normals.shape) != (n_samples, 3) or tuple(dirs.shape) != (n_samples, 3) or deltas.dim() != 2 or \
+                deltas.shape[1] != 2 or inv_s.numel() != 1:
+            raise RuntimeError(f"sdf_sigmas: expected sdf [M], normals [M,3], dirs [M,3], deltas [M,2], inv_s [1] (got {tuple(sdf.shape)}, "
+                               f"{tuple(normals.shape)}, {tuple(dirs.shape)}, {tuple(deltas.shape)}, {tuple(inv_s.shape)})")
+        sdf, normals, dirs, deltas, inv_s = (t.detach().to(dtype).contiguous() for t in tensors)
+        sdf, inv_s = sdf.reshape(-1), inv_s.reshape(1)
+        sigmas = torch.empty(n_samples, dtype=dtype, device=sdf.device)
+        _geo.sdf_sigmas_forward(sdf, normals, dirs, deltas, inv_s, n_samples, cos_anneal, sigmas)
+        ctx.save_for_backward(sdf, normals, dirs, deltas, inv_s)
+        ctx.cos_anneal = float(cos_anneal)
+        return sigmas
+
+    @staticmethod
+    def backward(ctx, grad_sigmas):
+        if torch.is_grad_enabled() and grad_sigmas.requires_grad:
+            raise RuntimeError("sdf_sigmas: second-order gradients are not provided (the op's backward is not differentiable; raymarching "
+                               "stays first-order)")
+        sdf, normals, dirs, deltas, inv_s = ctx.saved_tensors
+        n_samples = sdf.shape[0]
+        grad_sdf, grad_normals = torch.empty_like(sdf), torch.empty_like(normals)
+        grad_dirs = torch.empty_like(dirs) if ctx.needs_input_grad[2] else None
+        grad_inv_s = (torch.zeros_like if n_samples == 0 else torch.empty_like)(inv_s)   # without rows nothing is launched
+        _geo.sdf_sigmas_backward(grad_sigmas.to(sdf.dtype).contiguous(), sdf, normals, dirs, deltas, inv_s, n_samples, ctx.cos_anneal, grad_sdf,
+                                 grad_normals, grad_dirs, grad_inv_s)
+        back = lambda g, like: None if g is None else g.view(like[0]).to(like[1])
+        return (back(grad_sdf, ctx.like[0]), back(grad_normals, ctx.like[1]), back(grad_dirs, ctx.like[2]), None, back(grad_inv_s, ctx.like[4]),
+                None)
+
+
+def sdf_sigmas(sdf, normals, dirs, deltas, inv_s, cos_anneal=1.0):
+    return _sdf_sigmas.apply(sdf, normals, dirs, deltas, inv_s, cos_anneal)
+
+
+sdf_sigmas.__doc__ = _sdf_sigmas.__doc__
 
 
 def _ray_dtype(*tensors):
