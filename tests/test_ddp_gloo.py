@@ -618,25 +618,26 @@ def _stub_stepper(opt, table):
 
 
 def test_graphed_train_step_states_the_replay_at_every_replay_site(monkeypatch):
+    import dataclasses
     opt, table, mlp = _fused_double()
+    from graph import GraphedTrainStep, _Capture, _LaSet
     opt.enable_table_fusion(table)
     st = _stub_stepper(opt, table)
     log = []
     cap = st._capacity()
     o, d, t = torch.zeros(1, 8, 3), torch.zeros(1, 8, 3), torch.zeros(8, 3)
-    # the plain graph of step()
-    st.graphs, st.captured_capacity, st.loss = (_StubGraph(log, 'plain'),), cap, torch.zeros(())
-    st.table_fused = False
+    # the plain graph of step(): a capture record as _capture_plain leaves it
+    plain = _Capture(cap, replay=GraphedTrainStep._replay_plain, graphs=(_StubGraph(log, 'plain'),), loss=torch.zeros(()))
+    st.active, st.captured_capacity = plain, cap
     st.step(o, d, t)
     assert log == ['plain'] and not opt._maybe_flipped   # graphs with the separate sweep: nothing flips
-    st.table_fused = True
+    plain.table_fused = True
     st.step(o, d, t)
     assert log == ['plain', 'plain'] and opt._maybe_flipped
     # a switch to another captured capacity (_activate: no Python iteration runs), then its replay
     opt._maybe_flipped = False
-    st._captured = {cap: st._snapshot()}
-    other = dict(st._snapshot(), graphs=(_StubGraph(log, 'other'),))
-    st._captured[cap + 4 * st.quantum] = other
+    other = dataclasses.replace(plain, capacity=cap + 4 * st.quantum, graphs=(_StubGraph(log, 'other'),))
+    st._captured = {cap: plain, other.capacity: other}
     st.model.mean_count = cap + 3 * st.quantum
     st.step(o, d, t)
     assert log[-1] == 'other' and st.n_switches == 1 and st.captured_capacity == cap + 4 * st.quantum and opt._maybe_flipped
@@ -646,8 +647,9 @@ def test_graphed_train_step_states_the_replay_at_every_replay_site(monkeypatch):
     st.la_rays_o, st.la_rays_d = [torch.zeros(8, 3) for _ in range(2)], [torch.zeros(8, 3) for _ in range(2)]
     st.la_target, st.la_seed = [torch.zeros(8, 3) for _ in range(2)], torch.zeros(2, dtype=torch.int32)
     st.la_event, st.la_slot_event = [_StubEvent(), _StubEvent()], _StubEvent()
-    st.la = [(_StubGraph(log, f'march{p}'), _StubGraph(log, f'rest{p}'), torch.zeros(())) for p in range(2)]
-    st._captured = {st.captured_capacity: st._snapshot()}
+    sets = [_LaSet(_StubGraph(log, f'march{p}'), _StubGraph(log, f'rest{p}'), torch.zeros(()), None) for p in range(2)]
+    st.active = dataclasses.replace(other, replay=GraphedTrainStep._replay_lookahead, la=sets)
+    st._captured = {other.capacity: st.active}
     st.step(o, d, t)
     assert log[-2:] == ['march0', 'rest0'] and st.la_cur == 1 and opt._maybe_flipped
     opt.materialize()

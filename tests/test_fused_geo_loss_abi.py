@@ -139,13 +139,12 @@ def test_direct_path_accepts_geo_loss_and_still_declines_geo_renders():
     assert GraphedTrainStep._direct_ok(step) is False and len(asked) == 1   # declined before the renderer is asked
     step.render_kwargs = {'bg_color': 1, 'staged': True}
     assert GraphedTrainStep._direct_ok(step) is False and len(asked) == 1
-    # the geo_loss travels to the iteration through _iteration_args; a stand-in without the attribute passes None
+    # the geo_loss travels to the iteration through _iteration_args (the stepper always has the field: None without the term)
     opt = types.SimpleNamespace(scalars=torch.zeros(8))
     for geo in (GeoLoss(lambda_distortion=0.01), None):
-        attrs = {} if geo is None else {'geo_loss': geo}
         s = types.SimpleNamespace(model=types.SimpleNamespace(aabb_train=None), render_kwargs={'bg_color': 1}, optimizer=opt, rays_o=1, rays_d=2,
                                   target=3, counter=torch.zeros(16, 2), captured_capacity=4096, table_fused=False, _overwrites_table=lambda: True,
-                                  **attrs)
+                                  geo_loss=geo)
         args, kwargs = GraphedTrainStep._iteration_args(s, False)
         assert kwargs['geo_loss'] is geo and args[1:4] == (1, 2, 3)
 

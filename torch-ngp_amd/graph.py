@@ -42,7 +42,11 @@ one `update_extra_state` after 16 eager steps (`model.mean_count > 0`) -- before
 worst case and read back, which cannot be captured, and `step()` simply runs eagerly.
 """
 import contextlib
+import dataclasses
+import operator
 import os
+import typing
+from collections import namedtuple
 
 import torch
 
@@ -65,7 +69,67 @@ MARCH_MARKS = {'boundary': None, 'net': ('k_network_forward', 1), 'composite': (
 MARCH_MARK_ID = 1
 
 
-_PARKED = []   # graphs of steppers that were collected while another stepper was capturing (GraphedTrainStep.close)
+# one of the lookahead's two buffer sets as one capture recorded it: the march graph (static rays of the set -> its samples; replays on the
+# side stream), the rest graph (samples + target -> loss, gradients, optimizer step), the static loss and [N,3] image buffers the rest chain
+# writes, and the two closures of fused_train_iteration_split (they keep the marched buffers alive)
+_LaSet = namedtuple('_LaSet', 'march_graph rest_graph loss image march rest', defaults=(None, None))
+
+# the occupancy refresh as graphs: `graph` -> `mean`, the device mean density.  The split form (lookahead) carries the cell sampling as a graph
+# of its own (`sampling` -> `samples`), which may replay on the side stream under the previous iteration; the whole form has both None
+_Refresh = namedtuple('_Refresh', 'graph mean sampling samples', defaults=(None, None))
+
+# what a stepper that is collected inside ANOTHER stepper's stream capture keeps alive until a synchronize is allowed again
+_Parked = namedtuple('_Parked', 'active captured update_graphs side optimizer sample_pool')
+
+
+@dataclasses.dataclass(eq=False, slots=True)
+class _Capture:
+    """everything ONE capture produced and decided, for one sample capacity: `GraphedTrainStep._captured` is {capacity: _Capture}, the
+    stepper steps through `active`.  A field that is not stated here does not exist -- nothing of a capture lives on the stepper, where a
+    switch to another capacity would leave it behind."""
+    capacity: typing.Optional[int] = None   # None: nothing is captured (before the first capture, after a failed one)
+    # one step of this capture's replay shape: replay(stepper, rays_o, rays_d, target, next_rays) -> the device loss.  The plain function,
+    # not a bound method: a record that owned its stepper would leave the stepper's close() to the cyclic collector
+    replay: typing.Any = None
+    graphs: typing.Any = None        # every training graph, in capture order
+    # the rest graphs' launch chains as native command lists (cmdlist.CommandList, one per rest graph; None: the graphs are replayed)
+    lists: typing.Any = None
+    loss: typing.Any = None          # the static loss (single buffer set) ...
+    image: typing.Any = None         # ... and image buffer
+    la: typing.Any = None            # [_LaSet] x 2: the lookahead shape
+    la_apply: typing.Any = None      # sharded lookahead with eager collectives: the graph of the shard update
+    rest_pool: typing.Any = None     # the lookahead's rest graphs' memory pool (the refresh's density half joins it)
+    sharded: bool = False            # the three graphs around the two collectives
+    used_direct: bool = False        # the autograd-free iteration was captured
+    table_fused: bool = False        # the table's Adam sweep rides in the grid backward (needs the producers' non-finite sweep)
+    producers_check: bool = False    # the producers flag non-finite gradients: the optimizer step skips its own sweep
+    checked_ok: bool = False         # they could (fused.iteration_checks_gradients)
+
+    def get(self, field):
+        """a field by name, as readers of `_captured`'s values spell it (tests/test_gpu_step_cmdlist.py: `snap.get('lists')`); strict: a
+        name that is no field raises AttributeError, there is no default to hide behind"""
+        return getattr(self, field)
+
+
+class _Announced(namedtuple('_Announced', 'rays_o rays_d ray_versions epoch target target_version', defaults=(None, None))):
+    """a batch that was staged ahead of its step (marched into a lookahead buffer set, or copied into the sharded step's static buffers).
+    Holds REFERENCES to the announced tensors, compared by identity plus `_version`: a freed tensor's address can be handed out again by
+    the caching allocator (same data_ptr, fresh _version 0), which an address/version key would take for a hit.
+    target None: the rays were announced without it.  epoch: the occupancy epoch a march saw (None: the staging does not depend on the grid)"""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, rays_o, rays_d, target=None, epoch=None):
+        return cls(rays_o, rays_d, (rays_o._version, rays_d._version), epoch, target, None if target is None else target._version)
+
+    def holds_rays(self, rays_o, rays_d, epoch=None):
+        return self.rays_o is rays_o and self.rays_d is rays_d and self.ray_versions == (rays_o._version, rays_d._version) and self.epoch == epoch
+
+    def holds_target(self, target):
+        return self.target is target and self.target_version == target._version
+
+
+_PARKED = []   # _Parked of steppers that were collected while another stepper was capturing (GraphedTrainStep.close), evicted _Capture
 
 
 def _drain_parked():
@@ -117,28 +181,24 @@ class GraphedTrainStep:
         # follows the density network -- the estimate moves by tens of percent over the first thousands of steps (renderer.py:531-538) --
         # does not stop to capture (round 5: two re-captures in 96 steps made that stretch run at 1.98 ms / step against 0.43)
         self._captured = {}
+        self.active = _Capture()    # the record this stepper replays (and, during a capture, the one being filled in)
         self.capacity_ladder = tuple(float(f) for f in (capacity_ladder or ()))
+        self.ladder_error = None    # a rung of the ladder that could not be captured (the rungs before it are kept)
         self.n_switches = 0
-        self.graphs = None
-        # the rest graphs' launch chains as native command lists (cmdlist.CommandList, one per rest graph of the active capacity; None: the
-        # graphs are replayed).  NGP_STEP_CMDLIST=0: keep the graph replay in this build
-        self.lists = None
+        # command lists replace the replay of the rest graphs where the step is eligible.  NGP_STEP_CMDLIST=0: keep the graph replay in this build
         self.use_lists = os.environ.get('NGP_STEP_CMDLIST', '1') != '0'
         self.march_at = os.environ.get('NGP_STEP_MARCH_AT', 'boundary')
         if self.march_at not in MARCH_MARKS:
             raise ValueError(f'NGP_STEP_MARCH_AT={self.march_at!r}: one of {sorted(MARCH_MARKS)}')
         self.n_list_replays = 0
-        self.loss = None
         # the finished [N,3] fp32 image of the step that ran last: a view of a static buffer of the captured step (or the eager step's
         # render), valid until the next step() -- what an error-map update needs besides the loss (nerf.utils.ErrorMaps)
         self.image = None
         self.n_captures = 0
         self.capture_error = None
-        self._checked_ok = False
-        self.producers_check = False
-        self.used_direct = False
         self.graph_updates = True   # replay the occupancy refresh from a HIP graph as well (see _update_extra_state)
-        self.update_graphs = {}     # {full sweep?: (graph, device mean density)}
+        self.update_graphs = {}     # {full sweep?: _Refresh}
+        self._sample_pool = None    # memory pool of the refresh's sampling graphs (they replay on the side stream)
         self.n_update_captures = 0
         self.update_capture_error = None
         self.capacity = None  # sample capacity of the step that ran last (None while eager/worst-case)
@@ -157,24 +217,24 @@ class GraphedTrainStep:
             if not self.direct or self.render_kwargs.get('geo', False) or self.render_kwargs.get('staged', False):
                 raise ValueError('GraphedTrainStep: geo_loss needs the autograd-free iteration (direct=True, the default loss_fn, scaler=None, '
                                  "optim.NGPAdam) and render_kwargs without 'geo' / 'staged'")
-        self.lookahead = bool(lookahead) and self.direct and (averager is None or (averager is optimizer and getattr(optimizer, 'shard', False)))
-        self.la = None                      # [(march graph, rest graph, loss)] x 2 once captured
-        self.la_image = None                # [image buffer] x 2 with them
+        # the sharded data-parallel update: optim.NGPAdam(shard=True) that is its own averager (it exchanges the flat gradient buffer itself)
+        self.shards = averager is optimizer and bool(getattr(optimizer, 'shard', False))
+        self.lookahead = bool(lookahead) and self.direct and (averager is None or self.shards)
         self.la_cur = 0                     # buffer set of the CURRENT batch
-        self.la_ready = [None, None]        # what is marched into each set: references to the announced tensors + versions + occupancy epoch
+        self.la_ready = [None, None]        # what is marched into each set (_Announced; None: nothing)
         self.la_hits = 0                    # steps whose march had been done ahead
+        self._precopied = None              # sharded step: the batch already copied into the static buffers (_Announced)
         self.occupancy_epoch = 0
         self.la_presampled = None           # refresh mode (full sweep?) whose cell sampling already ran on the side stream
         self.la_presample_hits = 0
         # sharded lookahead only: capture the two RCCL collectives INSIDE the rest graph (one replay per step on the main stream) instead of
         # issuing them eagerly between two replays.  Off by default: measurable here only over a 1-rank group (bench.py ddp_overhead_1rank)
         self.graph_collectives = os.environ.get('NGP_GRAPH_COLLECTIVES', '0') == '1'
-        self.la_apply = None
         # single GPU, autograd-free iteration, optim.NGPAdam: the hash table's Adam sweep rides in the grid backward's slice accumulate
         # (speculative double buffer, parity flipped by the commit: optim.NGPAdam.enable_table_fusion) -- k_adam over 12 M parameters and the
         # scale update become one small launch.  The torch Parameter is then one of two buffer sets: read it through `sync_params()`.
         self.fused_table_adam = bool(fused_table_adam) and self.direct and averager is None and hasattr(optimizer, 'enable_table_fusion')
-        self.table_fused = False      # what the captured graphs do (decided at capture time: needs the producers' non-finite sweep)
+        self.la_side = None
         if self.lookahead:
             self.la_rays_o = [torch.zeros(n_rays, 3, device=dev) for _ in range(2)]
             self.la_rays_d = [torch.zeros(n_rays, 3, device=dev) for _ in range(2)]
@@ -193,27 +253,29 @@ class GraphedTrainStep:
         the situation deterministic (tests/test_gpu_graph_lifetime.py, tools/graph_lifetime_probe.py: side stream held by a spin kernel) and
         found that the graph destruction ITSELF waits for the replay on this runtime -- no use-after-free with or without this method.  It
         stays as the explicit statement of the ordering (and for runtimes that do not wait).  Called by __del__."""
-        side = getattr(self, 'la_side', None)
+        # __del__ runs this on an object whose __init__ raised half-way as well: the ONE place where the stepper's own fields are read with
+        # getattr defaults
+        side, active, captured = getattr(self, 'la_side', None), getattr(self, 'active', _Capture()), getattr(self, '_captured', {})
+        update_graphs = getattr(self, 'update_graphs', None)
         try:
             # this object may be collected by the cyclic GC while ANOTHER stepper is inside a stream capture (ADVICE r4): a synchronize (or
             # any stream / event query) there would invalidate that capture.  The graphs and everything they replay into are parked instead
             # and released by the next close() / capture that runs outside a capture (_drain_parked)
             if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                _PARKED.append((self.graphs, self.la, self.update_graphs, side, getattr(self, 'optimizer', None), getattr(self, '_captured', None),
-                                getattr(self, 'la_apply', None), getattr(self, '_sample_pool', None), getattr(self, '_rest_pool', None)))
+                _PARKED.append(_Parked(active, captured, update_graphs, side, getattr(self, 'optimizer', None), getattr(self, '_sample_pool', None)))
                 return
             if side is not None:
                 side.synchronize()
             comm = getattr(getattr(self, 'optimizer', None), '_comm_stream', None)
             if comm is not None:
                 comm.synchronize()
-            if torch.cuda.is_available() and (self.graphs is not None or self.update_graphs):
+            if torch.cuda.is_available() and (active.graphs is not None or update_graphs):
                 torch.cuda.current_stream().synchronize()
             # the lists go before the graphs that own their buffers (this object steps through the graphs from here on)
-            for snap in [self.__dict__] + list(getattr(self, '_captured', {}).values()):
-                for cl in snap.get('lists') or ():
+            for rec in [active, *captured.values()]:
+                for cl in rec.lists or ():
                     cl.destroy()
-                snap['lists'] = None
+                rec.lists = None
             _drain_parked()
         except Exception:  # noqa: BLE001 -- interpreter shutdown: the device context may be gone already
             pass
@@ -227,17 +289,16 @@ class GraphedTrainStep:
             return None
         return ((mc + 128 + self.quantum - 1) // self.quantum) * self.quantum
 
-    _SNAP = ('graphs', 'lists', 'la', 'loss', 'image', 'la_image', 'la_apply', '_rest_pool', 'sharded', 'used_direct', 'table_fused', 'producers_check', '_checked_ok')
-
-    def _snapshot(self):
-        return {k: getattr(self, k, None) for k in self._SNAP}
+    # what the active capture holds, readable on the stepper (read-only: a capture is changed through its record)
+    graphs, lists, loss, la, la_apply, sharded, used_direct, table_fused, producers_check, _checked_ok = (
+        property(operator.attrgetter('active.' + field)) for field in
+        ('graphs', 'lists', 'loss', 'la', 'la_apply', 'sharded', 'used_direct', 'table_fused', 'producers_check', 'checked_ok'))
 
     def _activate(self, cap):
         """make the graphs captured for `cap` samples the active ones (no device work).  A batch the side stream marched ahead sits in the
         OLD capacity's buffers: it is forgotten (the next step marches its batch in line) -- a switch follows an occupancy refresh, and the
         step before a refresh does not look ahead anyway."""
-        for k, v in self._captured[cap].items():
-            setattr(self, k, v)
+        self.active = self._captured[cap]
         if cap != self.captured_capacity:
             self.n_switches += 1
         self.captured_capacity = cap
@@ -266,15 +327,7 @@ class GraphedTrainStep:
         before = self.captures
         cap = self._capacity()
         if cap is not None and self.capture_error is None and not self._fits(cap):
-            self._geo_loss_needs_direct()
-            self.captured_capacity = cap
-            try:
-                self._capture()
-            except Exception as e:  # noqa: BLE001
-                self.capture_error = repr(e)
-                self.graphs = None
-                self._captures_discarded()
-                torch.cuda.synchronize()
+            self._try_capture(cap)
         if cap is not None and self.graphs is not None and self.capture_error is None and self.capacity_ladder:
             # the ladder: graphs for the capacities the estimate may move to (each rung owns its buffers: ~2 KB per sample and buffer set)
             base = self.captured_capacity
@@ -285,8 +338,7 @@ class GraphedTrainStep:
                 # (what the optimizer recorded about the graphs that stay, should this rung fail half-way: NGPAdam.captures_discarded)
                 kept = {k: getattr(self.optimizer, k) for k in ('_poison_captured', '_poisoned') if hasattr(self.optimizer, k)}
                 try:
-                    self.captured_capacity = rung
-                    self._capture()
+                    self._capture(rung)
                 except Exception as e:  # noqa: BLE001 -- the ladder is an optimisation: keep what was captured
                     self.ladder_error = repr(e)
                     for k, v in kept.items():
@@ -314,8 +366,7 @@ class GraphedTrainStep:
         import fused
         # (sharded update: the reduce-scatter reads the flat buffer the producers wrote -- every element of it, the MLP regions through the slab
         # reduction -- so the optimizer's memset of that buffer can go as well: NGPAdam.apply(zero=False))
-        sharded = self.averager is self.optimizer and getattr(self.optimizer, 'shard', False)
-        return bool(fused.USE_OVERWRITE_TABLE and (self.averager is None or sharded))
+        return bool(fused.USE_OVERWRITE_TABLE and (self.averager is None or self.shards))
 
     def _mark_deposits(self):
         """after a replay: what the captured optimizer step left in the table's deposit buffer (Python ran only at capture time)"""
@@ -335,9 +386,8 @@ class GraphedTrainStep:
             replayed_fused_table_step(self.optimizer)
 
     def _captures_discarded(self):
-        """the graphs are dropped (a failed capture) or about to be recorded anew: the optimizer forgets what it recorded at capture time,
-        and the command lists go with the graphs"""
-        self.lists = None
+        """the graphs are dropped (a failed capture) or about to be recorded anew: the optimizer forgets what it recorded at capture time
+        (the command lists go with the record that held the graphs)"""
         fn = getattr(self.optimizer, 'captures_discarded', None)
         if fn is not None:
             fn()
@@ -401,7 +451,7 @@ class GraphedTrainStep:
         if not (self.direct and m.training and getattr(m, 'bg_radius', 0) <= 0 and hasattr(m, '_fused_render_ok')):
             return False
         # geo: the caller wants depth_raw / distortion in the render's results and its own loss on them; the direct iteration serves the
-        # geometry terms it knows through `geo_loss` (read with getattr in _iteration_args: _direct_ok does not depend on it)
+        # geometry terms it knows through `geo_loss` (_iteration_args hands it over: _direct_ok does not depend on it)
         # aux: the caller's own channels are composited on the autograd path only
         if kw.get('staged', False) or kw.get('geo', False) or kw.get('aux', None) is not None:
             return False
@@ -425,7 +475,7 @@ class GraphedTrainStep:
         args = (m, *batch, m.aabb_train, counter, self.captured_capacity, opt.scalars.narrow(0, SCALE, 1), 1 if bg is None else bg, kw.get('perturb', False),
                 kw.get('dt_gamma', 0), kw.get('max_steps', 1024), kw.get('T_thresh', 1e-4))
         return args, dict(noise_seed=seed, found_inf=opt.scalars.narrow(0, FOUND_INF, 1) if checked else None, overwrite_table=self._overwrites_table(),
-                          table_adam=opt if checked and self.table_fused else None, geo_loss=getattr(self, 'geo_loss', None))
+                          table_adam=opt if checked and self.table_fused else None, geo_loss=self.geo_loss)
 
     def _iteration_front(self):
         """zero_grad -> render -> loss -> scaled backward, with the model's bookkeeping pinned for capture"""
@@ -435,15 +485,14 @@ class GraphedTrainStep:
             self.optimizer.zero_grad(set_to_none=True)
             # single rank (or local gradients before a sharded exchange): the producers flag non-finite gradients, no separate sweep.
             # After an all-reduce the sweep has to see the REDUCED values, so the replicated data-parallel path keeps it.
-            self.producers_check = self._checked_ok and (self.averager is None)
+            self.active.producers_check = self._checked_ok and (self.averager is None)
             args, kwargs = self._iteration_args(self.producers_check)
-            loss, image = fused_train_iteration(*args, **kwargs)[:2]
-            self.image = image
-            self.used_direct = True
+            loss, self.image = fused_train_iteration(*args, **kwargs)[:2]
+            self.active.used_direct = True
             return loss[0]
         self._geo_loss_needs_direct()
-        self.used_direct = False
-        self.producers_check = False
+        self.active.used_direct = False
+        self.active.producers_check = False
         saved_counter, saved_mc, saved_ls = m._buffers['step_counter'], m.mean_count, m.local_step
         m._buffers['step_counter'] = self.counter
         m.mean_count = self.captured_capacity - 128  # march_rays_train sizes its buffers as mean_count + 128 (raymarching.py:200-203)
@@ -466,7 +515,7 @@ class GraphedTrainStep:
 
     def _geo_loss_needs_direct(self):
         """a geo_loss is served by the autograd-free iteration alone: raise where the graphs about to be captured would leave it out"""
-        if getattr(self, 'geo_loss', None) is not None and not self._direct_ok():
+        if self.geo_loss is not None and not self._direct_ok():
             raise RuntimeError('GraphedTrainStep: geo_loss needs the autograd-free iteration and this model / render configuration is not '
                                'eligible for it (GraphedTrainStep._direct_ok)')
 
@@ -478,144 +527,284 @@ class GraphedTrainStep:
         if self.scaler is not None:
             self.scaler.step(self.optimizer)
             self.scaler.update()
-        elif getattr(self, 'producers_check', False):
+        elif self.producers_check:
             self.optimizer.step(gradients_checked=True)
         else:
             self.optimizer.step()
 
-    def _capture(self):
+    def _capture(self, cap):
+        """capture the training iteration for `cap` samples into a new record, which becomes the active one and joins `_captured`"""
         # No warm-up iterations here: they would be real optimizer steps.  Everything lazily created (optimizer state,
         # GradScaler scale tensor, LDS-size attributes, device properties) exists already because capture only starts once
         # `mean_count > 0`, i.e. after >= 16 eager iterations.  Capturing does not execute: the first replay is the step.
         import gc
-        self.graphs = None
-        self.loss = None
+        self.captured_capacity = cap
+        rec = self.active = _Capture(cap)   # (what the capture bodies read -- _iteration_front, _iteration_args, _cmdlist_ok -- and fill in)
         self.image = None
         gc.collect()  # drop autograd graphs of earlier eager iterations (their AccumulateGrad nodes are stream-bound)
         torch.cuda.synchronize()
         _drain_parked()
-        self.sharded = False
+        direct = self._direct_ok()
         # (outside capture: caches the host copy of the encoder offsets the in-kernel non-finite sweep needs)
-        self._checked_ok = False
-        if self._direct_ok():
+        if direct:
             from fused import iteration_checks_gradients
-            self._checked_ok = iteration_checks_gradients(self.model)
+            rec.checked_ok = iteration_checks_gradients(self.model)
         self.sync_params()   # (outside the capture: a re-capture starts from buffer set A)
         self._captures_discarded()   # (a capture that contains poison_shards() records it again)
-        self.table_fused = False
-        if self.fused_table_adam and self._checked_ok and self._overwrites_table() and self.captured_capacity >= 16384:
+        if self.fused_table_adam and rec.checked_ok and self._overwrites_table() and cap >= 16384:
             emb = getattr(getattr(self.model, 'encoder', None), 'embeddings', None)
             if emb is not None and getattr(emb, '_ngp_fp16', None) is not None and self._table_fusion_fits(emb):
                 self.optimizer.enable_table_fusion(emb)
-                self.table_fused = True
-        self.la = None
-        self.la_image = None
+                rec.table_fused = True
         self.la_ready = [None, None]
-        if self.lookahead and self._direct_ok():
-            self._capture_lookahead()
+        # THE choice of the replay shape; each shape states its capture and its step side by side below
+        if self.lookahead and direct:
+            self._capture_lookahead(rec)
         elif self.averager is None:
-            g = torch.cuda.CUDAGraph()
-            lists = []
-            with _capture_into(g):
-                with self._recording(lists, with_march=True):
-                    self.loss = self._iteration_front().detach()
-                    self._iteration_back()
-            self.graphs = (g,)
-            self.lists = tuple(lists) or None
-        elif self.averager is self.optimizer and getattr(self.optimizer, 'shard', False) and self._direct_ok():
-            # sharded data-parallel update (optim.NGPAdam, shard=True): graphs around the two collectives,
-            #   [march] -> wait for the shadow all-gather of the previous step -> [encode .. backward, local non-finite sweep, poison]
-            #   -> reduce-scatter (carries the skip verdict) -> [verdict, Adam on my shard, commit] -> all-gather of the shadows (side stream,
-            #   overlaps the next [march]).  This is the form WITHOUT lookahead; with lookahead (the default of bench.py) the march leaves the
-            #   main stream altogether: _capture_lookahead.  (Folding the next batch's march behind the shard update -- two replays per step --
-            #   was measured over a 1-rank RCCL group and dropped: 0.607 against 0.591 ms, EXPERIMENTS.md round 5.)
-            from fused import fused_train_iteration_split
-            opt = self.optimizer
-            args, kwargs = self._iteration_args(self._checked_ok)   # (no table fusion here: it needs averager=None)
-            march, rest = fused_train_iteration_split(*args, **kwargs)
-            opt.wait_shadows()
-            torch.cuda.synchronize()
-            ga, gb, gc_ = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with _capture_into(ga):
-                march()
-            with _capture_into(gb, pool=ga.pool()):
-                out = rest()
-                self.loss, self.image = out[0][0].detach(), out[1]
-                if not self._checked_ok:
-                    opt.pre_reduce_check()     # (else the kernels that deposited the local gradients flagged them)
-                opt.poison_shards()            # found_inf -> NaN in element 0 of every shard: the reduce-scatter carries the verdict
-            with _capture_into(gc_, pool=ga.pool()):
-                opt.apply(zero=not self._overwrites_table())
-            self.graphs = (ga, gb, gc_)
-            self.sharded = True
-            self.used_direct = True
-        else:  # the RCCL all-reduce stays eager between the two halves
-            g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with _capture_into(g1):
-                self.loss = self._iteration_front().detach()
-            with _capture_into(g2, pool=g1.pool()):
-                self._iteration_back()
-            self.graphs = (g1, g2)
+            self._capture_plain(rec)
+        elif self.shards and direct:
+            self._capture_sharded(rec)
+        else:
+            self._capture_replicated(rec)
         self.n_captures += 1
-        self._captured[self.captured_capacity] = self._snapshot()
+        self._captured[cap] = rec
         while len(self._captured) > 12:   # (an estimate that wanders for a long time: drop the capacity farthest from the active one)
-            far = max((c for c in self._captured if c != self.captured_capacity), key=lambda c: abs(c - self.captured_capacity))
+            far = max((c for c in self._captured if c != cap), key=lambda c: abs(c - cap))
             _PARKED.append(self._captured.pop(far))
 
-    def _capture_lookahead(self):
+    def _try_capture(self, cap):
+        """capture for `cap` samples -> True; a capture that fails is recorded (`capture_error`: every step from here on runs eagerly), what
+        it left is dropped and the optimizer is told.  THE statement of the fallback: `step()` and `precapture()` both come through here"""
+        self._geo_loss_needs_direct()
+        try:
+            self._capture(cap)
+            return True
+        except Exception as e:  # noqa: BLE001 -- keep training eagerly; the caller can inspect .capture_error
+            self.capture_error = repr(e)
+            self.active = _Capture()
+            self._captures_discarded()
+            torch.cuda.synchronize()
+            return False
+
+    def _set_batch(self, rays_o, rays_d, target):
+        """the batch into the single buffer set: ONE multi-tensor copy kernel (three separate copies cost ~5 us each plus the gaps)"""
+        torch._foreach_copy_([self.rays_o, self.rays_d, self.target], [rays_o.view_as(self.rays_o), rays_d.view_as(self.rays_d), target],
+                             non_blocking=True)
+
+    def _count_to_ring(self, p=0, ahead=0):
+        """hand the sample count of buffer set `p` (0: also the single set) to the model's 16-slot ring exactly where the eager renderer would
+        have put it -- ahead=1: the slot the NEXT step will own"""
+        m = self.model
+        m.step_counter[(m.local_step + ahead) % 16].copy_(self.counter[p], non_blocking=True)
+
+    # ---- plain: one graph (single rank, torch.optim or optim.NGPAdam, with or without the autograd-free iteration) ---------------------
+    def _capture_plain(self, rec):
+        g = torch.cuda.CUDAGraph()
+        lists = []
+        with _capture_into(g):
+            with self._recording(lists, with_march=True):
+                rec.loss = self._iteration_front().detach()
+                self._iteration_back()
+        rec.graphs, rec.lists, rec.image, rec.replay = (g,), tuple(lists) or None, self.image, GraphedTrainStep._replay_plain
+
+    def _replay_plain(self, rays_o, rays_d, target, next_rays):
+        rec = self.active
+        (g,), (cl,) = rec.graphs, rec.lists or (None,)
+        self.image = rec.image
+        self._set_batch(rays_o, rays_d, target)
+        self._replay_rest(g, cl)
+        self._count_to_ring()
+        return rec.loss
+
+    # ---- replicated data-parallel: two graphs, the RCCL all-reduce stays eager between the two halves ------------------------------------
+    def _capture_replicated(self, rec):
+        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with _capture_into(g1):
+            rec.loss = self._iteration_front().detach()
+        with _capture_into(g2, pool=g1.pool()):
+            self._iteration_back()
+        rec.graphs, rec.image, rec.replay = (g1, g2), self.image, GraphedTrainStep._replay_replicated
+
+    def _replay_replicated(self, rays_o, rays_d, target, next_rays):
+        rec = self.active
+        front, back = rec.graphs
+        self.image = rec.image
+        self._set_batch(rays_o, rays_d, target)
+        front.replay()
+        self.averager.all_reduce()
+        back.replay()
+        self._count_to_ring()
+        return rec.loss
+
+    # ---- sharded data-parallel update (optim.NGPAdam, shard=True) without lookahead: three graphs around the two collectives -------------
+    def _capture_sharded(self, rec):
+        #   [march] -> wait for the shadow all-gather of the previous step -> [encode .. backward, local non-finite sweep, poison]
+        #   -> reduce-scatter (carries the skip verdict) -> [verdict, Adam on my shard, commit] -> all-gather of the shadows (side stream,
+        #   overlaps the next [march]).  This is the form WITHOUT lookahead; with lookahead (the default of bench.py) the march leaves the
+        #   main stream altogether: _capture_lookahead.  (Folding the next batch's march behind the shard update -- two replays per step --
+        #   was measured over a 1-rank RCCL group and dropped: 0.607 against 0.591 ms, EXPERIMENTS.md round 5.)
+        from fused import fused_train_iteration_split
+        opt = self.optimizer
+        args, kwargs = self._iteration_args(rec.checked_ok)   # (no table fusion here: it needs averager=None)
+        march, rest = fused_train_iteration_split(*args, **kwargs)
+        opt.wait_shadows()
+        torch.cuda.synchronize()
+        ga, gb, gc_ = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with _capture_into(ga):
+            march()
+        with _capture_into(gb, pool=ga.pool()):
+            losses, rec.image = rest()[:2]
+            rec.loss = losses[0].detach()
+            if not rec.checked_ok:
+                opt.pre_reduce_check()     # (else the kernels that deposited the local gradients flagged them)
+            opt.poison_shards()            # found_inf -> NaN in element 0 of every shard: the reduce-scatter carries the verdict
+        with _capture_into(gc_, pool=ga.pool()):
+            opt.apply(zero=not self._overwrites_table())
+        rec.graphs, rec.sharded, rec.used_direct, rec.replay = (ga, gb, gc_), True, True, GraphedTrainStep._replay_sharded
+
+    def _replay_sharded(self, rays_o, rays_d, target, next_rays):
+        # Eager operations between graph replays are where this step loses time (kernel trace of the 1-rank RCCL step,
+        # profiles/r05_step_timeline_ddp.txt: a replay that follows an eager kernel starts at once, an eager kernel that follows a replay
+        # waits 9-32 us), so the small copies sit BEHIND the eager reduce-scatter, where a boundary exists anyway: the sample count goes
+        # to the model's ring there, and an announced next batch (next_rays) is copied into the static buffers there -- the next step then
+        # starts with a replay right behind this step's last one.  (rays_o / rays_d are read by the march graph only, the target by the
+        # rest graph: both are done with them by then, stream order.)
+        rec, opt = self.active, self.optimizer
+        march, rest, apply = rec.graphs
+        self.image = rec.image
+        pc, self._precopied = self._precopied, None
+        if not (pc is not None and pc.holds_rays(rays_o, rays_d) and pc.holds_target(target)):
+            self._set_batch(rays_o, rays_d, target)
+        march.replay()                     # near/far + ray marching: needs no weights, overlaps the shadow all-gather of the last step
+        opt.wait_shadows()
+        rest.replay()                      # encode .. backward (deposit) + local non-finite sweep + poison
+        opt.reduce_gradients()             # reduce-scatter (average of my shard; the skip verdict rides in it)
+        self._count_to_ring()
+        if next_rays is not None and len(next_rays) > 2:
+            self._set_batch(*next_rays)
+            self._precopied = _Announced.of(*next_rays)
+        apply.replay()                     # verdict + Adam on my shard, scale / step commit, deposit buffer zeroed
+        opt.gather_shadows()               # all-gather of the fp16 shadows on the side stream
+        return rec.loss
+
+    # ---- lookahead: two buffer sets, per set a march graph and a rest graph; the next batch's march runs on a side stream --------------
+    def _capture_lookahead(self, rec):
         """two buffer sets, per set a march graph (static rays of the set -> its samples) and a rest graph (samples + target -> loss,
         gradients, optimizer step).  The march graphs allocate from their own pool: a march replays while the OTHER set's rest graph runs."""
         from fused import fused_train_iteration_split
         opt = self.optimizer
-        self.producers_check = self._checked_ok
-        pool_march, pool_rest = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
+        rec.producers_check = rec.checked_ok
+        pool_march, rec.rest_pool = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
         # data-parallel sharded update: the rest graph ends with the local non-finite sweep + poison; reduce-scatter -> [apply graph] ->
         # all-gather follow eagerly (or, graph_collectives, inside the rest graph: ONE replay per step on the main stream)
-        sharded = self.averager is opt and getattr(opt, 'shard', False)
+        sharded = self.shards
         if sharded:
             opt.wait_shadows()
             torch.cuda.synchronize()
-        la, lists, images = [], [], []
+        la, lists = [], []
         for p in range(2):
-            args, kwargs = self._iteration_args(self._checked_ok, p)   # (a sharded update has no fused table: it needs averager=None)
+            args, kwargs = self._iteration_args(rec.checked_ok, p)   # (a sharded update has no fused table: it needs averager=None)
             march, rest = fused_train_iteration_split(*args, **kwargs)
             gm, gr = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with _capture_into(gm, pool=pool_march):
                 march()
-            with _capture_into(gr, pool=pool_rest), (contextlib.nullcontext() if sharded else self._recording(lists)):
+            with _capture_into(gr, pool=rec.rest_pool), (contextlib.nullcontext() if sharded else self._recording(lists)):
                 opt.zero_grad(set_to_none=True)
-                out = rest()
-                loss, image = out[0][0].detach(), out[1]
+                losses, image = rest()[:2]
                 if not sharded:
                     self._iteration_back()
                 else:
-                    if not self._checked_ok:
+                    if not rec.checked_ok:
                         opt.pre_reduce_check()
                     opt.poison_shards()
                     if self.graph_collectives:
                         opt.reduce_gradients()
                         opt.apply(zero=not self._overwrites_table())
                         opt.gather_shadows(async_op=False)   # same stream: no fork inside the graph
-            la.append((gm, gr, loss, march, rest))   # (the closures keep the marched buffers alive)
-            images.append(image)
-        self.la_apply = None
+            la.append(_LaSet(gm, gr, losses[0].detach(), image, march, rest))
         if sharded and not self.graph_collectives:
-            self.la_apply = torch.cuda.CUDAGraph()
-            with _capture_into(self.la_apply, pool=pool_rest):
+            rec.la_apply = torch.cuda.CUDAGraph()
+            with _capture_into(rec.la_apply, pool=rec.rest_pool):
                 opt.apply(zero=not self._overwrites_table())
-        self.la = la
-        self.la_image = images   # per set: the static image buffer its rest chain writes
-        self.graphs = tuple(g for e in la for g in e[:2])
-        self.lists = tuple(lists) or None
-        where = MARCH_MARKS[self.march_at]
-        if self.lists and where is not None:
-            for cl in self.lists:   # the event behind (before) the named launch: the side stream's march of the next batch waits for it
-                at = [i for i, n in enumerate(cl.names()) if where[0] in n]
+        rec.la, rec.graphs, rec.lists = la, tuple(g for s in la for g in (s.march_graph, s.rest_graph)), tuple(lists) or None
+        if rec.lists and MARCH_MARKS[self.march_at] is not None:
+            kernel, behind = MARCH_MARKS[self.march_at]
+            for cl in rec.lists:   # the event behind (before) the named launch: the side stream's march of the next batch waits for it
+                at = [i for i, n in enumerate(cl.names()) if kernel in n]
                 if not at:
-                    raise RuntimeError(f'GraphedTrainStep: NGP_STEP_MARCH_AT={self.march_at}: no {where[0]} launch in the recorded chain')
-                cl.mark(MARCH_MARK_ID, at[-1] + where[1])
-        self._rest_pool = pool_rest
-        self.used_direct = True
+                    raise RuntimeError(f'GraphedTrainStep: NGP_STEP_MARCH_AT={self.march_at}: no {kernel} launch in the recorded chain')
+                cl.mark(MARCH_MARK_ID, max(at) + behind)
+        rec.used_direct, rec.replay = True, GraphedTrainStep._replay_lookahead
+
+    def _replay_lookahead(self, rays_o, rays_d, target, next_rays):
+        m, rec = self.model, self.active
+        p = self.la_cur
+        q = 1 - p
+        cur = rec.la[p]
+        self.image = cur.image   # (this set's static image buffer: written by the rest chain replayed below)
+        main = torch.cuda.current_stream()
+        ready, self.la_ready[p] = self.la_ready[p], None
+        if ready is not None:
+            # hit or miss: whatever the side stream was asked to march into set p (its copies into la_rays_*/la_seed[p], the replay of
+            # gm_p, the ring-slot hand-over) must have finished before this stream reads OR overwrites that set
+            main.wait_event(self.la_event[p])
+        if ready is not None and ready.holds_rays(rays_o, rays_d, self.occupancy_epoch):
+            if not ready.holds_target(target):      # the target was not announced with the rays: copy it now
+                self.la_target[p].copy_(target, non_blocking=True)
+            self.la_hits += 1                       # the march of this batch ran on the side stream during the previous step
+        else:
+            torch._foreach_copy_([self.la_rays_o[p], self.la_rays_d[p], self.la_target[p]],
+                                 [rays_o.view_as(self.la_rays_o[p]), rays_d.view_as(self.la_rays_d[p]), target], non_blocking=True)
+            self.la_seed[p:p + 1].fill_(self.global_step)
+            cur.march_graph.replay()
+            self._count_to_ring(p)
+            if self.la_slot_event is None:
+                self.la_slot_event = torch.cuda.Event()
+            self.la_slot_event.record(main)
+        ahead = next_rays is not None and (self.global_step + 1) % self.update_interval != 0
+        cl = rec.lists[p] if rec.lists else None
+        # a marked list: the main chain goes first and the side stream waits for the mark inside it -- later than the step boundary, never
+        # earlier (set q was read by the previous step's chain, which `main` holds in front of this one)
+        early = ahead and cl is not None and MARCH_MARKS[self.march_at] is not None
+        if early:
+            self._replay_rest(cur.rest_graph, cl)
+        if ahead:
+            side = self.la_side
+            if early:
+                cl.wait_mark(MARCH_MARK_ID, side.cuda_stream)
+            else:
+                side.wait_stream(main)              # set q was read by the previous step's rest graph, queued on `main` before this point
+            with torch.cuda.stream(side):
+                no, nd, *nt = next_rays             # the next target too, where it is given: its copy leaves the main stream as well
+                dst, src = [self.la_rays_o[q], self.la_rays_d[q]], [no.view_as(self.la_rays_o[q]), nd.view_as(self.la_rays_d[q])]
+                torch._foreach_copy_(dst + [self.la_target[q]] * len(nt), src + nt, non_blocking=True)
+                self.la_seed[q:q + 1].fill_(self.global_step + 1)
+                rec.la[q].march_graph.replay()
+                self._count_to_ring(q, ahead=1)     # the sample count of the next step goes to the model's ring from here
+                self.la_event[q].record(side)
+            self.la_ready[q] = _Announced.of(no, nd, *nt, epoch=self.occupancy_epoch)
+        elif (self.global_step + 1) % self.update_interval == 0 and self.graph_updates and self.update_capture_error is None:
+            # the next step starts with an occupancy refresh: its weight-independent half (which cells, where inside them) runs here instead
+            full = m.iter_density < 16
+            entry = self.update_graphs.get(full)
+            if entry is not None and entry.sampling is not None:
+                side = self.la_side
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    entry.sampling.replay()
+                    self.la_sample_event.record(side)
+                self.la_presampled = full
+        if rec.la_apply is not None:           # sharded update, eager collectives: [rest] -> reduce-scatter -> [apply] -> all-gather (side stream)
+            opt = self.optimizer
+            opt.wait_shadows()
+            cur.rest_graph.replay()
+            opt.reduce_gradients()
+            rec.la_apply.replay()       # (issued eagerly instead -- one replay boundary less, three eager launches more: 0.530 against 0.516 ms, EXPERIMENTS.md)
+            opt.gather_shadows()
+        elif not early:
+            self._replay_rest(cur.rest_graph, cl)
+        self.la_cur = q
+        return cur.loss
 
     def _capture_update(self, full):
         """record the occupancy refresh into graphs of its own (nothing executes); False when capture is not possible.  Lookahead mode
@@ -635,20 +824,21 @@ class GraphedTrainStep:
                 raymarching.density_grid_state(m.density_grid, m.__dict__.setdefault('_refresh_state', {}))
             if self.la is not None and hasattr(m, 'refresh_sample'):
                 gs, ga = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                if getattr(self, '_sample_pool', None) is None:
+                if self._sample_pool is None:
                     self._sample_pool = torch.cuda.graph_pool_handle()
                 with _capture_into(gs, pool=self._sample_pool):
                     samples = m.refresh_sample(full=full)
-                with _capture_into(ga, pool=self._rest_pool):
+                with _capture_into(ga, pool=self.active.rest_pool):
                     with torch.autocast('cuda', dtype=self.autocast_dtype):
                         mean = m.refresh_apply(samples)
-                self.update_graphs[full] = (ga, mean, gs, samples)
+                self.update_graphs[full] = _Refresh(ga, mean, gs, samples)
             else:
                 g = torch.cuda.CUDAGraph()
-                with _capture_into(g, pool=self.graphs[0].pool()):
+                first, *_ = self.graphs   # (the refresh joins the pool of the active capture's first graph)
+                with _capture_into(g, pool=first.pool()):
                     with torch.autocast('cuda', dtype=self.autocast_dtype):
                         mean = m.refresh_occupancy(full=full)
-                self.update_graphs[full] = (g, mean)
+                self.update_graphs[full] = _Refresh(g, mean)
             self.n_update_captures += 1
             return True
         except Exception as e:  # noqa: BLE001 -- keep refreshing eagerly; the caller can inspect .update_capture_error
@@ -684,26 +874,23 @@ class GraphedTrainStep:
                 mean_count = int(m.step_counter[:used, 0].sum().item() / used)
         if use_graph:
             entry = self.update_graphs[full]
-            g, mean = entry[0], entry[1]
-            if len(entry) == 4:                      # split refresh: the sampling half may already have run under the previous iteration
+            mean = entry.mean
+            if entry.sampling is not None:           # split refresh: the sampling half may already have run under the previous iteration
                 if self.la_presampled == full:
                     torch.cuda.current_stream().wait_event(self.la_sample_event)
                     self.la_presample_hits += 1
                 else:
-                    entry[2].replay()
+                    entry.sampling.replay()
                 self.la_presampled = None
-            g.replay()
+            entry.graph.replay()
         else:
             with torch.autocast('cuda', dtype=self.autocast_dtype):
                 mean = refresh(full=full)
-        if mean_count is not None:
-            m.finish_update(mean, mean_count=mean_count)
-        else:
-            m.finish_update(mean)
+        m.finish_update(mean, mean_count=mean_count)   # (None: the model reads the ring itself)
 
     def _eager(self, rays_o, rays_d, target):
         self.optimizer.zero_grad(set_to_none=True)
-        geo = getattr(self, 'geo_loss', None)
+        geo = self.geo_loss
         with torch.autocast('cuda', dtype=self.autocast_dtype):
             if geo is None:
                 out = self.model.render(rays_o, rays_d, **self.render_kwargs)
@@ -721,94 +908,17 @@ class GraphedTrainStep:
         return loss.detach()
 
     # ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _announced(ready, rays_o, rays_d, epoch):
-        """is the batch marched into a buffer set THIS batch?  `ready` = (rays_o, rays_d, versions, occupancy epoch, target, target version)
-        holds REFERENCES to the announced tensors, compared by identity: a freed tensor's address can be handed out again by the
-        caching allocator (same data_ptr, fresh _version 0), which an address/version key would take for a hit."""
-        return (ready is not None and ready[0] is rays_o and ready[1] is rays_d and ready[2] == (rays_o._version, rays_d._version)
-                and ready[3] == epoch)
-
-    def _step_lookahead(self, rays_o, rays_d, target, next_rays):
-        m = self.model
-        p = self.la_cur
-        gm, gr, loss = self.la[p][:3]
-        images = getattr(self, 'la_image', None)
-        if images is not None:
-            self.image = images[p]   # (this set's static image buffer: written by the rest chain replayed below)
-        main = torch.cuda.current_stream()
-        ready = self.la_ready[p]
-        hit = self._announced(ready, rays_o, rays_d, self.occupancy_epoch)
-        slot = m.step_counter[m.local_step % 16]
-        if ready is not None:
-            # hit or miss: whatever the side stream was asked to march into set p (its copies into la_rays_*/la_seed[p], the replay of
-            # gm_p, the ring-slot hand-over) must have finished before this stream reads OR overwrites that set
-            main.wait_event(self.la_event[p])
-        if hit:
-            if not (ready[4] is target and ready[5] == target._version):   # the target was not announced with the rays: copy it now
-                self.la_target[p].copy_(target, non_blocking=True)
-            self.la_hits += 1                       # the march of this batch ran on the side stream during the previous step
-        else:
-            torch._foreach_copy_([self.la_rays_o[p], self.la_rays_d[p], self.la_target[p]],
-                                 [rays_o.view_as(self.la_rays_o[p]), rays_d.view_as(self.la_rays_d[p]), target], non_blocking=True)
-            self.la_seed[p:p + 1].fill_(self.global_step)
-            gm.replay()
-            slot.copy_(self.counter[p], non_blocking=True)
-            if self.la_slot_event is None:
-                self.la_slot_event = torch.cuda.Event()
-            self.la_slot_event.record(main)
-        self.la_ready[p] = None
-        q = 1 - p
-        ahead = next_rays is not None and (self.global_step + 1) % self.update_interval != 0
-        cl = self.lists[p] if self.lists else None
-        # a marked list: the main chain goes first and the side stream waits for the mark inside it -- later than the step boundary, never
-        # earlier (set q was read by the previous step's chain, which `main` holds in front of this one)
-        early = ahead and cl is not None and MARCH_MARKS[self.march_at] is not None
-        if early:
-            self._replay_rest(gr, cl)
-        if ahead:
-            side = self.la_side
-            if early:
-                cl.wait_mark(MARCH_MARK_ID, side.cuda_stream)
-            else:
-                side.wait_stream(main)              # set q was read by the previous step's rest graph, queued on `main` before this point
-            with torch.cuda.stream(side):
-                no, nd = next_rays[0], next_rays[1]
-                dst, src = [self.la_rays_o[q], self.la_rays_d[q]], [no.view_as(self.la_rays_o[q]), nd.view_as(self.la_rays_d[q])]
-                nt, ntv = None, None
-                if len(next_rays) > 2:              # the next target too: its copy leaves the main stream as well
-                    dst.append(self.la_target[q])
-                    src.append(next_rays[2])
-                    nt, ntv = next_rays[2], next_rays[2]._version
-                torch._foreach_copy_(dst, src, non_blocking=True)
-                self.la_seed[q:q + 1].fill_(self.global_step + 1)
-                self.la[q][0].replay()
-                # the sample count of the next step goes to the model's ring from here (the slot the next step will own)
-                m.step_counter[(m.local_step + 1) % 16].copy_(self.counter[q], non_blocking=True)
-                self.la_event[q].record(side)
-            self.la_ready[q] = (no, nd, (no._version, nd._version), self.occupancy_epoch, nt, ntv)
-        elif (self.global_step + 1) % self.update_interval == 0 and self.graph_updates and self.update_capture_error is None:
-            # the next step starts with an occupancy refresh: its weight-independent half (which cells, where inside them) runs here instead
-            full = m.iter_density < 16
-            entry = self.update_graphs.get(full)
-            if entry is not None and len(entry) == 4:
-                side = self.la_side
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    entry[2].replay()
-                    self.la_sample_event.record(side)
-                self.la_presampled = full
-        if self.la_apply is not None:          # sharded update, eager collectives: [rest] -> reduce-scatter -> [apply] -> all-gather (side stream)
-            opt = self.optimizer
-            opt.wait_shadows()
-            gr.replay()
-            opt.reduce_gradients()
-            self.la_apply.replay()      # (issued eagerly instead -- one replay boundary less, three eager launches more: 0.530 against 0.516 ms, EXPERIMENTS.md)
-            opt.gather_shadows()
-        elif not early:
-            self._replay_rest(gr, cl)
-        self.la_cur = q
-        return loss
+    def _ready_for(self, cap):
+        """make a capture that serves an estimate of `cap` samples the active one: the active one where it still fits, else another captured
+        capacity (a switch: no capture, no device work), else a new capture.  False: nothing is captured, the step runs eagerly"""
+        if self._fits(cap):
+            return True
+        pick = self._pick_captured(cap)
+        if pick is None:
+            return self._try_capture(cap)
+        if pick != self.captured_capacity:
+            self._activate(pick)
+        return True
 
     def step(self, rays_o, rays_d, target, next_rays=None):
         """one training iteration on rays_o/rays_d [1,N,3], target [N,3]; returns the (device) loss of this step.  Afterwards `self.image` is
@@ -825,80 +935,15 @@ class GraphedTrainStep:
             self.occupancy_epoch += 1
             if self.after_update is not None:
                 self.after_update(m)
-        cap = self._capacity()
-        self.capacity = cap
-        if cap is None:
+        self.capacity = cap = self._capacity()
+        # eager: no sample estimate yet, or a capture failed (now or earlier: stay on the eager path)
+        if cap is None or self.capture_error is not None or not self._ready_for(cap):
             loss = self._eager(rays_o, rays_d, target)
-            self.global_step += 1
-            return loss
-        if self.capture_error is not None:  # an earlier capture failed: stay on the eager path
-            loss = self._eager(rays_o, rays_d, target)
-            self.global_step += 1
-            return loss
-        pick = None if self._fits(cap) else self._pick_captured(cap)
-        if pick is not None:
-            if pick != self.captured_capacity:
-                self._activate(pick)     # another captured capacity serves this estimate: no capture, no device work
-        elif not self._fits(cap):
-            self._geo_loss_needs_direct()
-            self.captured_capacity = cap
-            try:
-                self._capture()
-            except Exception as e:  # noqa: BLE001 -- keep training eagerly; the caller can inspect .capture_error
-                self.capture_error = repr(e)
-                self.graphs = None
-                self._captures_discarded()
-                torch.cuda.synchronize()
-                loss = self._eager(rays_o, rays_d, target)
-                self.global_step += 1
-                return loss
-        self.capacity = self.captured_capacity
-        self._clean_deposits()
-        if self.la is not None:
-            loss = self._step_lookahead(rays_o, rays_d, target, next_rays)
+        else:
+            self.capacity = self.captured_capacity
+            self._clean_deposits()
+            loss = self.active.replay(self, rays_o, rays_d, target, next_rays)
             self._after_replay()
-            m.local_step += 1
-            self.global_step += 1
-            return loss
-        if getattr(self, 'sharded', False):
-            # Eager operations between graph replays are where this step loses time (kernel trace of the 1-rank RCCL step,
-            # profiles/r05_step_timeline_ddp.txt: a replay that follows an eager kernel starts at once, an eager kernel that follows a replay
-            # waits 9-32 us), so the small copies sit BEHIND the eager reduce-scatter, where a boundary exists anyway: the sample count goes
-            # to the model's ring there, and an announced next batch (next_rays) is copied into the static buffers there -- the next step then
-            # starts with a replay right behind this step's last one.  (rays_o / rays_d are read by the march graph only, the target by the
-            # rest graph: both are done with them by then, stream order.)
-            opt = self.optimizer
-            pc = getattr(self, '_precopied', None)
-            self._precopied = None
-            if not (pc is not None and pc[0] is rays_o and pc[1] is rays_d and pc[2] is target
-                    and pc[3] == (rays_o._version, rays_d._version, target._version)):
-                torch._foreach_copy_([self.rays_o, self.rays_d, self.target], [rays_o.view_as(self.rays_o), rays_d.view_as(self.rays_d), target],
-                                     non_blocking=True)
-            self.graphs[0].replay()            # near/far + ray marching: needs no weights, overlaps the shadow all-gather of the last step
-            opt.wait_shadows()
-            self.graphs[1].replay()            # encode .. backward (deposit) + local non-finite sweep + poison
-            opt.reduce_gradients()             # reduce-scatter (average of my shard; the skip verdict rides in it)
-            m.step_counter[m.local_step % 16].copy_(self.counter[0], non_blocking=True)
-            if next_rays is not None and len(next_rays) > 2:
-                no, nd, nt = next_rays[0], next_rays[1], next_rays[2]
-                torch._foreach_copy_([self.rays_o, self.rays_d, self.target], [no.view_as(self.rays_o), nd.view_as(self.rays_d), nt], non_blocking=True)
-                self._precopied = (no, nd, nt, (no._version, nd._version, nt._version))
-            self.graphs[2].replay()            # verdict + Adam on my shard, scale / step commit, deposit buffer zeroed
-            opt.gather_shadows()               # all-gather of the fp16 shadows on the side stream
-            self._after_replay()
-            m.local_step += 1
-            self.global_step += 1
-            return self.loss
-        # the batch into the static input buffers: ONE multi-tensor copy kernel (three separate copies cost ~5 us each plus the gaps)
-        torch._foreach_copy_([self.rays_o, self.rays_d, self.target], [rays_o.view_as(self.rays_o), rays_d.view_as(self.rays_d), target],
-                             non_blocking=True)
-        self._replay_rest(self.graphs[0], self.lists[0] if self.lists else None)
-        if len(self.graphs) == 2:
-            self.averager.all_reduce()
-            self.graphs[1].replay()
-        self._after_replay()
-        # hand the sample count to the model's 16-slot ring exactly where the eager renderer would have put it
-        m.step_counter[m.local_step % 16].copy_(self.counter[0], non_blocking=True)
-        m.local_step += 1
+            m.local_step += 1    # (the eager render counts its own steps)
         self.global_step += 1
-        return self.loss
+        return loss
