@@ -1053,6 +1053,58 @@ int ngp_sdf_sigmas_backward_f64(const double* grad_sigmas, const double* sdf, co
                                 const double* inv_s, uint32_t M, float cos_anneal, double* grad_sdf, double* grad_normals, double* grad_dirs,
                                 double* grad_inv_s, void* workspace, size_t workspace_bytes, ngp_stream_t stream);
 
+/* ---- mesh extraction: naive surface nets and the occupancy-culled lattice (csrc/surface_nets.hip) ----
+ * Replaces the reference's save_mesh (nerf/utils.py: a dense torch volume, then mcubes / trimesh on the host).  Surface nets: one vertex per
+ * sign-changing cell, one quad per sign-changing lattice edge -- no case table, an indexed mesh with shared vertices, fully deterministic.
+ * Volume and sign: volume f[z][y][x], fp32, contiguous, nx, ny, nz >= 2, nx * ny * nz < 2^31.  s = f - level (inside_below != 0, as for an
+ *   SDF: s = level - f).  A lattice point is inside iff s > 0; NaN and s == 0 count as outside.
+ * Cells and vertices: cell (i, j, k), 0 <= i < nx - 1 (likewise j, k), spans the lattice points (i..i+1, j..j+1, k..k+1) and is active iff its
+ *   eight corners are neither all inside nor all outside.  Vertices are numbered by an exclusive scan of the active flags in linear cell
+ *   order (k (ny - 1) + j) (nx - 1) + i.  The vertex of an active cell is the mean of the crossing points of its sign-changing edges (3 to 12):
+ *   on the edge from corner a to b = a + e_axis the crossing is a + t e_axis, t = s_a / (s_a - s_b) clamped to [0, 1], a non-finite t
+ *   replaced by 0.5 (fp32).  The terms are added in cell-local coordinates (every term in [0, 1]^3) in a fixed order -- the x-edges, the
+ *   y-edges, the z-edges, each four with the lower of the two other axes running fastest --, divided by their number, the integer cell
+ *   coordinate is added, and the world position is fma(lattice, h, o) per axis.
+ * Faces: axes (a, b, c) a cyclic triple of (x, y, z).  The lattice edge p -> p + e_a emits one quad iff it is interior, 1 <= p_b <= N_b - 2 and
+ *   1 <= p_c <= N_c - 2, and inside(p) != inside(p + e_a).  Its corners are the vertices of the cells q0 = p - e_b - e_c, q1 = p - e_c,
+ *   q2 = p, q3 = p - e_b; p inside: triangles (q0, q1, q2), (q0, q2, q3), else (q0, q3, q2), (q0, q2, q1): normals point from inside to
+ *   outside.  Faces are ordered by (linear lattice index of p) * 3 + a, two triangles each, int32 indices.  A surface that leaves the box is
+ *   left open there: nothing is emitted on boundary edges.
+ * ngp_surface_nets_count: counts_dev[0] = V, counts_dev[1] = the number of triangles (device words; 0xFFFFFFFF: does not fit int32), and
+ *   the scanned per-workgroup counts in the workspace.  ngp_surface_nets_emit, with the SAME volume, level, sense and workspace, after it on
+ *   the stream: the flags are recomputed (no mask volume), the cell -> vertex map and vertices [V,3] are written, then -- a later launch --
+ *   faces [F,3].  Every store is bounded by v_cap / f_cap (rows) on the device; the entry then reads the two counts back (it synchronises
+ *   the stream: an export op, neither capturable nor recordable) and returns NGP_ERR_INVALID ("truncated") when a capacity is below its
+ *   count -- a caller with stale counts gets a truncated mesh and an error, never a write past its buffers.  No atomics: the output order
+ *   is the scans' order, the same bits on every run.
+ * workspace: ngp_surface_nets_workspace_bytes(nx, ny, nz) bytes (monotone in each dimension; 0 for refused dimensions), 4-byte aligned: the
+ *   int32 cell -> vertex map, one word per lattice point, and two scan words per workgroup of 256 lattice points.
+ * NGP_ERR_INVALID before any device work: a NULL pointer, a dimension below 2, nx * ny * nz >= 2^31, a zero capacity (an empty mesh needs no
+ *   emit). */
+size_t ngp_surface_nets_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int ngp_surface_nets_count(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, float level, int inside_below, void* workspace,
+                           uint32_t* counts_dev, ngp_stream_t stream);
+int ngp_surface_nets_emit(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, float level, int inside_below, float ox, float oy, float oz,
+                          float hx, float hy, float hz, void* workspace, float* vertices, uint32_t v_cap, int32_t* faces, uint32_t f_cap,
+                          ngp_stream_t stream);
+/* the lattice points of the z-range [z0, z1) of an nx x ny x . lattice that lie near occupied space, compacted in lattice order: where an
+ * extraction has to evaluate the field at all.  Point (i, j, k) has the world position fma(i, h, o) per axis and the linear index
+ * (k ny + j) nx + i in the whole lattice (int32: nx * ny * z1 < 2^31).  Its cascade is the marcher's position term alone,
+ * mip_exponent(max |x|, cascade - 1) (`lp` of probe_geom, raymarching.hip), its cell probe_geom's index statement at that cascade (positions
+ * outside the cascade's box fall into its boundary cells).  The point is kept iff one of the (2 dilate + 1)^3 cells around its own cell at
+ * that cascade has its bit set in `bitfield` (the layout of ngp_packbits; neighbour coordinates clamped to [0, grid_size - 1]); dilate in
+ * [0, 4].  bitfield == NULL: every point is kept (bound, cascade, grid_size, dilate are not looked at).
+ * Output: points [K,3] fp32, index [K] int32 and count_dev[0] = K, by the flag / scan / compact scheme of the extraction (no atomics, the same
+ * bits on every run).  Stores are bounded by `capacity` (rows); K is the full count, so K > capacity tells the caller the output is cut.
+ * workspace: ngp_lattice_points_workspace_bytes(nx, ny, z1 - z0) bytes, 4-byte aligned (one scan word per workgroup of 256 points) -- the
+ * compaction across workgroups needs it like every scan of this library; contents irrelevant before and after.
+ * NGP_ERR_INVALID before any device work: a NULL pointer (other than bitfield), an empty lattice or slab, nx * ny * z1 >= 2^31, zero capacity;
+ * with a bitfield: bound <= 0, cascade outside [1, 8], grid_size not a power of two in [1, 1024], dilate > 4. */
+size_t ngp_lattice_points_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz_slab);
+int ngp_lattice_points(float ox, float oy, float oz, float hx, float hy, float hz, uint32_t nx, uint32_t ny, uint32_t z0, uint32_t z1,
+                       const uint8_t* bitfield, float bound, uint32_t cascade, uint32_t grid_size, uint32_t dilate, void* workspace, float* points,
+                       int32_t* index, uint32_t* count_dev, uint32_t capacity, ngp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,10 @@ _SIGNATURES = {
     'ngp_sdf_sigmas_backward': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     'ngp_sdf_sigmas_forward_f64': [_vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp],
     'ngp_sdf_sigmas_backward_f64': [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    # mesh extraction (csrc/surface_nets.hip): surface nets over a volume, and the occupancy-culled lattice that fills it
+    'ngp_surface_nets_count': [_vp, _u32, _u32, _u32, _f32, _i32, _vp, _vp, _vp],
+    'ngp_surface_nets_emit': [_vp, _u32, _u32, _u32, _f32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _u32, _vp, _u32, _vp],
+    'ngp_lattice_points': [_f32, _f32, _f32, _f32, _f32, _f32, _u32, _u32, _u32, _u32, _vp, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp],
 }
 for _name, _args in _SIGNATURES.items():
     _fn = getattr(lib, _name)
@@ -210,6 +214,10 @@ lib.ngp_linear_stack_flat_size.restype = _u32
 lib.ngp_density_grid_update_workspace_bytes.restype = _sz
 lib.ngp_sdf_sigmas_workspace_bytes.argtypes = [_u32]
 lib.ngp_sdf_sigmas_workspace_bytes.restype = _sz
+lib.ngp_surface_nets_workspace_bytes.argtypes = [_u32, _u32, _u32]
+lib.ngp_surface_nets_workspace_bytes.restype = _sz
+lib.ngp_lattice_points_workspace_bytes.argtypes = [_u32, _u32, _u32]
+lib.ngp_lattice_points_workspace_bytes.restype = _sz
 
 if lib.ngp_abi_version() != ABI_VERSION:
     raise ImportError(f"{LIB_PATH}: ABI version {lib.ngp_abi_version()} != expected {ABI_VERSION}; rebuild the extension")
@@ -220,7 +228,8 @@ EXPORTED = sorted(list(_SIGNATURES) + ['ngp_last_error', 'ngp_target_arch', 'ngp
                                        'ngp_ffmlp_backward_slab_count', 'ngp_density_grid_update_workspace_bytes', 'ngp_grid_forward_work_lists', 'ngp_coarse_occupancy_bytes',
                                        'ngp_grid_table_adam_prefix', 'ngp_linear_stack_flat_size',
                                        'ngp_grid_backward_backward_workspace_bytes', 'ngp_ffmlp_backward_backward_workspace_bytes',
-                                       'ngp_grid_ordered_workspace_bytes', 'ngp_sdf_sigmas_workspace_bytes'])
+                                       'ngp_grid_ordered_workspace_bytes', 'ngp_sdf_sigmas_workspace_bytes',
+                                       'ngp_surface_nets_workspace_bytes', 'ngp_lattice_points_workspace_bytes'])
 
 
 def check(rc):

@@ -96,6 +96,28 @@ class NeuSNetwork(NeRFRenderer):
             inv_s = self.inv_s
             return {'sigma': inv_s * torch.sigmoid(-inv_s * sdf)}
 
+    # extract_mesh contours the SDF itself (not the density the occupancy refresh sees): level 0, inside below it, and a lattice point the
+    # occupancy cull skipped counts as outside (+1)
+    mesh_level, mesh_inside_below, mesh_fill = 0.0, True, 1.0
+
+    def _mesh_values(self, pts):
+        return self._sdf_head(pts, False)[0].float()
+
+    def extract_mesh(self, *args, normals=False, **kwargs):
+        """NeRFRenderer.extract_mesh on the SDF; normals=True appends the unit normals at the vertices [V,3] (the SDF's gradient through
+        sdf_and_normal, normalised)"""
+        out = super().extract_mesh(*args, **kwargs)
+        if not normals:
+            return out
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.autocast('cuda', dtype=torch.float16, enabled=out[0].is_cuda):
+                n = torch.cat([self.sdf_and_normal(part)[1].float() for part in out[0].split(1 << 20)]) if out[0].shape[0] else out[0].clone()
+        finally:
+            self.train(was_training)
+        return (*out, torch.nn.functional.normalize(n, dim=-1))
+
     def get_params(self, lr):
         groups = [{'params': m.parameters(), 'lr': lr} for m in (self.encoder, self.sdf_net, self.encoder_dir, self.color_net)]
         return groups + [{'params': [self.log_inv_s], 'lr': lr}]

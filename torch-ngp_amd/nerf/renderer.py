@@ -509,6 +509,59 @@ class NeRFRenderer(nn.Module):
             return
         self.finish_update(self.refresh_occupancy(decay, S))
 
+    # -- mesh extraction (extension) ---------------------------------------------
+    # the scalar field extract_mesh contours: density(x)['sigma'] * density_scale, inside ABOVE the level (default 10, the reference's
+    # save_mesh threshold), unevaluated lattice points hold 0.  A model with another field overrides the three attributes and _mesh_values
+    # (network_sdf.py).
+    mesh_level, mesh_inside_below, mesh_fill = 10.0, False, 0.0
+
+    def _mesh_values(self, pts):
+        return self._query_sigma(pts).float()
+
+    @torch.no_grad()
+    def mesh_volume(self, dims, lo, hi, cull=True, fill=None, slab_points=2 ** 24):
+        """the fill of extract_mesh alone: the model's field on the lattice dims = (nx, ny, nz) over [lo, hi] -> (volume [nz,ny,nx] fp32, the
+        number of lattice points evaluated).  z-slab by z-slab of at most `slab_points` points: raymarching.lattice_points names the points
+        (cull: those within one occupancy cell of a set bit of density_bitfield; else all), the field is evaluated on them in eval mode under
+        fp16 autocast (the numerics a frame is rendered with) and scattered by index into a volume prefilled with `fill`."""
+        if cull and not self.cuda_ray:
+            raise RuntimeError("extract_mesh(cull=True) reads the occupancy bitfield of a cuda_ray model; pass cull=False")
+        nx, ny, nz = dims
+        dev = self.aabb_train.device
+        volume = torch.full((nz, ny, nx), float(self.mesh_fill if fill is None else fill), dtype=torch.float32, device=dev)
+        flat = volume.view(-1)
+        slab = max(1, int(slab_points) // (nx * ny))
+        bits = self.density_bitfield if cull else None
+        evaluated = 0
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.autocast('cuda', dtype=torch.float16, enabled=dev.type == 'cuda'):
+                for z0 in range(0, nz, slab):
+                    pts, index = raymarching.lattice_points(lo, hi, dims, z0, min(z0 + slab, nz), bits, self.bound, self.cascade, self.grid_size,
+                                                            1, device=dev)
+                    if pts.shape[0]:
+                        flat[index.long()] = self._mesh_values(pts).reshape(-1)
+                        evaluated += pts.shape[0]
+        finally:
+            self.train(was_training)
+        return volume, evaluated
+
+    def extract_mesh(self, resolution=256, level=None, lo=None, hi=None, cull=True, fill=None, slab_points=2 ** 24, return_volume=False):
+        """the level set of the model's field as an indexed triangle mesh -> (vertices [V,3] fp32 world positions, faces [F,3] int32), plus
+        the volume [nz,ny,nx] with return_volume.  The field is evaluated on the lattice of `resolution` (an int or (nx, ny, nz)) points
+        spanning [lo, hi] (default +-bound) by mesh_volume -- cull=True: only near occupied space, which needs cuda_ray -- and contoured by
+        raymarching.surface_nets at `level` (default: the model's mesh_level).  No gradient."""
+        dims = [int(resolution)] * 3 if not hasattr(resolution, '__len__') else [int(n) for n in resolution]
+        if len(dims) != 3 or min(dims) < 2:
+            raise ValueError(f"extract_mesh: resolution must be an int or (nx, ny, nz), each at least 2 (got {resolution})")
+        lo = -self.bound if lo is None else lo
+        hi = self.bound if hi is None else hi
+        volume, _ = self.mesh_volume(dims, lo, hi, cull, fill, slab_points)
+        origin, spacing = raymarching.lattice_frame(lo, hi, dims)
+        vertices, faces = raymarching.surface_nets(volume, self.mesh_level if level is None else level, self.mesh_inside_below, origin, spacing)
+        return (vertices, faces, volume) if return_volume else (vertices, faces)
+
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
         """renderer.py:540-574: run_cuda with cuda_ray (never staged), else `run`, in ray batches of `max_ray_batch` when staged"""
         if kwargs.get('aux') is not None and (staged or not self.cuda_ray):

@@ -190,3 +190,33 @@ def pose_rays(poses, intrinsics, H, W, inds=None):
         inds = inds.to(poses.device).contiguous()
     n = H * W if inds is None else inds.shape[-1]
     return _pose_rays.apply(poses, fx, fy, cx, cy, int(W), inds, n)
+
+
+def save_mesh(path, vertices, faces, normals=None):
+    """write an indexed triangle mesh as a binary little-endian PLY with numpy alone (the reference's save_mesh needs trimesh): vertices
+    [V,3] float32 (x, y, z), optional normals [V,3] float32 (nx, ny, nz), faces [F,3] int32 as `list uchar int vertex_indices`.  Tensors
+    (any device) or arrays."""
+    import numpy as np
+
+    def host(a, dtype, what):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"save_mesh: {what} must be [n,3] (got {a.shape})")
+        return np.ascontiguousarray(a, dtype)
+    v, f = host(vertices, '<f4', 'vertices'), host(faces, '<i4', 'faces')
+    names = ['x', 'y', 'z']
+    if normals is not None:
+        n = host(normals, '<f4', 'normals')
+        if len(n) != len(v):
+            raise ValueError(f"save_mesh: {len(n)} normals for {len(v)} vertices")
+        v, names = np.concatenate([v, n], axis=1), names + ['nx', 'ny', 'nz']
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError("save_mesh: a face names a vertex that does not exist")
+    header = ['ply', 'format binary_little_endian 1.0', f'element vertex {len(v)}'] + [f'property float {n}' for n in names] + \
+             [f'element face {len(f)}', 'property list uchar int vertex_indices', 'end_header']
+    rows = np.empty(len(f), dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    rows['n'], rows['v'] = 3, f
+    with open(path, 'wb') as out:
+        out.write(('\n'.join(header) + '\n').encode('ascii'))
+        out.write(v.tobytes())
+        out.write(rows.tobytes())

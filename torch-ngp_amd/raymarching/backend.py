@@ -363,6 +363,68 @@ def sdf_sigmas_backward(grad_sigmas, sdf, normals, dirs, deltas, inv_s, M, cos_a
                   capi.ptr(grad_sdf), capi.ptr(grad_normals), capi.ptr(grad_dirs), capi.ptr(grad_inv_s), capi.ptr(ws), n, capi.stream()))
 
 
+def _counts(t, name, words):
+    capi.dense(t, name)
+    if t.dtype != torch.int32 or t.numel() < words:
+        raise RuntimeError(f"{name} must be an int tensor of at least {words} element(s)")
+    return t
+
+
+def _volume_dims(volume):
+    _f32(volume, 'volume')
+    if volume.dim() != 3:
+        raise RuntimeError(f"volume must be [nz, ny, nx] (got {tuple(volume.shape)})")
+    nz, ny, nx = volume.shape
+    return nx, ny, nz
+
+
+def surface_nets_workspace(volume):
+    """the workspace ngp_surface_nets_count and _emit share for this volume (uint8 tensor)"""
+    nx, ny, nz = _volume_dims(volume)
+    n = int(capi.lib.ngp_surface_nets_workspace_bytes(nx, ny, nz)) if nx * ny * nz < (1 << 31) else 0   # (ctypes would wrap a larger extent)
+    if n == 0:
+        raise RuntimeError(f"surface_nets: every dimension must be at least 2 and nx * ny * nz below 2^31 (got {nx} x {ny} x {nz})")
+    return torch.empty(n, dtype=torch.uint8, device=volume.device)
+
+
+def surface_nets_count(volume, level, inside_below, workspace, counts):
+    """extension (include/ngp_hip.h, ngp_surface_nets_count): counts[0] = vertices, counts[1] = triangles (int32 [2]; -1: does not fit)"""
+    nx, ny, nz = _volume_dims(volume)
+    capi.dense(workspace, 'workspace'); _counts(counts, 'counts', 2)
+    capi.check(capi.lib.ngp_surface_nets_count(capi.ptr(volume), nx, ny, nz, float(level), int(bool(inside_below)), capi.ptr(workspace),
+                                               capi.ptr(counts), capi.stream()))
+
+
+def surface_nets_emit(volume, level, inside_below, origin, spacing, workspace, vertices, faces):
+    """extension (ngp_surface_nets_emit), after surface_nets_count with the same volume, level, sense and workspace: vertices [v_cap,3] fp32,
+    faces [f_cap,3] int32; raises ('truncated') when a capacity is below its count -- nothing is written past the buffers"""
+    nx, ny, nz = _volume_dims(volume)
+    _f32(vertices, 'vertices'); _i32(faces, 'faces'); capi.dense(workspace, 'workspace')
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f"surface_nets: expected vertices [V,3] and faces [F,3] (got {tuple(vertices.shape)}, {tuple(faces.shape)})")
+    (ox, oy, oz), (hx, hy, hz) = (float(v) for v in origin), (float(v) for v in spacing)
+    capi.check(capi.lib.ngp_surface_nets_emit(capi.ptr(volume), nx, ny, nz, float(level), int(bool(inside_below)), ox, oy, oz, hx, hy, hz,
+                                              capi.ptr(workspace), capi.ptr(vertices), vertices.shape[0], capi.ptr(faces), faces.shape[0],
+                                              capi.stream()))
+
+
+def lattice_points(origin, spacing, nx, ny, z0, z1, bitfield, bound, C, H, dilate, points, index, count):
+    """extension (ngp_lattice_points): the lattice points of the z-slab [z0, z1) near occupied space, compacted in lattice order; points
+    [capacity,3] fp32, index [capacity] int32, count int32 [1] = K (the full count)"""
+    _f32(points, 'points'); _i32(index, 'index'); _counts(count, 'count', 1)
+    if bitfield is not None:
+        capi.dense(bitfield, 'bitfield')
+        if bitfield.dtype != torch.uint8 or bitfield.numel() * 8 < C * H ** 3:
+            raise RuntimeError(f"bitfield must be a uint8 tensor of at least {C} * {H}^3 / 8 bytes")
+    if points.dim() != 2 or points.shape[1] != 3 or index.numel() < points.shape[0]:
+        raise RuntimeError(f"lattice_points: expected points [capacity,3] and index [capacity] (got {tuple(points.shape)}, {tuple(index.shape)})")
+    n = int(capi.lib.ngp_lattice_points_workspace_bytes(nx, ny, max(z1 - z0, 0)))
+    ws = torch.empty(max(n, 4), dtype=torch.uint8, device=points.device)
+    (ox, oy, oz), (hx, hy, hz) = (float(v) for v in origin), (float(v) for v in spacing)
+    capi.check(capi.lib.ngp_lattice_points(ox, oy, oz, hx, hy, hz, nx, ny, z0, z1, capi.ptr(bitfield), float(bound), C, H, dilate, capi.ptr(ws),
+                                           capi.ptr(points), capi.ptr(index), capi.ptr(count), points.shape[0], capi.stream()))
+
+
 def _accept_half(fn):
     """the reference dispatches its raymarching entry points on the tensor dtype (AT_DISPATCH_FLOATING_TYPES_AND_HALF, raymarching.cu:486);
     its own wrappers always hand over fp32 (custom_fwd(cast_inputs=float32)), so fp16 is unreachable from them.  For direct `_backend`

@@ -23,7 +23,7 @@ from . import backend as _geo  # the geometry compositor's entries are ctypes-on
 
 __all__ = ['near_far_from_aabb', 'sph_from_ray', 'morton3D', 'morton3D_invert', 'packbits', 'packbits_capped', 'march_rays_train',
            'composite_rays_train', 'composite_rays_train_geo', 'composite_rays_train_features', 'sample_ts', 'ray_points', 'march_rays', 'composite_rays', 'composite_rays_features', 'compact_rays', 'update_density_grid', 'density_grid_state',
-           'sdf_sigmas']
+           'sdf_sigmas', 'surface_nets', 'lattice_points', 'lattice_frame']
 
 _f32_fwd = custom_fwd(device_type='cuda', cast_inputs=torch.float32)
 
@@ -365,6 +365,61 @@ def sdf_sigmas(sdf, normals, dirs, deltas, inv_s, cos_anneal=1.0):
 
 
 sdf_sigmas.__doc__ = _sdf_sigmas.__doc__
+
+
+def surface_nets(volume, level, inside_below=False, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0)):
+    """extension (include/ngp_hip.h, ngp_surface_nets_count / _emit): the level set of volume [nz,ny,nx] (fp32, on the device)
+    as an indexed triangle mesh by naive surface nets -> vertices [V,3] fp32 (x, y, z = fma(lattice, spacing, origin)), faces [F,3] int32,
+    normals pointing from inside (above the level; inside_below: below it, as for an SDF) to outside.  Deterministic: the same bits on every
+    run.  An export op: the two counts are read back between the two native calls.  An empty result is two zero-row tensors."""
+    volume = volume.detach()
+    ws = _geo.surface_nets_workspace(volume)
+    counts = torch.empty(2, dtype=torch.int32, device=volume.device)
+    _geo.surface_nets_count(volume, level, inside_below, ws, counts)
+    n_vertices, n_faces = counts.tolist()
+    if n_vertices < 0 or n_faces < 0:
+        raise RuntimeError("surface_nets: the mesh does not fit int32 indices (more than 2^31 - 1 vertices or triangles)")
+    vertices = torch.empty(n_vertices, 3, dtype=torch.float32, device=volume.device)
+    faces = torch.empty(max(n_faces, 1), 3, dtype=torch.int32, device=volume.device)   # (the entry refuses a zero capacity)
+    if n_vertices > 0:
+        _geo.surface_nets_emit(volume, level, inside_below, origin, spacing, ws, vertices, faces)
+    return vertices, faces[:n_faces]
+
+
+def lattice_frame(lo, hi, dims):
+    """the lattice of dims = (nx, ny, nz) points spanning [lo, hi] -> (origin, spacing), three Python floats each that are fp32 values:
+    spacing = (hi - lo) / (N - 1) computed in double and narrowed ONCE -- the `origin` / `spacing` of surface_nets over a volume filled on it"""
+    def triple(v):
+        return [float(x) for x in v] if hasattr(v, '__len__') else [float(v)] * 3
+
+    def narrow(x):
+        return float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
+    lo, hi, dims = triple(lo), triple(hi), [int(n) for n in dims]
+    if len(dims) != 3 or min(dims) < 1:
+        raise RuntimeError(f"lattice: dims must be (nx, ny, nz), each at least 1 (got {dims})")
+    return [narrow(a) for a in lo], [narrow((b - a) / (n - 1)) if n > 1 else 0.0 for a, b, n in zip(lo, hi, dims)]
+
+
+def lattice_points(lo, hi, dims, z0, z1, bitfield=None, bound=1, cascade=1, grid_size=128, dilate=1, device=None):
+    """extension (ngp_lattice_points): the points of the z-slab [z0, z1) of the lattice dims = (nx, ny, nz) over [lo, hi] that
+    lie near occupied space -- one of the (2 dilate + 1)^3 cells of `bitfield` around the point's own cell, at the cascade the marcher would
+    look it up in, is set -- compacted in lattice order -> points [K,3] fp32, index [K] int32 (the linear index (k ny + j) nx + i in the whole
+    lattice).  bitfield None: every point of the slab.  One read-back (K)."""
+    nx, ny, nz = (int(n) for n in dims)
+    if not 0 <= z0 < z1 <= nz:
+        raise RuntimeError(f"lattice_points: the slab [{z0}, {z1}) must be a non-empty range of [0, {nz})")
+    if bitfield is not None:
+        device = bitfield.device
+    elif device is None:
+        device = torch.device('cuda')
+    origin, spacing = lattice_frame(lo, hi, dims)
+    capacity = nx * ny * (z1 - z0)
+    points = torch.empty(capacity, 3, dtype=torch.float32, device=device)
+    index = torch.empty(capacity, dtype=torch.int32, device=device)
+    count = torch.empty(1, dtype=torch.int32, device=device)
+    _geo.lattice_points(origin, spacing, nx, ny, z0, z1, bitfield, bound, cascade, grid_size, dilate, points, index, count)
+    kept = int(count.item())
+    return points[:kept], index[:kept]
 
 
 def _ray_dtype(*tensors):
